@@ -7,13 +7,17 @@ restored cover) over one batch of synthetic uint16 slices already resident in HB
 (N > 1) the RCCL all-gather of every slice's side information and location map (on a side
 stream after embed, overlapped with extract).  `value` / `ms_per_step` are that step.
 
-Side legs in the same JSON line: `lsb` (the reference's own bit-plane LSB pixel path,
-src/codec.py:412-487 + 752-793, bit-exact with it), `inplace` (the PEE step with stego =
-cover), `quality` / `pee.quality` (src/mse.py metrics of the LSB and the MED-PEE stego),
-`c3` (256 x 512^2), `c2` (1 x 2048^2); at N > 1 `ranks` (what each rank ran on).  Prints ONE
-JSON line (rank 0).
+A plain run does only that: set up, warm up, time the steps, write the last step's outputs
+(`--dump-outputs DIR`) and print the result line.  Everything else runs under `--full`, in
+the same JSON line: the round-trip checks of the state the timed steps left, the per-kernel
+HIP-event passes and rooflines, the CPU baselines, `lsb` (the reference's own bit-plane LSB
+pixel path, src/codec.py:412-487 + 752-793, bit-exact with it), `inplace` (the PEE step with
+stego = cover), `quality` / `pee.quality` (src/mse.py metrics of the LSB and the MED-PEE
+stego), `c3` (256 x 512^2), `c2` (1 x 2048^2); at N > 1 `c4`, the exchange's own timings and
+`ranks` (what each rank ran on).  Prints ONE JSON line (rank 0).
 
     python bench.py                              # N=1, 256 x 2048^2 ct12, K=20, W=3
+    python bench.py --full                       # ... and every side leg, check and baseline
     torchrun --nproc-per-node N bench.py --gpus N
 """
 from __future__ import annotations
@@ -43,6 +47,12 @@ def parse():
     ap.add_argument("--kind", default="ct12", choices=["ct12", "u16"])
     ap.add_argument("--payload-chars", type=int, default=1024)
     ap.add_argument("--pee-T", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks, per-kernel passes, CPU baselines and side legs (the options "
+                         "below choose among them); off: only the headline step is set up, timed and reported")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step returned (stego, location map, side "
+                         "information, recovered payload, restored cover) as DIR/<name>.npy (rank 0)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
                     help="CPU-baseline budget of the MED-PEE oracle (0 = skip every CPU baseline)")
     ap.add_argument("--cpu-ref-seconds", type=float, default=6.0,
@@ -304,9 +314,15 @@ def cpu_baseline_pool(args, which: str, per_worker: int = 0):
 
 
 # ------------------------------------------------------------------ helpers
+PROFILE_MAX_STEPS = 256   # of a per-kernel pass: the mean launch time needs no more, and the
+#                           window holds at most 2^20 launches (codec_profile_begin)
+
+
 def _profile(lib, _lib, fn, steps):
+    """Mean HIP-event time per kernel tag over min(steps, PROFILE_MAX_STEPS) calls of fn."""
     import ctypes as C
     import torch
+    steps = max(1, min(int(steps), PROFILE_MAX_STEPS))
     cap = 64 * steps
     _lib.check(lib.codec_profile_begin(cap), "codec_profile_begin")
     for _ in range(steps):
@@ -369,9 +385,45 @@ def _roof(kernel, by, t_ms, traffic=None):
     return r
 
 
+# ------------------------------------------------------------------ --dump-outputs
+DUMP_MAX_ELEMS = 1 << 21   # per array: 8 MiB as float32, so the step's five arrays stay below 64 MB
+DUMP_SEED = 0x5EED
+
+
+def _dump_array(torch, t):
+    """A tensor as a float array that holds its values exactly: 1- and 2-byte integers as
+    float32 (2-byte ones read as unsigned), 4-byte ones as float64, 8-byte words as their four
+    unsigned 16-bit pieces (little endian) in float32.  An array of more than DUMP_MAX_ELEMS
+    elements is cut to a fixed sample: flat indices drawn from DUMP_SEED and the element count
+    alone, ascending, so every run and every build dumps the same elements."""
+    size = t.element_size()
+    v = t.contiguous()
+    if size in (2, 8):
+        v = v.view(torch.int16)
+    shape = tuple(v.shape)
+    flat = v.reshape(-1)
+    if flat.numel() > DUMP_MAX_ELEMS:
+        g = torch.Generator()
+        g.manual_seed(DUMP_SEED)
+        idx = torch.randint(0, flat.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+        shape = (DUMP_MAX_ELEMS,)
+    a = flat.cpu().numpy()
+    if a.dtype == np.int16:
+        a = a.view(np.uint16)
+    return a.astype(np.float64 if size == 4 else np.float32).reshape(shape)
+
+
+def dump_outputs(torch, dirname, outputs):
+    """--dump-outputs: one DIR/<name>.npy per array of `outputs` (see _dump_array)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in outputs.items():
+        np.save(os.path.join(dirname, name + ".npy"), _dump_array(torch, t))
+
+
 # ------------------------------------------------------------------ MED-PEE (headline)
 def bench_pee(args, torch, dist, world, rank, dev, covers, B, H, W, *, inplace=False, exchange=False,
-              steps=None, kind=None, T=None, graph=False):
+              steps=None, kind=None, T=None, graph=False, dump=False):
     """MED-PEE embed + extract over one resident batch (1 KB payload per slice).
     Out of place at 2048^2: k_pee_embed1 (one pass: copy + look-back cursor + embed) and
     k_pee_extract1 (one pass: copy + look-back cursor + recover).  In place (and small
@@ -379,7 +431,11 @@ def bench_pee(args, torch, dist, world, rank, dev, covers, B, H, W, *, inplace=F
     k_pee_extract_ss (one workgroup per slice); in place only the items up to each slice's
     `end` are read and written.  exchange (N > 1):
     the side information + location maps of every slice to every rank
-    (distributed.PeeRecordExchange), on a side stream overlapped with extract."""
+    (distributed.PeeRecordExchange), on a side stream overlapped with extract.
+    Without --full the timing is all: no check of the state the steps left, no per-kernel
+    pass, no exchange-only timing.  dump: `_outputs` holds what the last timed step returned
+    (the location map with the bits past each slice's `end`, which the embed leaves
+    unwritten, cleared)."""
     from codec_tcc_amd import _lib, synth
     from codec_tcc_amd import distributed as D
     from codec_tcc_amd.pee import PeeCodec, PeeEncoded
@@ -427,6 +483,14 @@ def bench_pee(args, torch, dist, world, rank, dev, covers, B, H, W, *, inplace=F
             step()
     mine = {}
     el = _timed(torch, dist, world, dev, step, steps, local=mine)
+    res = {"value": round(B * H * W * world * steps / el / 1e6, 1), "unit": "Mpixels/s",
+           "ms_per_step": round(el / steps * 1e3, 4), "T": T,
+           "_rank_ms_per_step": round(mine["s"] / steps * 1e3, 4)}
+    if dump:
+        res["_outputs"] = {"stego": stego, "location_map": D.map_prefix(meta, lm, codec.lm_words),
+                           "side_info": meta.view(torch.int32), "payload": outw, "cover": cov2}
+    if not args.full:
+        return res
     # correctness of the state the timed steps left (outside the timed region): restored
     # cover, recovered payload bits, per-slice status and the decode-side look-back flag
     recs = PeeEncoded(stego, lm, meta, packed[1], pw).records()
@@ -434,9 +498,7 @@ def bench_pee(args, torch, dist, world, rank, dev, covers, B, H, W, *, inplace=F
     cover_ok = bool(torch.equal(cov2.view(torch.int16), covers.view(torch.int16)))
     pay_ok = payload_equal(outw, packed[0], nbits)
     flags_ok = all(r.status in (0, 1) for r in recs) and not codec.lookback_failed(pw)
-    res = {"value": round(B * H * W * world * steps / el / 1e6, 1), "unit": "Mpixels/s",
-           "ms_per_step": round(el / steps * 1e3, 4), "T": T,
-           "_rank_ms_per_step": round(mine["s"] / steps * 1e3, 4),
+    res.update({
            "roundtrip_ok": cover_ok and pay_ok and flags_ok and all(r.status == 0 for r in recs),
            "cover_ok": cover_ok, "payload_ok": pay_ok, "lookback_ok": flags_ok,
            "end_candidates_mean": float(np.mean([r.end + 1 for r in recs])),
@@ -446,7 +508,7 @@ def bench_pee(args, torch, dist, world, rank, dev, covers, B, H, W, *, inplace=F
            # slices whose payload exceeds the T-capacity (truncated, still exactly reversible;
            # roundtrip_ok then reads False): uniform-noise slices at T=2
            "overflow_slices": int(sum(1 for r in recs if r.status == 1)),
-           "repaired_slices": codec.repaired(pw)}
+           "repaired_slices": codec.repaired(pw)})
     if graph:
         res["launch"] = "hip_graph"
         res["eager"] = {"value": round(B * H * W * world * steps / el_eager / 1e6, 1),
@@ -963,7 +1025,7 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     pools = {}
     cpu_base = None
-    if args.cpu_seconds > 0 and world == 1:
+    if args.full and args.cpu_seconds > 0 and world == 1:
         # before anything touches the GPU: the baselines run in forked, core-pinned children
         cpu_base = cpu_baseline(args)
         if args.cpu_pool > 0:
@@ -993,27 +1055,32 @@ def main():
     B, H, W = args.batch, args.size, args.size
     covers = make_covers(torch, args.kind, B, H, W, dev, seed=rank * B)
 
-    head = bench_pee(args, torch, dist, world, rank, dev, covers, B, H, W, exchange=world > 1)
-    pee_stego = head.pop("_stego")
-    if rank == 0:   # MED-PEE stego quality (src/mse.py metrics) beside the LSB one
-        head["quality"] = bench_quality(args, torch, covers, pee_stego, B, H, W)
-    del pee_stego
-    inplace = bench_pee(args, torch, dist, world, rank, dev, covers, B, H, W, inplace=True)
-    lsb = None
-    quality = None
-    if args.lsb:
-        lsb = bench_lsb(args, torch, dist, world, rank, dev, covers, B, H, W, exchange=world > 1)
-        stego = lsb.pop("_stego")
-        lsb["inplace"] = bench_lsb_inplace(args, torch, dist, world, dev, covers, B, H, W)
-        quality = bench_quality(args, torch, covers, stego, B, H, W) if rank == 0 else None
-        del stego
-    c4 = bench_c4(args, torch, dist, world, rank, dev) if (world > 1 and args.c3) else None
-    ranks = None
-    if world > 1:
-        ranks = gather_rank_records(torch, dist, world,
-                                    rank_record(torch, dist, rank, local, dev, args.backend, head, c4), args.backend)
-    c3 = bench_c3(args, torch, dist, world, dev, rank) if (rank == 0 and args.c3) else None
-    c2 = bench_c2(args, torch, dev, rank) if (rank == 0 and args.c2 and world == 1) else None
+    head = bench_pee(args, torch, dist, world, rank, dev, covers, B, H, W, exchange=world > 1,
+                     dump=bool(args.dump_outputs) and rank == 0)
+    outputs = head.pop("_outputs", None)
+    if outputs is not None:
+        dump_outputs(torch, args.dump_outputs, outputs)
+        del outputs
+    inplace = lsb = quality = c4 = ranks = c3 = c2 = None
+    if args.full:
+        pee_stego = head.pop("_stego")
+        if rank == 0:   # MED-PEE stego quality (src/mse.py metrics) beside the LSB one
+            head["quality"] = bench_quality(args, torch, covers, pee_stego, B, H, W)
+        del pee_stego
+        inplace = bench_pee(args, torch, dist, world, rank, dev, covers, B, H, W, inplace=True)
+        if args.lsb:
+            lsb = bench_lsb(args, torch, dist, world, rank, dev, covers, B, H, W, exchange=world > 1)
+            stego = lsb.pop("_stego")
+            lsb["inplace"] = bench_lsb_inplace(args, torch, dist, world, dev, covers, B, H, W)
+            quality = bench_quality(args, torch, covers, stego, B, H, W) if rank == 0 else None
+            del stego
+        c4 = bench_c4(args, torch, dist, world, rank, dev) if (world > 1 and args.c3) else None
+        if world > 1:
+            ranks = gather_rank_records(torch, dist, world,
+                                        rank_record(torch, dist, rank, local, dev, args.backend, head, c4),
+                                        args.backend)
+        c3 = bench_c3(args, torch, dist, world, dev, rank) if (rank == 0 and args.c3) else None
+        c2 = bench_c2(args, torch, dev, rank) if (rank == 0 and args.c2 and world == 1) else None
 
     if rank == 0:
         out = {
@@ -1030,15 +1097,18 @@ def main():
                                       "per-slice PEE side information + location maps (side stream, overlapped "
                                       "with extract)" if world > 1 else ""),
                        "global_batch": B * world, "slice": f"{H}x{W}", "parallelism": f"slices/{world} GPUs"},
-            "roofline": head.get("roofline"),
-            "embed_read_roofline_frac": head.get("embed_read_roofline_frac"),
             "step_hbm_gbs": round(B * H * W * 8 / (head["ms_per_step"] / 1e3) / 1e9, 1),
-            "kernels_ms": head["kernels_ms"],
-            "roundtrip_ok": head["roundtrip_ok"],
-            "pee": {k: v for k, v in head.items() if k not in ("value", "ms_per_step", "roofline", "kernels_ms",
-                                                                 "roundtrip_ok", "embed_read_roofline_frac")},
-            "inplace": inplace,
         }
+        if args.full:
+            out.update({
+                "roofline": head.get("roofline"),
+                "embed_read_roofline_frac": head.get("embed_read_roofline_frac"),
+                "kernels_ms": head["kernels_ms"],
+                "roundtrip_ok": head["roundtrip_ok"],
+                "pee": {k: v for k, v in head.items() if k not in ("value", "ms_per_step", "roofline", "kernels_ms",
+                                                                     "roundtrip_ok", "embed_read_roofline_frac")},
+                "inplace": inplace,
+            })
         if lsb is not None:
             out["lsb"] = lsb
             out["quality"] = quality

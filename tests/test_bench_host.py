@@ -96,6 +96,36 @@ def test_committed_pmc_summaries_resolve_every_bench_instance():
         assert "profiles/r06/" in bench.pmc_traffic(tag, *shape, "ct12", {2: "false"} if tag == "k_pee_embed1" else {})["source"]
 
 
+def test_dump_array_is_exact_and_samples_deterministically(tmp_path, monkeypatch):
+    """--dump-outputs: every integer width comes back exactly from its float array (uint16
+    as unsigned, 64-bit words as four little-endian 16-bit pieces, int32 in float64), and an
+    array above the element cap is cut to the same ascending sample on every call."""
+    import numpy as np
+    import torch
+    u16 = torch.from_numpy(np.array([[0, 1, 4095], [32768, 65534, 65535]], dtype=np.uint16))
+    a = bench._dump_array(torch, u16)
+    assert a.dtype == np.float32 and a.shape == (2, 3)
+    np.testing.assert_array_equal(a, u16.numpy().astype(np.float32))
+    w = torch.tensor([[-1, 0x0123456789ABCDEF], [1 << 62, -(1 << 63)]], dtype=torch.int64)
+    a = bench._dump_array(torch, w)
+    assert a.dtype == np.float32 and a.shape == (2, 8)
+    np.testing.assert_array_equal(a.astype(np.uint16).view(np.int64), w.numpy())
+    i32 = torch.tensor([[-(1 << 31), -1, 0, (1 << 31) - 1]], dtype=torch.int32)
+    a = bench._dump_array(torch, i32)
+    assert a.dtype == np.float64 and np.array_equal(a, i32.numpy().astype(np.float64))
+    a = bench._dump_array(torch, torch.arange(256, dtype=torch.uint8).view(16, 16))
+    assert a.dtype == np.float32 and np.array_equal(a.ravel(), np.arange(256))
+    # above the cap: a fixed ascending sample of the flat elements
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 100)
+    big = torch.arange(101 * 7, dtype=torch.int16).view(101, 7)      # value = flat index
+    s1, s2 = bench._dump_array(torch, big), bench._dump_array(torch, big.clone())
+    assert s1.shape == (100,) and np.array_equal(s1, s2) and np.all(np.diff(s1) >= 0)
+    assert s1.min() >= 0 and s1.max() < 101 * 7 and len(np.unique(s1)) > 50
+    bench.dump_outputs(torch, str(tmp_path / "d"), {"x": u16, "big": big})
+    assert np.array_equal(np.load(tmp_path / "d" / "big.npy"), s1)
+    assert np.array_equal(np.load(tmp_path / "d" / "x.npy"), u16.numpy().astype(np.float32))
+
+
 def _launcher(env_extra):
     """bench.py --gpus 2 --backend gloo without a launcher, ranks driven by the fault knobs
     (they act right after init_process_group, before any GPU call, so this runs on CPU)."""

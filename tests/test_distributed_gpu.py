@@ -136,7 +136,7 @@ def test_bench_launches_its_own_ranks():
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--backend", "gloo", "--batch", "8",
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--batch", "8",
            "--size", "512", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--c2", "0", "--no-profile",
            "--payload-chars", "256"]   # within a 512^2 slice's T = 2 capacity
     r = subprocess.run(cmd, env=env, cwd=repo, capture_output=True, text=True, timeout=540)
@@ -175,7 +175,7 @@ def test_bench_eight_ranks_rehearsal():
     from test_bench_host import _gone, _kill_all
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    cmd = [sys.executable, "-u", os.path.join(repo, "bench.py"), "--gpus", "8", "--backend", "gloo", "--batch", "4",
+    cmd = [sys.executable, "-u", os.path.join(repo, "bench.py"), "--full", "--gpus", "8", "--backend", "gloo", "--batch", "4",
            "--size", "512", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--c2", "0", "--no-profile",
            "--payload-chars", "256"]
     proc = subprocess.Popen(cmd, env=env, cwd=repo, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)

@@ -138,3 +138,80 @@ def test_headline_pee_256x2048(ss, monkeypatch):
     if ss != "auto":
         monkeypatch.setenv("CODEC_PEE_SS", ss)
     _pee_batch_check(_batch(256, 2048, 2048, seed=11), sample=(0, 101, 255))
+
+
+def test_profile_pass_is_bounded_for_any_step_count():
+    """bench._profile with a step count whose launches would not fit the library's event
+    window (64 x steps > 2^20, e.g. the C2 leg's 10 x --steps of a long run): the pass runs
+    PROFILE_MAX_STEPS calls and returns the kernel's mean time instead of failing."""
+    import bench
+    from codec_tcc_amd import _lib
+    from codec_tcc_amd import quality as Q
+    a = _batch(2, 64, 64, seed=5)
+    b = _batch(2, 64, 64, seed=6)
+    calls = []
+
+    def fn():
+        calls.append(1)
+        Q.moments(a, b)
+
+    kern = bench._profile(_lib.load(), _lib, fn, 10 * 2000)
+    assert len(calls) == bench.PROFILE_MAX_STEPS and 64 * bench.PROFILE_MAX_STEPS <= 1 << 20
+    assert kern.get("k_quality", 0) > 0, kern
+    few = []
+    bench._profile(_lib.load(), _lib, lambda: (few.append(1), Q.moments(a, b)), 3)
+    assert len(few) == 3
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """`bench.py` without --full: the line holds the headline figure only (--steps timed
+    steps, ms_per_step and value consistent with each other), none of the side legs, checks
+    or baselines; --dump-outputs writes the last step's arrays as float32 / float64 .npy,
+    and they equal an embed + extract made here from the same seeds (so the inputs of a run
+    are a function of its arguments alone)."""
+    import json
+    import subprocess
+
+    import bench
+    from codec_tcc_amd import distributed as D
+    from codec_tcc_amd.pee import PeeCodec
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B, H, chars = 3, 256, 64
+    out_dir = tmp_path / "outputs"
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--batch", str(B), "--size", str(H), "--payload-chars", str(chars), "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["metric"] == bench.METRIC and out["unit"] == "Mpixels/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "u16" and out["n_gpus"] == 1 and out["steps"] == 2 and out["warmup"] == 1
+    assert out["ms_per_step"] > 0
+    # value and ms_per_step are rounded to 1 and 4 decimals: half a unit of each, relative
+    px = B * H * H / 1e6
+    assert out["value"] == pytest.approx(px / (out["ms_per_step"] / 1e3),
+                                         rel=0.5e-4 / out["ms_per_step"] + 0.05 / out["value"] + 1e-9)
+    for moved in ("pee", "inplace", "lsb", "quality", "c3", "c2", "cpu_baseline", "kernels_ms", "roofline",
+                  "roundtrip_ok"):
+        assert moved not in out, moved
+    # the same step made here from the same seeds
+    dev = torch.device("cuda", torch.cuda.current_device())
+    covers = bench.make_covers(torch, "ct12", B, H, H, dev, seed=0)
+    codec = PeeCodec(B, H, H, dtype="uint16", T=2, device=dev)
+    enc = codec.embed(covers, [synth.payload(chars, 99 + i) for i in range(B)])
+    words, cover = codec.extract(enc.stego, enc.meta, enc.lm, payload_words=enc.payload_words)
+    want = {"stego": enc.stego.cpu().numpy(), "cover": cover.cpu().numpy(),
+            "side_info": enc.meta.view(torch.int32).cpu().numpy(),
+            "payload": words.cpu().numpy().view(np.uint16),
+            "location_map": D.map_prefix(enc.meta, enc.lm, codec.lm_words).cpu().numpy().view(np.uint16)}
+    assert sorted(os.listdir(out_dir)) == sorted(n + ".npy" for n in want)
+    total = 0
+    for name, w in want.items():
+        got = np.load(out_dir / (name + ".npy"))
+        total += got.nbytes
+        assert got.dtype == (np.float64 if name == "side_info" else np.float32), name
+        np.testing.assert_array_equal(got, w.astype(got.dtype), err_msg=name)
+    assert total <= 64e6
+    np.testing.assert_array_equal(want["cover"], covers.cpu().numpy())

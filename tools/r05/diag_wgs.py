@@ -16,7 +16,8 @@ def main():
     B = int(os.environ.get("DIAG_B", "256"))
     H = W = 2048
     covers = bench.make_covers(torch, "ct12", B, H, W, dev, 0)
-    args = types.SimpleNamespace(payload_chars=1024, pee_T=2, warmup=1, steps=2, no_profile=True, kind="ct12")
+    args = types.SimpleNamespace(payload_chars=1024, pee_T=2, warmup=1, steps=2, no_profile=True, kind="ct12",
+                                 full=True)   # the round-trip fields are bench.py's --full part
     for wgs in sys.argv[1:]:
         if wgs == "default":
             os.environ.pop("CODEC_PEE_1P_WGS", None)

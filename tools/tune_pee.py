@@ -39,7 +39,8 @@ def main():
     B, H, W = a.batch, a.size, a.size
     covers = bench.make_covers(torch, a.kind, B, H, W, dev, 0)
     T = a.T if a.T == "auto" else int(a.T)
-    args = types.SimpleNamespace(payload_chars=1024, pee_T=T, warmup=2, steps=10, no_profile=False, kind=a.kind)
+    args = types.SimpleNamespace(payload_chars=1024, pee_T=T, warmup=2, steps=10, no_profile=False, kind=a.kind,
+                                 full=True)   # the round-trip check and kernels_ms are bench.py's --full part
     modes = [m == "ip" for m in a.modes.split(",")]
     res = {}
     for _ in range(a.rounds):
