@@ -50,7 +50,7 @@ def _obj(src: str) -> str:
 
 
 def _common_deps():
-    return HDRS + [os.path.join(INC, "codec_tcc.h")]
+    return HDRS + [os.path.join(INC, "codec_tcc.h"), os.path.join(INC, "codec_tcc_ext.h")]
 
 
 def _digest(paths, flags) -> str:

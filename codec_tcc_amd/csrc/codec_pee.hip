@@ -13,6 +13,7 @@
 //   extract: k_pee_copy (stego->cover) + k_pee_dcount (prefix tiles) + k_pee_offsets
 //            -> k_pee_recover (prefix tiles: bits + restored pixels)
 #include "codec_common.h"
+#include "codec_tcc_ext.h"
 
 #include <map>
 #include <mutex>
@@ -4458,6 +4459,145 @@ __global__ __launch_bounds__(LSS_THREADS) void k_pee_lat_ss(const T* __restrict_
     }
 }
 
+// ---- scheme 2, capacity-controlled (codec_pee_multi_embed_auto, include/codec_tcc_ext.h): the
+// slice's workgroup scans T = tmin .. tmax itself.  A trial is the copy cover -> stego (which
+// also undoes a failed trial's pixels) and the four embed passes of k_pee_lat_ss<.., EXTRACT =
+// false, .., PF = true> at p_first = 0 -- the same chunk walk, records, map words and sink
+// slots; the body is restated here so that kernel's code is untouched.  The capacity of pass
+// p depends on T and on the bits the earlier passes wrote, so no cover-side count predicts the
+// first T that fits: the trial is the test.  The retry decision is taken from
+// `base` (uniform: every lane holds the scans' totals), lengths[b] and T, so every lane reaches
+// every barrier; the loop runs at most tmax - tmin + 1 times and the workgroup waits on no
+// other.  The payload row is staged once (PL), it does not change between trials.
+template <typename T, bool PL>
+__global__ __launch_bounds__(LSS_THREADS) void k_pee_lat_auto(const T* __restrict__ src, T* dst, int H, int W, int tmin,
+                                                              int tmax, int maxval, int copy_mode,
+                                                              const u64* __restrict__ payload_all, int pw,
+                                                              const int32_t* __restrict__ lengths, codec_pee_meta* metas,
+                                                              int B, u64* lm_all, int lmw, int32_t* __restrict__ t_out,
+                                                              char* __restrict__ sink) {
+    __shared__ uint32_t pad[LSS_PAD_WORDS];   // as k_pee_lat_ss: wave totals, [32]: end, [33]: unsafe count
+    uint32_t (*wtot)[16] = reinterpret_cast<uint32_t (*)[16]>(pad);
+    uint32_t* pay32 = pad + LSS_PAY_BASE;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const size_t npx = (size_t)H * W;
+    T* img = dst + (size_t)b * npx;
+    T* const sink_px = reinterpret_cast<T*>(sink + SS_SINK_SLOT(b, tid));
+    u64* const sink_w = reinterpret_cast<u64*>(sink + SS_SINK_SLOT(b, tid) + 32);
+    const u64* payload = payload_all + (size_t)b * pw;
+    if (PL)
+        for (int w = tid; w < 2 * pw; w += LSS_THREADS) pay32[w] = reinterpret_cast<const uint32_t*>(payload)[w];
+    const uint32_t nbits = 64u * (uint32_t)pw;
+    const int len = lengths[b];
+    int par = 0, Tt = tmin;
+    for (;;) {
+        lss_copy<T>(src + (size_t)b * npx, img, npx, copy_mode);
+        __syncthreads();   // the copy (and, first time, the payload row) visible; the last trial's stores ordered before
+        uint32_t base = 0;   // payload bits taken by this trial's passes so far
+        for (int p = 0; p < 4; ++p) {
+            const PeeLat g = pee_lattice(p, H, W);
+            const int nc = g.hc * g.wc, ntiles = (nc + PEE_TILE - 1) / PEE_TILE;
+            codec_pee_meta* M = metas + (size_t)p * B + b;
+            u64* lm = lm_all + ((size_t)p * B + b) * lmw;
+            const int rem = len - (int)base;
+            if (rem <= 0) {   // nothing left: the pass leaves the slice untouched
+                if (tid == 0) {
+                    M->T = Tt; M->maxval = maxval; M->L = 0; M->end = -1; M->nc = nc; M->ntiles = ntiles;
+                    M->tile_end = -1; M->status = 0; M->capacity = -1; M->lm_count = 0; M->h = H; M->w = W;
+                    M->flags = 0; M->reserved[0] = p; M->reserved[1] = 0; M->reserved[2] = 0;
+                }
+                continue;
+            }
+            int end = nc - 1;   // until the chunk holding the rem-th expandable candidate is found
+            const uint32_t pbase = base, lim = (uint32_t)rem;
+            if (tid == 0) pad[33] = 0;
+            const int kstop = nc - 1;
+            const int nch = kstop >= 0 ? kstop / LSS_CHUNK + 1 : 0;
+            uint32_t cursor = 0, unsafe = 0;   // rank of the chunk's first candidate (uniform); lane's unsafe count
+            int c_done = nch;
+            bool found = false;
+            LatQuad<T> qa;   // the next chunk's candidates, requested before this one is processed
+            if (nch > 0) qa.load(img, W, g, 4 * tid, kstop);
+            for (int c = 0; c < nch; ++c) {
+                const LatQuad<T> cur = qa;
+                qa.load(img, W, g, (c + 1) * LSS_CHUNK + 4 * tid, kstop);   // clamped past kstop
+                const int k0 = c * LSS_CHUNK + 4 * tid;
+                uint32_t n = 0, fl = 0;
+                int ps[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    ps[u] = med3(cur.a[u], cur.b[u], cur.c[u]);
+                    const PeeCand pc = pee_classify(cur.x[u], cur.a[u], cur.b[u], cur.c[u], Tt, maxval);
+                    const bool in = k0 + u < nc;
+                    fl |= ((in & pc.expand & pc.safe) ? 1u : 0u) << u | ((in & pc.safe) ? 16u : 0u) << u |
+                          ((in & pc.right) ? 256u : 0u) << u | (in ? 4096u : 0u) << u;
+                    n += (in & pc.expand & pc.safe) ? 1u : 0u;
+                }
+                uint32_t ex, tot, wb;
+                ss_scan_small(n, wtot, par, &ex, &tot, &wb);
+                par ^= 1;
+                // candidate k is processed iff fewer than lim expandable ones precede it
+                const bool last = cursor + tot >= lim;   // this chunk holds the lim-th (uniform)
+                uint32_t r = cursor + ex, nib = 0;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const bool proc = ((fl >> (12 + u)) & 1u) && r < lim;   // before nc and up to end
+                    const bool safe = (fl >> (4 + u)) & 1u, es = (fl >> u) & 1u;
+                    nib |= (proc && !safe) ? 1u << u : 0u;
+                    unsafe += (proc && !safe) ? 1u : 0u;
+                    const uint32_t bi = pbase + r;
+                    uint32_t bit;
+                    if (PL) {
+                        const uint32_t wv = pay32[min(bi >> 5, (uint32_t)(2 * pw - 1))];
+                        bit = bi < nbits ? (wv >> (bi & 31)) & 1u : 0u;
+                    } else {
+                        bit = (proc && es && bi < nbits) ? (uint32_t)((payload[bi >> 6] >> (bi & 63)) & 1ull) : 0u;
+                    }
+                    if (proc && es && r + 1 == lim) pad[32] = (uint32_t)(k0 + u);
+                    const int nv = es ? ps[u] + 2 * (cur.x[u] - ps[u]) + (int)bit
+                                      : (((fl >> (8 + u)) & 1u) ? cur.x[u] + Tt : cur.x[u] - Tt);
+                    *(proc && safe ? img + cur.o[u] : sink_px) = (T)nv;
+                    r += (proc && es) ? 1u : 0u;
+                }
+                // this chunk's map words (its 16-lane rows); in the chunk holding `end` only those
+                // of tiles <= end's tile
+                const u64 word = row_or16_64((u64)nib << (4 * (lane & 15)));
+                int tile_lim = ntiles - 1;
+                if (last) {
+                    lds_barrier();   // pad[32] (end) visible
+                    end = (int)pad[32];
+                    tile_lim = end / PEE_TILE;
+                    found = true;
+                }
+                const int w = k0 >> 6;
+                *((lane & 15) == 0 && w < lmw && (k0 / PEE_TILE) <= tile_lim ? lm + w : sink_w) = word;
+                cursor += tot;
+                if (last) { c_done = c + 1; break; }
+            }
+            if (unsafe) atomicAdd(&pad[33], unsafe);   // rare: candidates whose transform would overflow
+            __syncthreads();   // pad[33] complete; the next pass reads this lattice's pixels
+            if (tid == 0) {
+                M->T = Tt; M->maxval = maxval; M->nc = nc; M->ntiles = ntiles; M->h = H; M->w = W;
+                M->lm_count = (int)pad[33];
+                M->reserved[0] = p; M->reserved[1] = 0; M->reserved[2] = 0;
+                if (!found) {   // the pass fills up: its capacity's bits, every candidate processed
+                    M->L = (int)cursor; M->end = nc - 1; M->tile_end = ntiles - 1; M->status = 1;
+                    M->capacity = (int)cursor; M->flags = 0;
+                } else {
+                    M->L = (int)lim; M->end = end; M->tile_end = end / PEE_TILE; M->status = 0;
+                    M->capacity = (int)cursor;   // counted through end's chunk: exact only if it is the last
+                    M->flags = c_done < (nc + LSS_CHUNK - 1) / LSS_CHUNK ? CODEC_PEE_PARTIAL : 0;
+                }
+            }
+            base += found ? lim : cursor;
+            __syncthreads();   // pad[32..33] reusable
+        }
+        if (len - (int)base <= 0 || Tt >= tmax) break;   // uniform: all bits placed, or the last T (kept, truncated)
+        ++Tt;
+    }
+    if (tid == 0) t_out[b] = Tt;
+}
+
 // pass 0 is scheme 1 on its own lattice: its record keeps the number of bits it embedded in L
 // (scheme 1 keeps the requested length there and its capacity when it fills up)
 __global__ __launch_bounds__(256) void k_pee_pass0_fix(codec_pee_meta* __restrict__ metas, int B) {
@@ -4681,6 +4821,39 @@ int codec_pee_multi_extract(const codec_pee_params* P, const void* stego, const 
     }
 #undef PLSX
     LAUNCH_CHECK("k_pee_lat_ss<extract>");
+    return 0;
+}
+
+int codec_pee_multi_embed_auto(const codec_pee_params* P, const void* cover, void* stego, const uint64_t* payload,
+                               const int32_t* lengths, int32_t tmin, int32_t tmax, int32_t* t_out,
+                               codec_pee_meta* metas, uint64_t* lm, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    if (!P) return set_err(CODEC_EINVAL, "params is NULL");
+    if (tmin < 1 || tmax < tmin || tmax > PEE_TMAX_MAX)
+        return set_err(CODEC_EINVAL, "codec_pee_multi_embed_auto: need 1 <= tmin <= tmax <= 64");
+    codec_pee_params Q = *P;   // P->T is ignored: the kernel scans tmin..tmax
+    Q.T = tmin;
+    int rc = pee_multi_check(&Q, 0);
+    if (rc) return rc;
+    if (!cover || !stego || !payload || !lengths || !t_out || !metas || !lm || !workspace)
+        return set_err(CODEC_EINVAL, "codec_pee_multi_embed_auto: NULL pointer argument");
+    if (cover == stego)
+        return set_err(CODEC_EINVAL, "codec_pee_multi_embed_auto: out of place only (a failed trial is undone from the cover)");
+    const PeeWs L = pee_ws(&Q);
+    if (workspace_bytes < L.total) return set_err(CODEC_EINVAL, "workspace too small");
+    hipStream_t st = as_stream(stream);
+    const int cm = pee_lss_copy_mode(&Q, cover, stego);
+    char* sink = static_cast<char*>(workspace) + L.sink;
+    const bool pl = Q.payload_words <= LSS_PAY_MAXW;
+    ProfScope prof(st, CODEC_K_PEE_LAT_AUTO);
+#define PLA(TT, PLV) hipLaunchKernelGGL((k_pee_lat_auto<TT, PLV>), dim3((unsigned)Q.B), dim3(LSS_THREADS), 0, st, \
+                                   static_cast<const TT*>(cover), static_cast<TT*>(stego), Q.H, Q.W, (int)tmin, (int)tmax, \
+                                   Q.maxval, cm, reinterpret_cast<const u64*>(payload), Q.payload_words, lengths, metas, \
+                                   Q.B, reinterpret_cast<u64*>(lm), Q.lm_words, t_out, sink)
+    if (Q.bytes == 2) { if (pl) PLA(uint16_t, true); else PLA(uint16_t, false); }
+    else { if (pl) PLA(uint8_t, true); else PLA(uint8_t, false); }
+#undef PLA
+    LAUNCH_CHECK("k_pee_lat_auto");
     return 0;
 }
 

@@ -8,7 +8,9 @@ oracle/pee_cpu.py (parity unpinned) and summarised in include/codec_tcc.h.
 
 Scheme 2 (PeeCodec(..., scheme=2), oracle/pee_cpu.py "Scheme 2"): four sublattice passes on
 the running image, about four times the capacity at one T; enc.meta / enc.lm then hold one
-record / map per pass ([4, B, ...], pass-major).
+record / map per pass ([4, B, ...], pass-major).  With T="auto" each slice's workgroup tries
+T = tmin .. tmax inside one launch and keeps the first T that holds the payload
+(include/codec_tcc_ext.h, codec_pee_multi_embed_auto).
 """
 from __future__ import annotations
 
@@ -61,17 +63,20 @@ class PeeEncoded:
 
 
 class PeeCodec:
-    def __init__(self, batch: int, height: int, width: int, dtype="uint16", *, T=2, tmax: int = 16,
+    def __init__(self, batch: int, height: int, width: int, dtype="uint16", *, T=2, tmin: int = 1, tmax: int = 16,
                  maxval: Optional[int] = None, device=None, scheme: int = 1):
         """T: the expansion threshold for every slice, or "auto" -- capacity control: each
-        slice gets the smallest T <= tmax whose capacity holds its payload
-        (codec_pee_capacity, one extra read-only pass; meta.T records the choice).
-        scheme: 1 = the (odd, odd) lattice in one pass; 2 = four sublattice passes
-        (codec_pee_multi_embed_pass; integer T only)."""
+        slice gets the smallest T <= tmax whose capacity holds its payload (meta.T records
+        the choice, t_slices holds it per slice).  Scheme 1 reads it off the cover's capacity
+        curve (codec_pee_capacity, one extra read-only pass); scheme 2's capacity depends on
+        the bits already embedded, so its workgroup tries T = tmin, tmin + 1, ... tmax inside
+        one launch (codec_pee_multi_embed_auto; out of place only; a slice no T fits is the
+        truncated T = tmax embedding).  tmin: scheme 2 only.
+        scheme: 1 = the (odd, odd) lattice in one pass; 2 = four sublattice passes."""
         if scheme not in (1, 2):
             raise ValueError("scheme must be 1 or 2")
-        if scheme == 2 and isinstance(T, str):
-            raise ValueError("scheme 2 takes an integer T (capacity control is scheme 1's)")
+        if scheme == 1 and int(tmin) != 1:
+            raise ValueError("tmin is scheme 2's (scheme 1's capacity control starts at T = 1)")
         self.scheme = int(scheme)
         _require_gpu()
         torch = _torch()
@@ -88,11 +93,16 @@ class PeeCodec:
         if not 1 <= int(tmax) <= 64:
             raise ValueError("tmax must be in 1..64")
         self.tmax = int(tmax)
+        if not 1 <= int(tmin) <= self.tmax:
+            raise ValueError("tmin must be in 1..tmax")
+        self.tmin = int(tmin)
         self.maxval = vmax if maxval is None else int(maxval)
         self.nc = (self.H // 2) * (self.W // 2)
         self.lm_words = max(1, (self.nc + 63) // 64)
         self.config = dict(method="pee", T="auto" if self.auto else self.T, tmax=self.tmax, maxval=self.maxval,
                            dtype="uint16" if nbytes == 2 else "uint8", scheme=self.scheme)
+        if self.scheme == 2:
+            self.config["tmin"] = self.tmin
         P = self._params(1)
         ws = _lib.load().codec_pee_workspace_bytes(C.byref(P))
         if ws == 0:
@@ -194,8 +204,12 @@ class PeeCodec:
     def _embed_multi(self, covers, words, lengths, lens_t, stego, lm, meta, check):
         """Scheme 2: passes 0..3 in one library call (codec_pee_multi_embed: one slice-serial
         launch after scheme 1's pass 0 on chip-filling batches, per-pass tile launches
-        otherwise); pass 0 copies cover -> stego, the others run in place."""
+        otherwise); pass 0 copies cover -> stego, the others run in place.  T="auto":
+        codec_pee_multi_embed_auto, one launch that scans T per slice (out of place only)."""
         torch = _torch()
+        if self.auto and _same_storage(covers, stego):
+            raise ValueError("scheme 2 with T='auto' embeds out of place only (a failed trial is undone from "
+                             "the cover): pass a stego buffer other than the covers")
         if lm is None:
             lm = torch.empty((4, self.B, self.lm_words), dtype=torch.int64, device=self.device)
         if meta is None:
@@ -206,9 +220,15 @@ class PeeCodec:
             raise ValueError("scheme 2's lm and meta must be contiguous")
         P = self._params(words.shape[1])
         lib = _lib.load()
-        self._guarded(lambda: _lib.check(lib.codec_pee_multi_embed(
-            C.byref(P), covers.data_ptr(), stego.data_ptr(), words.data_ptr(), lens_t.data_ptr(), meta.data_ptr(),
-            lm.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), _stream()), "codec_pee_multi_embed"))
+        if self.auto:
+            self._guarded(lambda: _lib.check(lib.codec_pee_multi_embed_auto(
+                C.byref(P), covers.data_ptr(), stego.data_ptr(), words.data_ptr(), lens_t.data_ptr(), self.tmin,
+                self.tmax, self.t_slices.data_ptr(), meta.data_ptr(), lm.data_ptr(), self.workspace.data_ptr(),
+                self.workspace.numel(), _stream()), "codec_pee_multi_embed_auto"))
+        else:
+            self._guarded(lambda: _lib.check(lib.codec_pee_multi_embed(
+                C.byref(P), covers.data_ptr(), stego.data_ptr(), words.data_ptr(), lens_t.data_ptr(), meta.data_ptr(),
+                lm.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), _stream()), "codec_pee_multi_embed"))
         enc = PeeEncoded(stego=stego, lm=lm, meta=meta, lengths=list(lengths), payload_words=int(words.shape[1]),
                          config=self.config, scheme=2)
         if check:   # pass 0 in place runs scheme 1's look-back embed
@@ -261,6 +281,9 @@ class PeeCodec:
         d = self.diagnostics(payload_words)
         return d["embed_fallback_chunks"] + d["extract_fallback_chunks"]
 
+    def _t_text(self) -> str:
+        return f"T={'auto, tmax=%d' % self.tmax if self.auto else self.T}"
+
     def decode(self, enc: PeeEncoded):
         """(list of 0/1 bit vectors, restored cover tensor); raises if a slice overflowed."""
         if enc.scheme != self.scheme:
@@ -269,13 +292,13 @@ class PeeCodec:
             got = enc.embedded()
             short = [i for i, (g, n) in enumerate(zip(got, enc.lengths)) if g < n]
             if short:
-                raise ValueError(f"payload exceeds PEE capacity in slices {short} (scheme 2, T={self.T})")
+                raise ValueError(f"payload exceeds PEE capacity in slices {short} (scheme 2, {self._t_text()})")
             words, cover = self.extract(enc.stego, enc.meta, enc.lm, payload_words=enc.payload_words)
             host = words.cpu().numpy()   # the extract passes have no look-back (tile or slice-serial)
             return [framing.unpack_bits(host[i], enc.lengths[i]) for i in range(self.B)], cover
         recs = enc.records()
         _raise_lookback(recs)
-        _raise_status(recs, f"T={'auto, tmax=%d' % self.tmax if self.auto else self.T}")
+        _raise_status(recs, self._t_text())
         words, cover = self.extract(enc.stego, enc.meta, enc.lm, payload_words=enc.payload_words)
         host = words.cpu().numpy()
         if self.lookback_failed(enc.payload_words):
@@ -285,7 +308,11 @@ class PeeCodec:
         return [framing.unpack_bits(host[i], enc.lengths[i]) for i in range(self.B)], cover
 
 
-# one PeeCodec (and its zeroed workspace) per (shape, dtype, T, tmax, maxval, device); the
+def _same_storage(a, b) -> bool:
+    return a is b or a.data_ptr() == b.data_ptr()
+
+
+# one PeeCodec (and its zeroed workspace) per (shape, dtype, T, tmin, tmax, maxval, device); the
 # least recently used one is dropped past _CODECS_MAX entries, so varied shapes do not keep
 # GPU memory alive indefinitely (clear_codec_cache() drops them all)
 _CODECS: "OrderedDict" = OrderedDict()
@@ -297,14 +324,14 @@ def clear_codec_cache():
     _CODECS.clear()
 
 
-def _codec_for(shape, dtype: str, *, T, tmax: int, maxval: Optional[int], scheme: int = 1) -> PeeCodec:
+def _codec_for(shape, dtype: str, *, T, tmax: int, maxval: Optional[int], scheme: int = 1, tmin: int = 1) -> PeeCodec:
     torch = _torch()
     if maxval is None:
         maxval = 65535 if "16" in dtype else 255
-    key = (tuple(shape), dtype, T, int(tmax), int(maxval), int(scheme), torch.cuda.current_device())
+    key = (tuple(shape), dtype, T, int(tmin), int(tmax), int(maxval), int(scheme), torch.cuda.current_device())
     c = _CODECS.get(key)
     if c is None:
-        c = PeeCodec(*shape, dtype=dtype, T=T, tmax=tmax, maxval=maxval, scheme=scheme)
+        c = PeeCodec(*shape, dtype=dtype, T=T, tmin=tmin, tmax=tmax, maxval=maxval, scheme=scheme)
         _CODECS[key] = c
         while len(_CODECS) > _CODECS_MAX:
             _CODECS.popitem(last=False)
@@ -347,12 +374,12 @@ def _config_from_records(enc: "PeeEncoded") -> dict:
 
 
 def encode(covers, payloads: Sequence, *, T=2, tmax: int = 16, maxval: Optional[int] = None,
-           scheme: int = 1) -> PeeEncoded:
+           scheme: int = 1, tmin: int = 1) -> PeeEncoded:
     """MED-PEE embed of one payload per slice (the package's `encode(..., method="pee")`).
     covers: [B,H,W] / [H,W] uint8/uint16 torch tensor or numpy array; T: expansion threshold
     or "auto" (smallest T <= tmax whose capacity holds each slice's payload); maxval: the
     largest legal pixel value (e.g. 4095 for 12-bit DICOM; default the dtype's maximum);
-    scheme 2: four sublattice passes (integer T).
+    scheme 2: four sublattice passes; its T="auto" tries T = tmin .. tmax per slice in one launch.
     Raises ValueError when a payload exceeds its slice's capacity."""
     from .codec import _as_batch
     _require_gpu()
@@ -360,12 +387,12 @@ def encode(covers, payloads: Sequence, *, T=2, tmax: int = 16, maxval: Optional[
     if isinstance(payloads, (str, bytes, bytearray)):
         payloads = [payloads]
     dt = "uint16" if _elem_bytes(covers) == 2 else "uint8"
-    codec = _codec_for(tuple(covers.shape), dt, T=T, tmax=tmax, maxval=maxval, scheme=scheme)
+    codec = _codec_for(tuple(covers.shape), dt, T=T, tmax=tmax, maxval=maxval, scheme=scheme, tmin=tmin)
     enc = codec.embed(covers, payloads)
     if scheme == 2:
         short = [i for i, (g, n) in enumerate(zip(enc.embedded(), enc.lengths)) if g < n]
         if short:
-            raise ValueError(f"payload exceeds PEE capacity in slices {short} (scheme 2, T={T})")
+            raise ValueError(f"payload exceeds PEE capacity in slices {short} (scheme 2, {codec._t_text()})")
     else:
         _raise_status(enc.records(), f"T={T}, tmax={tmax}")
     return enc
@@ -378,7 +405,8 @@ def decode(enc: PeeEncoded, *, restore: bool = True):
     _require_gpu()
     cfg = enc.config or _config_from_records(enc)
     codec = _codec_for(tuple(enc.stego.shape), cfg.get("dtype", "uint16"), T=cfg.get("T", 2),
-                       tmax=cfg.get("tmax", 16), maxval=cfg.get("maxval"), scheme=int(getattr(enc, "scheme", 1)))
+                       tmax=cfg.get("tmax", 16), maxval=cfg.get("maxval"), scheme=int(getattr(enc, "scheme", 1)),
+                       tmin=cfg.get("tmin", 1))
     bits, cover = codec.decode(enc)
     return bits, (cover if restore else None)
 

@@ -138,13 +138,14 @@ def decode_bin_exact(filepath: str, search_block_size: Optional[int] = None) -> 
 
 # ------------------------------------------------------------------ MED-PEE files
 def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxval: Optional[int] = None,
-                    codec: str = "raw", scheme: int = 1) -> Dict:
+                    codec: str = "raw", scheme: int = 1, tmin: int = 1) -> Dict:
     """MED-PEE embed of one slice into a version-16 STGC file.  `image` is an array or a
     DICOM path; maxval defaults to the DICOM's full scale 2**BitsStored - 1 (4095 for the
     reference's 12-bit pe.dcm), else the dtype maximum.  T = 'auto' picks the smallest
     T <= tmax whose capacity holds the payload.  A payload beyond the capacity is truncated
     (status 1, 'L' = bits embedded); the file stays exactly reversible.  scheme 2: four
-    sublattice passes (integer T; container scheme byte 2)."""
+    sublattice passes (container scheme byte 2); with T = 'auto' the smallest T in tmin..tmax whose
+    four passes hold the payload, which the header and the returned 'T' then carry."""
     from .pee import PeeCodec, lm_bits
     _require_gpu()
     torch = _torch()
@@ -158,7 +159,7 @@ def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxva
         raise ValueError("A imagem deve ser 2D uint8 ou uint16.")
     h, w = img.shape
     bits = framing.to_bits(payload)
-    pc = PeeCodec(1, h, w, dtype=str(img.dtype), T=T, tmax=tmax, maxval=maxval, scheme=scheme)
+    pc = PeeCodec(1, h, w, dtype=str(img.dtype), T=T, tmin=tmin, tmax=tmax, maxval=maxval, scheme=scheme)
     enc = pc.embed(torch.from_numpy(np.ascontiguousarray(img)[None]).cuda(), [bits])
     if scheme == 2:
         prs = [pr[0] for pr in enc.pass_records()]
@@ -166,10 +167,11 @@ def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxva
         embedded = enc.embedded()[0]
         status = 1 if embedded < len(bits) else 0
         stego = enc.stego.cpu().numpy()[0]
-        hdr = container.create_pee2_header(codec, img.dtype.itemsize, w, h, pc.T, pc.maxval, embedded, status,
+        t_used = int(prs[0].T)   # T = 'auto': the slice's chosen T (every pass records it)
+        hdr = container.create_pee2_header(codec, img.dtype.itemsize, w, h, t_used, pc.maxval, embedded, status,
                                            [(r.L, r.end, r.status, len(b)) for r, b in zip(prs, blobs)])
         size = container.create_binary_file(out_path, hdr, _compress(stego, codec), b"".join(blobs))
-        return {"path": out_path, "bytes": size, "T": pc.T, "L": embedded, "maxval": pc.maxval, "status": status,
+        return {"path": out_path, "bytes": size, "T": t_used, "L": embedded, "maxval": pc.maxval, "status": status,
                 "scheme": 2, "passes": [{"L": r.L, "end": r.end, "status": r.status, "lm_count": r.lm_count}
                                         for r in prs], "stego": stego}
     r = enc.records()[0]

@@ -375,7 +375,8 @@ int codec_pee_multi_extract_pass(const codec_pee_params* P, int32_t pass, const 
  * copy-fused kernels first); a pass then stops counting at its `end` chunk and its capacity
  * carries CODEC_PEE_PARTIAL as scheme 1's single pass does.  Otherwise the per-pass tile
  * launches run.  No reference counterpart (the reference has no PEE code; oracle/pee_cpu.py
- * pee_embed_multi / pee_extract_multi is the specification). */
+ * pee_embed_multi / pee_extract_multi is the specification).  The capacity-controlled embed
+ * (per-slice smallest T that fits, one launch) is declared in codec_tcc_ext.h. */
 int codec_pee_multi_embed(const codec_pee_params* P, const void* cover, void* stego, const uint64_t* payload,
                           const int32_t* lengths, codec_pee_meta* metas, uint64_t* lm, void* workspace,
                           size_t workspace_bytes, void* stream);
