@@ -152,8 +152,44 @@ def lm_blob(lm_bits: np.ndarray) -> bytes:
 
 
 def lm_from_blob(blob: bytes, end: int) -> np.ndarray:
-    raw = np.frombuffer(zlib.decompress(blob), dtype=np.uint8)
-    return np.unpackbits(raw, bitorder="little")[: end + 1].astype(bool)
+    """Location-map bits of candidates 0..end.  ValueError for a blob that is not zlib or
+    holds fewer than end + 1 bits; at most the bytes those bits need are inflated (one more,
+    to see that nothing follows), so a tiny blob cannot inflate without bound."""
+    end = int(end)
+    if end < 0:
+        return np.zeros(0, dtype=bool)
+    need = (end + 8) // 8
+    d = zlib.decompressobj()
+    try:
+        out = d.decompress(bytes(blob), need + 1)
+    except zlib.error as exc:
+        raise ValueError(f"MED-PEE location-map blob is not valid zlib data ({exc})") from None
+    if len(out) > need:
+        raise ValueError(f"MED-PEE location-map blob inflates past the {need} bytes of end + 1 = {end + 1} bits")
+    if not d.eof:   # every input byte was consumed (the output limit was not reached)
+        raise ValueError("MED-PEE location-map blob is a truncated zlib stream")
+    if len(out) < need:
+        raise ValueError(f"MED-PEE location-map blob holds {8 * len(out)} bits, fewer than end + 1 = {end + 1}")
+    return np.unpackbits(np.frombuffer(out, dtype=np.uint8), bitorder="little")[: end + 1].astype(bool)
+
+
+def _pee_header(data: bytes, fmt_bytes: int, what: str) -> Tuple[bytes, bytes]:
+    """(header, body) of a version-16 file whose header holds at least fmt_bytes bytes
+    (structure only: the field values are checked where the records are built)."""
+    (hlen,) = struct.unpack(">I", data[4:8])   # pee_scheme() saw the magic and 4 header bytes
+    hdr = data[8:8 + hlen]
+    if len(hdr) < hlen:
+        raise ValueError(f"truncated {what}: the header needs {hlen} bytes, the file holds {len(hdr)}")
+    if hlen < fmt_bytes:
+        raise ValueError(f"truncated {what}: a header of {hlen} bytes, {fmt_bytes} needed")
+    return hdr, data[8 + hlen:]
+
+
+def _pee_shape_check(bpp: int, width: int, height: int):
+    if bpp not in (1, 2):
+        raise ValueError(f"MED-PEE header: {bpp} bytes per pixel (1 or 2)")
+    if width < 1 or height < 1:
+        raise ValueError(f"MED-PEE header: width x height = {width} x {height}")
 
 
 _PEE2_FMT = ">BBBBIIiiii"
@@ -175,6 +211,8 @@ def pee_scheme(data: bytes) -> int:
     """1 or 2: the MED-PEE scheme of a version-16 STGC file (its scheme byte)."""
     if data[:4] != MAGIC:
         raise ValueError("Arquivo inválido ou com assinatura incorreta.")   # codec.py:698
+    if len(data) < 8:
+        raise ValueError("truncated STGC file: no header length")
     (hlen,) = struct.unpack(">I", data[4:8])
     hdr = data[8:8 + hlen]
     if len(hdr) < 4 or hdr[0] != PEE_VERSION:
@@ -188,13 +226,16 @@ def parse_pee2_bytes(data: bytes) -> Tuple[Dict, List[bytes], bytes]:
     """A scheme-2 version-16 STGC file -> (side information with 'passes', 4 lm blobs, stego bytes)."""
     if pee_scheme(data) != 2:
         raise ValueError("not a scheme-2 MED-PEE container")
-    (hlen,) = struct.unpack(">I", data[4:8])
-    hdr = data[8:8 + hlen]
     n0 = struct.calcsize(_PEE2_FMT)
+    hdr, body = _pee_header(data, n0 + 4 * struct.calcsize(_PEE2_PASS), "scheme-2 MED-PEE file")
     (_v, cid, bpp, _s, width, height, T, maxval, L, status) = struct.unpack(_PEE2_FMT, hdr[:n0])
-    passes, blobs, body, pos = [], [], data[8 + hlen:], 0
+    _pee_shape_check(bpp, width, height)
+    passes, blobs, pos = [], [], 0
     for p in range(4):
         Lp, endp, stp, nb = struct.unpack(_PEE2_PASS, hdr[n0 + 16 * p: n0 + 16 * (p + 1)])
+        if pos + nb > len(body):
+            raise ValueError(f"truncated scheme-2 MED-PEE file: pass {p}'s location-map blob of {nb} bytes "
+                             f"does not fit the {len(body) - pos} bytes left")
         passes.append({"L": Lp, "end": endp, "status": stp})
         blobs.append(body[pos:pos + nb])
         pos += nb
@@ -208,11 +249,12 @@ def parse_pee_bytes(data: bytes) -> Tuple[Dict, bytes, bytes]:
     """A version-16 STGC file of scheme 1 -> (side information, lm_blob, stego bytes)."""
     if pee_scheme(data) != 1:
         raise ValueError("a scheme-2 MED-PEE container: use parse_pee2_bytes")
-    (hlen,) = struct.unpack(">I", data[4:8])
-    hdr = data[8:8 + hlen]
+    hdr, body = _pee_header(data, struct.calcsize(_PEE_FMT), "MED-PEE file")
     (_v, cid, bpp, _r, width, height, T, L, end, maxval, status, blob_size) = struct.unpack(
         _PEE_FMT, hdr[:struct.calcsize(_PEE_FMT)])
-    body = data[8 + hlen:]
+    _pee_shape_check(bpp, width, height)
+    if blob_size > len(body):
+        raise ValueError(f"truncated MED-PEE file: a location-map blob of {blob_size} bytes, {len(body)} left")
     md = {"version": PEE_VERSION, "codec": CODEC_NAMES.get(cid, "raw" if cid == 0 else "unknown"),
           "bytes": bpp, "width": width, "height": height, "T": T, "L": L, "end": end, "maxval": maxval,
           "status": status}

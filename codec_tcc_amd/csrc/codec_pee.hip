@@ -33,6 +33,27 @@ __device__ __forceinline__ int med3(int a, int b, int c) {
     return max(min(a, b), min(max(a, b), a + b - c));
 }
 
+// The record fields an extract kernel bounds itself (include/codec_tcc.h, "record contract";
+// the records live in device memory, so the library cannot check them on the host):
+//   end       never past the lattice's last candidate nc - 1 (so no pixel, map word or tile
+//             slot beyond the slice is addressed), tile_end never past end's tile;
+//   L, pw     a bit of rank >= min(L, 64 pw) is dropped, as oracle/pee_cpu.py pee_extract's
+//             bits[:L] (a negative L counts as 0).
+// All three are one uniform min / compare per record (scalar registers).
+__device__ __forceinline__ int pee_clamp_end(int end, int nc) { return min(end, nc - 1); }
+__device__ __forceinline__ int pee_clamp_tile_end(int tile_end, int end) {
+    return min(tile_end, end >= 0 ? end / PEE_TILE : -1);
+}
+__device__ __forceinline__ uint32_t pee_bit_limit(int L, int pw) {
+    // 64 * min(pw, 2^25 - 1) < 2^31 exceeds every int32 L: 32-bit arithmetic throughout
+    return min((uint32_t)max(L, 0), (uint32_t)min(pw, 0x1FFFFFF) * 64u);
+}
+// the bits of payload word w whose rank is below lim
+__device__ __forceinline__ unsigned long long pee_word_mask(uint32_t lim, int w) {
+    const long long r = (long long)lim - 64ll * w;
+    return r >= 64 ? ~0ull : (r <= 0 ? 0ull : (1ull << r) - 1ull);
+}
+
 // branch-free classification: -T <= e < T as one unsigned compare; the expansion target
 // y = p + 2e (+ bit) must stay in [0, maxval], i.e. (unsigned)y < maxval
 __device__ __forceinline__ PeeCand pee_classify(int x, int a, int b, int c, int T, int maxval) {
@@ -550,7 +571,8 @@ __global__ __launch_bounds__(256) void k_pee_dcount_w(const T* __restrict__ steg
     typedef typename Vec8<T>::type V;
     const int b = blockIdx.y;
     const codec_pee_meta* M = meta_all + b;
-    const int tile_end = M->tile_end, end = M->end, Tthr = M->T;
+    const int end = pee_clamp_end(M->end, (H / 2) * (W / 2)), tile_end = pee_clamp_tile_end(M->tile_end, end);
+    const int Tthr = M->T;
     const T* src = stego + (size_t)b * H * W;
     const u64* lm = lm_all + (size_t)b * lmw;
     const int lane = threadIdx.x & 63;
@@ -716,8 +738,9 @@ __global__ __launch_bounds__(256) void k_pee_dcount(const T* __restrict__ stego,
     __shared__ uint32_t sh[8];
     const int b = blockIdx.y;
     const codec_pee_meta* M = meta_all + b;
-    const int tile_end = M->tile_end, end = M->end, Tthr = M->T;
     const int wc = W / 2;
+    const int end = pee_clamp_end(M->end, (H / 2) * wc), tile_end = pee_clamp_tile_end(M->tile_end, end);
+    const int Tthr = M->T;
     const T* src = stego + (size_t)b * H * W;
     const u64* lm = lm_all + (size_t)b * lmw;
     for (int t = blockIdx.x; t <= tile_end; t += gridDim.x) {
@@ -743,7 +766,9 @@ __global__ __launch_bounds__(256) void k_pee_offsets(const codec_pee_meta* __res
                                                      uint32_t* __restrict__ tile_off_all, int ntiles_max) {
     __shared__ uint32_t sh[8];
     const int b = blockIdx.x;
-    const int n = meta_all[b].tile_end + 1;
+    // never past the slice's tile slots (the count kernels bound tile_end by `end`'s tile; a
+    // larger record value only scans slots no recover kernel reads)
+    const int n = min(meta_all[b].tile_end + 1, ntiles_max);
     const uint32_t* cnt = tile_cnt_all + (size_t)b * ntiles_max;
     uint32_t* off = tile_off_all + (size_t)b * ntiles_max;
     uint32_t running = 0;
@@ -766,8 +791,10 @@ __global__ __launch_bounds__(256) void k_pee_recover(const T* __restrict__ stego
     __shared__ uint32_t sh[8];
     const int b = blockIdx.y;
     const codec_pee_meta* M = meta_all + b;
-    const int tile_end = M->tile_end, end = M->end, Tthr = M->T;
     const int wc = W / 2;
+    const int end = pee_clamp_end(M->end, (H / 2) * wc), tile_end = pee_clamp_tile_end(M->tile_end, end);
+    const int Tthr = M->T;
+    const uint32_t plim = pee_bit_limit(M->L, pw);   // bits of rank >= min(L, 64 pw) are dropped
     const size_t npx = (size_t)H * W;
     const T* src = stego + b * npx;
     T* dst = cover + b * npx;
@@ -805,7 +832,7 @@ __global__ __launch_bounds__(256) void k_pee_recover(const T* __restrict__ stego
             const int e2 = q.x[u] - ps[u];
             int x;
             if (inner[u]) {
-                if (e2 & 1) {      // bits of one thread are consecutive: one atomic per word
+                if ((e2 & 1) && cur < plim) {   // bits of one thread are consecutive: one atomic per word
                     if (wi != (int)(cur >> 6)) {
                         if (wi >= 0 && word) atomicOr(&payload[wi], word);
                         wi = (int)(cur >> 6);
@@ -864,7 +891,9 @@ __global__ __launch_bounds__(256) void k_pee_restore_gs(const T* __restrict__ st
             const uint32_t b = gt / tiles_per_slice, t = gt - b * tiles_per_slice;
             const codec_pee_meta* M = meta_all + b;
             if ((int)t <= M->tile_end) {                                 // uniform per slot
+                // t < tiles_per_slice bounds every candidate index by nc whatever `end` says
                 const int end = M->end, Tthr = M->T;
+                const uint32_t plim = pee_bit_limit(M->L, pw);   // as k_pee_recover
                 const u64* lm = lm_all + (size_t)b * lmw;
                 const int k0 = (int)t * PEE_TILE + 4 * threadIdx.x;
                 int ps[4], xs[4];
@@ -895,7 +924,7 @@ __global__ __launch_bounds__(256) void k_pee_restore_gs(const T* __restrict__ st
                     const int e2 = xs[q] - ps[q];
                     int x;
                     if (inner[q]) {
-                        if (e2 & 1) {
+                        if ((e2 & 1) && cur < plim) {
                             if (wi != (int)(cur >> 6)) {
                                 if (wi >= 0 && word) atomicOr(&payload[wi], word);
                                 wi = (int)(cur >> 6);
@@ -1761,7 +1790,8 @@ __global__ PEE_X1_LB void k_pee_extract1(const T* stego, T* cover, int H, int W,
         if (j > cmax) return;                           // in place: a lane's chunks only grow
         if (!valid) continue;
         const codec_pee_meta* M = meta_all + b;
-        const int end = M->end, Tthr = M->T;
+        const int end = pee_clamp_end(M->end, (int)(4u * items)), Tthr = M->T;   // nc = 4 items (8 | W)
+        const uint32_t plim = pee_bit_limit(M->L, pw);   // bits of rank >= min(L, 64 pw) are dropped
 #ifdef PEE_X_COPYONLY   // diagnostic build (tools): every chunk a plain copy
         const int cend = -1;
         (void)end;
@@ -1910,7 +1940,7 @@ __global__ PEE_X1_LB void k_pee_extract1(const T* stego, T* cover, int H, int W,
             const uint32_t f = excl + agg;
             if (!sc) {
                 if (tid < nw) {
-                    const u64 wv = pbuf[tid];
+                    const u64 wv = pbuf[tid] & pee_word_mask(plim, w0 + tid);   // 0 past min(L, 64 pw)
                     if (wv) {
                         const bool shared = (tid == 0 && (excl & 63u)) || (tid == nw - 1 && (f & 63u));
                         if (shared) atomicOr(&payload[w0 + tid], wv);
@@ -1938,7 +1968,7 @@ __global__ PEE_X1_LB void k_pee_extract1(const T* stego, T* cover, int H, int W,
                     if (owned && w < pw) {
                         u64 wv = pbuf[tid];
                         if (ahead && tid == nw - 1) wv |= s_ra << (f & 63u);
-                        payload[w] = wv;
+                        payload[w] = wv & pee_word_mask(plim, w);
                     }
                 }
                 if (c == cend)
@@ -2915,7 +2945,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_pee_extract_ss(const T* __restri
     const uint32_t items = (uint32_t)(H / 2) * (uint32_t)CR;
     const int nchunks = (int)((items + SS_THREADS - 1) / SS_THREADS);
     const codec_pee_meta* M = meta_all + b;
-    const int end = M->end, Tthr = M->T;
+    const int end = pee_clamp_end(M->end, (int)(4u * items)), Tthr = M->T;   // nc = 4 items (8 | W)
     const int cend = end >= 0 ? (end >> 2) / SS_THREADS : -1;
     const int nproc = INPLACE ? cend + 1 : nchunks;
     const int klast = max(nproc, 1) - 1;
@@ -3917,7 +3947,7 @@ struct LatQuad {
 
 __device__ __forceinline__ int pee_pass_base(const codec_pee_meta* metas, int pass, int B, int b) {
     int base = 0;
-    for (int q = 0; q < pass; ++q) base += metas[(size_t)q * B + b].L;
+    for (int q = 0; q < pass; ++q) base += max(0, metas[(size_t)q * B + b].L);   // as k_pee_lat_ss
     return base;
 }
 
@@ -4097,8 +4127,10 @@ __global__ __launch_bounds__(256) void k_pee_lat_dcount(const T* __restrict__ im
     __shared__ uint32_t sh[8];
     const int b = blockIdx.y;
     const codec_pee_meta* M = metas + (size_t)pass * B + b;
-    const int tile_end = M->tile_end, end = M->end, Tthr = M->T;
     const PeeLat g = pee_lattice(lat, H, W);
+    // `end` bounded by this lattice's own candidates (the map is sized for lattice 0's)
+    const int end = pee_clamp_end(M->end, g.hc * g.wc), tile_end = pee_clamp_tile_end(M->tile_end, end);
+    const int Tthr = M->T;
     const T* src = img + (size_t)b * H * W;
     const u64* lm = lm_all + (size_t)b * lmw;
     for (int t = blockIdx.x; t <= tile_end; t += gridDim.x) {
@@ -4132,11 +4164,12 @@ __global__ __launch_bounds__(256) void k_pee_lat_recover(T* __restrict__ img, in
     __shared__ uint32_t sh[8];
     const int b = blockIdx.y;
     const codec_pee_meta* M = metas + (size_t)pass * B + b;
-    const int tile_end = M->tile_end, end = M->end, Tthr = M->T;
+    const PeeLat g = pee_lattice(lat, H, W);
+    const int end = pee_clamp_end(M->end, g.hc * g.wc), tile_end = pee_clamp_tile_end(M->tile_end, end);   // as k_pee_lat_dcount
+    const int Tthr = M->T;
     if (tile_end < 0) return;
     const uint32_t pbase = (uint32_t)pee_pass_base(metas, pass, B, b);
     const uint32_t plim = pbase + (uint32_t)max(0, M->L);
-    const PeeLat g = pee_lattice(lat, H, W);
     T* dst = img + (size_t)b * H * W;
     const u64* lm = lm_all + (size_t)b * lmw;
     u64* payload = payload_all + (size_t)b * pw;
@@ -4282,7 +4315,7 @@ __global__ __launch_bounds__(LSS_THREADS) void k_pee_lat_ss(const T* __restrict_
         uint32_t pbase, lim;   // embed: lim = bits left; extract: lim = pbase + L
         if (EXTRACT) {
             if (M->tile_end < 0) continue;   // uniform
-            end = M->end;
+            end = pee_clamp_end(M->end, nc);   // this lattice's candidates only (record contract)
             Tt = M->T;
             pbase = 0;
             for (int q = 0; q < p; ++q) pbase += (uint32_t)max(0, metas[(size_t)q * B + b].L);
@@ -4768,7 +4801,8 @@ int codec_pee_multi_embed(const codec_pee_params* P, const void* cover, void* st
                                     static_cast<const TT*>(cover), static_cast<TT*>(stego), P->H, P->W, P->T, P->maxval, cm, \
                                     p0s1 ? 1 : 0, const_cast<u64*>(reinterpret_cast<const u64*>(payload)), P->payload_words, \
                                     lengths, metas, P->B, reinterpret_cast<u64*>(lm), P->lm_words, sink)
-    const bool pf = knob("CODEC_PEE_LAT_SS_PF", 1) != 0;
+    // the no-prefetch A/B instantiation stages the payload in LDS: only where it fits (pl)
+    const bool pf = knob("CODEC_PEE_LAT_SS_PF", 1) != 0 || !pl;
     if (P->bytes == 2) {
         if (!pf) hipLaunchKernelGGL((k_pee_lat_ss<uint16_t, false, true, false>), dim3((unsigned)P->B), dim3(LSS_THREADS), 0,
                                     st, static_cast<const uint16_t*>(cover), static_cast<uint16_t*>(stego), P->H, P->W, P->T,
@@ -4811,7 +4845,7 @@ int codec_pee_multi_extract(const codec_pee_params* P, const void* stego, const 
                                     0, reinterpret_cast<u64*>(payload_out), P->payload_words, nullptr, \
                                     const_cast<codec_pee_meta*>(metas), P->B, const_cast<u64*>(reinterpret_cast<const u64*>(lm)), \
                                     P->lm_words, sink)
-    const bool pf = knob("CODEC_PEE_LAT_SS_PF", 1) != 0;
+    const bool pf = knob("CODEC_PEE_LAT_SS_PF", 1) != 0 || !pl;   // as codec_pee_multi_embed
     if (P->bytes == 2) {
         if (!pf) PLSX(uint16_t, true, false);
         else if (pl) PLSX(uint16_t, true, true);

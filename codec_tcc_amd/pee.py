@@ -33,6 +33,123 @@ def lattice_geometry(lattice: int, H: int, W: int):
     return y0, x0, max(0, (H - y0 + 1) // 2), max(0, (W - x0 + 1) // 2)
 
 
+def make_record(H: int, W: int, *, T: int, maxval: int, L: int, end: int, status: int, lattice: int = 0) -> _lib.PeeMeta:
+    """The codec_pee_meta an embed of lattice `lattice` writes for this side information (what a
+    file header or a side dict of oracle/pee_cpu.py carries); the geometry fields follow from H x W.  The
+    values are stored as given -- check_records() judges them."""
+    _y0, _x0, hc, wc = lattice_geometry(lattice, H, W)
+    nc = hc * wc
+    m = _lib.PeeMeta()
+    m.T, m.maxval, m.L, m.end = int(T), int(maxval), int(L), int(end)
+    m.nc, m.ntiles = nc, (nc + 1023) // 1024
+    m.tile_end = int(end) // 1024 if int(end) >= 0 else -1
+    m.status, m.capacity, m.h, m.w = int(status), int(L), int(H), int(W)
+    m.reserved[0] = lattice
+    return m
+
+
+def check_records(records, H: int, W: int, *, scheme: int, payload_words: int, lm_words: int, bytes: int,
+                  lengths: Optional[Sequence[int]] = None) -> None:
+    """Host-side check of MED-PEE side records before a launch that trusts them (a file header,
+    hand-made tensors): the extract kernels bound `end`, `L` and the payload row themselves
+    (include/codec_tcc.h, record contract) but decode an inconsistent record to garbage, and the
+    library cannot look at device-resident records -- so this layer does.  Pure host code: no
+    GPU, no library load.
+
+    records: scheme 1 -- one per slice; scheme 2 -- [4][B] pass-major (or the flat 4 * B list of
+    PeeEncoded.records()).  lengths (scheme 2): the embedded bits per slice the container
+    states, checked against the passes' sum.  Raises ValueError naming slice, pass and field.
+
+    The invariants are those of the records oracle/pee_cpu.py and tests/pee_scalar.py write
+    (nc_p = the lattice's candidate count):
+      1 <= T <= 64; 1 <= maxval <= the dtype's maximum (the library refuses maxval 0);
+      h, w, nc, ntiles = the geometry's; scheme 2: reserved[0] = the pass;
+      status 0: L = 0 and end = -1, or 1 <= L <= end + 1 <= nc_p;
+      status 1 (the pass filled up): end = nc_p - 1 and 0 <= L <= nc_p (L = 0 when the
+        capacity is 0 and bits were left over);
+      status CODEC_PEE_ELOOKBACK (never in files; decode refuses it): only the bounds;
+      tile_end = end // 1024 (-1 for end = -1);
+      scheme 2: a pass embeds bits only when every earlier pass filled up, and the passes' L
+        sum to the stated length;
+      64 * payload_words >= the slice's bits; 64 * lm_words > end."""
+    if scheme not in (1, 2):
+        raise ValueError("scheme must be 1 or 2")
+    if bytes not in (1, 2):
+        raise ValueError(f"bytes = {bytes}: 1 (uint8) or 2 (uint16)")
+    H, W, payload_words, lm_words = int(H), int(W), int(payload_words), int(lm_words)
+    if H < 1 or W < 1:
+        raise ValueError(f"shape {H} x {W}")
+    if payload_words < 1 or lm_words < 1:
+        raise ValueError(f"payload_words = {payload_words}, lm_words = {lm_words}: both >= 1")
+    npass = 4 if scheme == 2 else 1
+    recs = list(records)
+    if recs and not isinstance(recs[0], (list, tuple)):
+        if len(recs) % npass:
+            raise ValueError(f"{len(recs)} records are no multiple of the scheme's {npass} passes")
+        n = len(recs) // npass
+        recs = [recs[p * n:(p + 1) * n] for p in range(npass)]
+    if len(recs) != npass or len({len(pr) for pr in recs}) != 1:
+        raise ValueError(f"scheme {scheme} takes {npass} pass(es) of one record per slice")
+    B = len(recs[0])
+    if lengths is not None and len(lengths) != B:
+        raise ValueError(f"{len(lengths)} lengths for {B} slices")
+    vmax = 65535 if bytes == 2 else 255
+
+    def bad(b, p, field, value, why):
+        raise ValueError(f"MED-PEE record of slice {b}, pass {p}: {field} = {value} ({why})")
+
+    for b in range(B):
+        total, filled = 0, True   # filled: every earlier pass has status 1
+        for p in range(npass):
+            r = recs[p][b]
+            _y0, _x0, hc, wc = lattice_geometry(p, H, W)
+            nc = hc * wc
+            T, maxval, L, end, status = int(r.T), int(r.maxval), int(r.L), int(r.end), int(r.status)
+            if not 1 <= T <= 64:
+                bad(b, p, "T", T, "1..64")
+            if not 1 <= maxval <= vmax:
+                bad(b, p, "maxval", maxval, f"1..{vmax}")
+            for name, got, want in (("h", r.h, H), ("w", r.w, W), ("nc", r.nc, nc), ("ntiles", r.ntiles, (nc + 1023) // 1024)):
+                if int(got) != want:
+                    bad(b, p, name, int(got), f"the geometry's is {want}")
+            if scheme == 2 and int(r.reserved[0]) != p:
+                bad(b, p, "reserved[0]", int(r.reserved[0]), "the pass's lattice")
+            if status == 0:
+                if L == 0:
+                    if end != -1:
+                        bad(b, p, "end", end, "-1 when no bit is embedded")
+                elif L < 0:
+                    bad(b, p, "L", L, ">= 0")
+                elif not 0 <= end < nc:
+                    bad(b, p, "end", end, f"0..{nc - 1}, the lattice's candidates")
+                elif L > end + 1:
+                    bad(b, p, "L", L, f"at most end + 1 = {end + 1}")
+            elif status == 1:
+                if end != nc - 1:
+                    bad(b, p, "end", end, f"{nc - 1}: a pass that filled up processes every candidate")
+                if not 0 <= L <= nc:
+                    bad(b, p, "L", L, f"0..{nc}")
+            elif status == _lib.CODEC_PEE_ELOOKBACK:
+                if not -1 <= end < nc:
+                    bad(b, p, "end", end, f"-1..{nc - 1}")
+                if L < 0:
+                    bad(b, p, "L", L, ">= 0")
+            else:
+                bad(b, p, "status", status, f"0, 1 or {_lib.CODEC_PEE_ELOOKBACK}")
+            if int(r.tile_end) != (end // 1024 if end >= 0 else -1):
+                bad(b, p, "tile_end", int(r.tile_end), f"end // 1024 = {end // 1024 if end >= 0 else -1}")
+            if end >= 64 * lm_words:
+                bad(b, p, "end", end, f"past the location map's {64 * lm_words} bits")
+            if L > 0 and not filled:
+                bad(b, p, "L", L, "bits embedded after a pass that did not fill up")
+            filled = filled and status == 1
+            total += L
+        if total > 64 * payload_words:
+            bad(b, npass - 1, "L", total, f"the slice's bits exceed the payload row's {64 * payload_words}")
+        if scheme == 2 and lengths is not None and int(lengths[b]) != total:
+            bad(b, npass - 1, "L", total, f"the passes' sum; the stated length is {int(lengths[b])}")
+
+
 @dataclass
 class PeeEncoded:
     stego: object      # torch [B,H,W]
@@ -214,10 +331,7 @@ class PeeCodec:
             lm = torch.empty((4, self.B, self.lm_words), dtype=torch.int64, device=self.device)
         if meta is None:
             meta = torch.empty((4, self.B, _lib.PEE_META_BYTES), dtype=torch.uint8, device=self.device)
-        if tuple(lm.shape) != (4, self.B, self.lm_words) or tuple(meta.shape) != (4, self.B, _lib.PEE_META_BYTES):
-            raise ValueError("scheme 2 takes lm [4, B, lm_words] and meta [4, B, PEE_META_BYTES]")
-        if not (lm.is_contiguous() and meta.is_contiguous()):
-            raise ValueError("scheme 2's lm and meta must be contiguous")
+        _check_multi_args(self.B, self.lm_words, meta, lm)
         P = self._params(words.shape[1])
         lib = _lib.load()
         if self.auto:
@@ -255,8 +369,7 @@ class PeeCodec:
     def _extract_multi(self, stego, meta, lm, payload_words, cover, payload):
         """Scheme 2: passes 3..0 in one library call (codec_pee_multi_extract; the first copies
         stego -> cover, the others run in place; payload written whole)."""
-        if not (lm.is_contiguous() and meta.is_contiguous()):
-            raise ValueError("scheme 2's lm and meta must be contiguous")
+        _check_multi_args(self.B, self.lm_words, meta, lm, payload=payload, payload_words=payload_words)
         P = self._params(payload_words)
         lib = _lib.load()
         self._guarded(lambda: _lib.check(lib.codec_pee_multi_extract(
@@ -284,21 +397,30 @@ class PeeCodec:
     def _t_text(self) -> str:
         return f"T={'auto, tmax=%d' % self.tmax if self.auto else self.T}"
 
+    def _check(self, enc: PeeEncoded, recs, lengths=None):
+        """check_records() on records already read back (decode: no extra sync)."""
+        check_records(recs, self.H, self.W, scheme=self.scheme, payload_words=enc.payload_words,
+                      lm_words=self.lm_words, bytes=self.bytes, lengths=lengths)
+
     def decode(self, enc: PeeEncoded):
-        """(list of 0/1 bit vectors, restored cover tensor); raises if a slice overflowed."""
+        """(list of 0/1 bit vectors, restored cover tensor); raises if a slice overflowed, and
+        ValueError for records that are not an embed's (check_records)."""
         if enc.scheme != self.scheme:
             raise ValueError(f"a scheme-{enc.scheme} embedding given to a scheme-{self.scheme} codec")
         if self.scheme == 2:
-            got = enc.embedded()
+            prs = enc.pass_records()   # one read-back serves the capacity test and the record check
+            got = [sum(int(pr[b].L) for pr in prs) for b in range(len(enc.lengths))]
             short = [i for i, (g, n) in enumerate(zip(got, enc.lengths)) if g < n]
             if short:
                 raise ValueError(f"payload exceeds PEE capacity in slices {short} (scheme 2, {self._t_text()})")
+            self._check(enc, prs, enc.lengths)
             words, cover = self.extract(enc.stego, enc.meta, enc.lm, payload_words=enc.payload_words)
             host = words.cpu().numpy()   # the extract passes have no look-back (tile or slice-serial)
             return [framing.unpack_bits(host[i], enc.lengths[i]) for i in range(self.B)], cover
         recs = enc.records()
         _raise_lookback(recs)
         _raise_status(recs, self._t_text())
+        self._check(enc, recs)
         words, cover = self.extract(enc.stego, enc.meta, enc.lm, payload_words=enc.payload_words)
         host = words.cpu().numpy()
         if self.lookback_failed(enc.payload_words):
@@ -306,6 +428,24 @@ class PeeCodec:
             raise RuntimeError("codec_pee_extract: in-place cursor look-back timed out; the recovered "
                                "payload is invalid (the restored cover is exact)")
         return [framing.unpack_bits(host[i], enc.lengths[i]) for i in range(self.B)], cover
+
+
+def _check_multi_args(B: int, lm_words: int, meta, lm, *, payload=None, payload_words: Optional[int] = None):
+    """Scheme 2's argument shapes (the library reads 4 * B records and maps, and with `payload`
+    writes B rows of payload_words words): ValueError before any launch.  Shapes only -- runs
+    on tensors of any device."""
+    if tuple(lm.shape) != (4, B, lm_words) or tuple(meta.shape) != (4, B, _lib.PEE_META_BYTES):
+        raise ValueError("scheme 2 takes lm [4, B, lm_words] and meta [4, B, PEE_META_BYTES]")
+    if lm.element_size() != 8 or meta.element_size() != 1:
+        raise ValueError("scheme 2 takes lm as 64-bit words and meta as bytes")
+    if not (lm.is_contiguous() and meta.is_contiguous()):
+        raise ValueError("scheme 2's lm and meta must be contiguous")
+    if payload is not None:
+        pw = int(payload_words)
+        if pw < 1 or payload.dim() != 2 or payload.shape[0] != B or payload.shape[1] < pw or payload.element_size() != 8:
+            raise ValueError(f"the payload buffer must hold at least [B, payload_words] = [{B}, {pw}] 64-bit words")
+        if payload.stride(1) != 1 or (B > 1 and payload.stride(0) != pw):
+            raise ValueError("the payload buffer's rows must be payload_words words apart (the library's row pitch)")
 
 
 def _same_storage(a, b) -> bool:

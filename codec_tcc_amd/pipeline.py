@@ -19,11 +19,12 @@ import os
 import shutil
 import subprocess
 import tempfile
-from typing import Dict, Optional, Tuple
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from . import _lib, api, container, dicom, framing
+from . import api, container, dicom, framing
 from .codec import Codec, _require_gpu, _torch, meta_records
 
 
@@ -185,66 +186,68 @@ def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxva
             "status": r.status, "lm_count": r.lm_count, "stego": stego}
 
 
-def decode_bin_pee(filepath: str) -> Tuple[np.ndarray, np.ndarray]:
-    """(payload bits as a 0/1 uint8 vector, restored cover) from a version-16 STGC file."""
-    from .pee import PeeCodec
-    _require_gpu()
-    torch = _torch()
-    with open(filepath, "rb") as f:
-        raw = f.read()
-    if container.pee_scheme(raw) == 2:
-        return _decode_pee2(raw)
-    md, blob, data = container.parse_pee_bytes(raw)
+@dataclass
+class PeeFile:
+    """The host half of a MED-PEE file decode (read_pee_bytes): everything the launch needs."""
+    md: Dict                 # the header's side information
+    scheme: int              # 1 or 2
+    records: List            # checked codec_pee_meta records: [pass][slice] (one slice)
+    lm: np.ndarray           # bool [passes, 1, 64 * lm_words]: the location-map bits
+    stego: np.ndarray        # [H, W] uint8 / uint16
+    payload_words: int
+    lm_words: int
+
+
+def read_pee_bytes(raw: bytes) -> PeeFile:
+    """File bytes -> checked records, location-map bits, the stego array and the payload word
+    count, on the host alone (no GPU): decode_bin_pee launches on what this returns.  A file
+    that is truncated, malformed or whose header fields contradict each other raises
+    ValueError here (container.parse_pee*_bytes for the structure, pee.check_records for the
+    records), before anything reaches a kernel."""
+    from .pee import check_records, make_record
+    scheme = container.pee_scheme(raw)
+    if scheme == 2:
+        md, blobs, data = container.parse_pee2_bytes(raw)
+        passes = md["passes"]
+    else:
+        md, blob, data = container.parse_pee_bytes(raw)
+        blobs, passes = [blob], [{"L": md["L"], "end": md["end"], "status": md["status"]}]
     h, w = md["height"], md["width"]
+    if h * w > 0x7FFFFFFF:
+        raise ValueError(f"MED-PEE header: {w} x {h} pixels exceed the codec's 2^31 - 1")
     stego = _decompress(data, md["codec"], h, w)
-    if stego.dtype.itemsize != md["bytes"]:
-        raise ValueError("stego pixel size does not match the MED-PEE header")
-    pc = PeeCodec(1, h, w, dtype=str(stego.dtype), T=max(1, md["T"]), maxval=md["maxval"])
-    lm = np.zeros(pc.lm_words * 64, dtype=bool)
-    if md["end"] >= 0:
-        lm[: md["end"] + 1] = container.lm_from_blob(blob, md["end"])
-    lm_t = torch.from_numpy(np.packbits(lm, bitorder="little").view(np.int64).copy()).view(1, -1).cuda()
-    m = _lib.PeeMeta()
-    nc = (h // 2) * (w // 2)
-    m.T, m.maxval, m.L, m.end = md["T"], md["maxval"], md["L"], md["end"]
-    m.nc, m.ntiles = nc, (nc + 1023) // 1024
-    m.tile_end = md["end"] // 1024 if md["end"] >= 0 else -1
-    m.status, m.capacity, m.h, m.w = md["status"], md["L"], h, w
-    meta = torch.frombuffer(bytearray(bytes(m)), dtype=torch.uint8).view(1, -1).cuda()
+    if stego.shape != (h, w) or stego.dtype.itemsize != md["bytes"]:
+        raise ValueError("stego pixels do not match the MED-PEE header's shape / pixel size")
+    lm_words = max(1, ((h // 2) * (w // 2) + 63) // 64)
     pw = max(1, (md["L"] + 63) // 64)
-    words, cover = pc.extract(torch.from_numpy(np.ascontiguousarray(stego)[None]).cuda(), meta, lm_t,
-                              payload_words=pw)
-    return framing.unpack_bits(words.cpu().numpy()[0], md["L"]), cover.cpu().numpy()[0]
-
-
-def _decode_pee2(raw: bytes) -> Tuple[np.ndarray, np.ndarray]:
-    """Scheme-2 file: the passes' records rebuilt from the header, then the reverse passes."""
-    from .pee import PeeCodec, PeeEncoded, lattice_geometry
-    torch = _torch()
-    md, blobs, data = container.parse_pee2_bytes(raw)
-    h, w = md["height"], md["width"]
-    stego = _decompress(data, md["codec"], h, w)
-    if stego.dtype.itemsize != md["bytes"]:
-        raise ValueError("stego pixel size does not match the MED-PEE header")
-    pc = PeeCodec(1, h, w, dtype=str(stego.dtype), T=max(1, md["T"]), maxval=md["maxval"], scheme=2)
-    lm = np.zeros((4, 1, pc.lm_words * 64), dtype=bool)
-    metas = bytearray()
-    for p, ps in enumerate(md["passes"]):
+    records = [[make_record(h, w, T=md["T"], maxval=md["maxval"], L=ps["L"], end=ps["end"], status=ps["status"],
+                            lattice=p)] for p, ps in enumerate(passes)]
+    check_records(records, h, w, scheme=scheme, payload_words=pw, lm_words=lm_words, bytes=md["bytes"],
+                  lengths=[md["L"]] if scheme == 2 else None)
+    if md["status"] not in (0, 1) or any(ps["status"] not in (0, 1) for ps in passes):
+        raise ValueError("MED-PEE header: a status other than 0 / 1 (files hold finished embeddings)")
+    lm = np.zeros((len(passes), 1, lm_words * 64), dtype=bool)
+    for p, ps in enumerate(passes):   # end < 64 * lm_words: checked above
         if ps["end"] >= 0:
             lm[p, 0, : ps["end"] + 1] = container.lm_from_blob(blobs[p], ps["end"])
-        _y0, _x0, hc, wc = lattice_geometry(p, h, w)
-        m = _lib.PeeMeta()
-        nc = hc * wc
-        m.T, m.maxval, m.L, m.end = md["T"], md["maxval"], ps["L"], ps["end"]
-        m.nc, m.ntiles = nc, (nc + 1023) // 1024
-        m.tile_end = ps["end"] // 1024 if ps["end"] >= 0 else -1
-        m.status, m.capacity, m.h, m.w = ps["status"], ps["L"], h, w
-        m.reserved[0] = p
-        metas += bytes(m)
-    meta_t = torch.frombuffer(metas, dtype=torch.uint8).view(4, 1, -1).cuda()
-    lm_t = torch.from_numpy(np.packbits(lm, axis=-1, bitorder="little").view(np.int64).copy()).cuda()
-    pw = max(1, (md["L"] + 63) // 64)
-    enc = PeeEncoded(stego=torch.from_numpy(np.ascontiguousarray(stego)[None]).cuda(), lm=lm_t, meta=meta_t,
-                     lengths=[md["L"]], payload_words=pw, config=pc.config, scheme=2)
-    words, cover = pc.extract(enc.stego, enc.meta, enc.lm, payload_words=pw)
+    return PeeFile(md=md, scheme=scheme, records=records, lm=lm, stego=stego, payload_words=pw, lm_words=lm_words)
+
+
+def decode_bin_pee(filepath: str) -> Tuple[np.ndarray, np.ndarray]:
+    """(payload bits as a 0/1 uint8 vector, restored cover) from a version-16 STGC file
+    (either scheme): read_pee_bytes on the host, then one extract launch."""
+    from .pee import PeeCodec
+    with open(filepath, "rb") as f:
+        pf = read_pee_bytes(f.read())
+    _require_gpu()
+    torch = _torch()
+    md, h, w = pf.md, pf.stego.shape[0], pf.stego.shape[1]
+    pc = PeeCodec(1, h, w, dtype=str(pf.stego.dtype), T=md["T"], maxval=md["maxval"], scheme=pf.scheme)
+    metas = b"".join(bytes(r) for pr in pf.records for r in pr)
+    meta_t = torch.frombuffer(bytearray(metas), dtype=torch.uint8).view(len(pf.records), 1, -1).cuda()
+    lm_t = torch.from_numpy(np.packbits(pf.lm, axis=-1, bitorder="little").view(np.int64).copy()).cuda()
+    if pf.scheme == 1:
+        meta_t, lm_t = meta_t[0], lm_t[0]
+    words, cover = pc.extract(torch.from_numpy(np.ascontiguousarray(pf.stego)[None]).cuda(), meta_t, lm_t,
+                              payload_words=pf.payload_words)
     return framing.unpack_bits(words.cpu().numpy()[0], md["L"]), cover.cpu().numpy()[0]

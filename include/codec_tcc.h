@@ -333,7 +333,26 @@ int codec_pee_embed_auto(const codec_pee_params* P, const void* cover, void* ste
                          const int32_t* lengths, int32_t tmax, int32_t* t_out, codec_pee_meta* meta, uint64_t* lm,
                          void* workspace, size_t workspace_bytes, void* stream);
 /* stego -> exact payload bits + restored cover.  cover_out == stego is allowed (in
- * place: only the items up to `end` are read and written). */
+ * place: only the items up to `end` are read and written).
+ *
+ * Record contract (this call, codec_pee_multi_extract_pass and codec_pee_multi_extract).  The
+ * records and maps are device memory: the library cannot look at them without a copy and a
+ * sync, so it does not validate them -- a caller that builds records itself (a file header, a
+ * record exchange) checks them on the host first (codec_tcc_amd/pee.py check_records: the
+ * invariants of the records oracle/pee_cpu.py writes).
+ *   trusted:  T, status (unused), the map's bits, and that L, end and tile_end describe the
+ *             same embedding -- an inconsistent record decodes to a wrong payload / cover, but
+ *             see the bounds below.
+ *   bounded by the kernels, whatever the record says (one uniform min / compare each):
+ *     end       taken as min(end, nc - 1) with nc the candidates of the record's own lattice
+ *               ((H/2)(W/2) for scheme 1; scheme 2's lattices 1..3 have fewer), tile_end as
+ *               min(tile_end, end / 1024): no pixel, map word or workspace slot outside the
+ *               slice's own is addressed;
+ *     L         a bit of rank >= L (a negative L counts as 0) is not written, as the oracle's
+ *               pee_extract returns bits[:L] (the slice-serial scheme-1 kernel bounds by whole
+ *               words only: its last word may carry bits of rank L .. 64 payload_words - 1);
+ *     payload   word index >= payload_words is never written.
+ *   unused:   nc, ntiles, capacity, lm_count, h, w, flags, reserved (the shape is P's). */
 int codec_pee_extract(const codec_pee_params* P, const void* stego, const codec_pee_meta* meta,
                       const uint64_t* lm, void* cover_out, uint64_t* payload_out, void* workspace,
                       size_t workspace_bytes, void* stream);
