@@ -1,4 +1,5 @@
-"""ctypes binding of libcodec_hip.so (include/codec_tcc.h, include/codec_tcc_ext.h).
+"""ctypes binding of libcodec_hip.so (include/codec_tcc.h, include/codec_tcc_ext.h,
+include/codec_tcc_crc.h).
 
 The library is built in-tree (codec_tcc_amd/libcodec_hip.so, see build.py).  There is no
 CPU fallback: if the library cannot be loaded, every entry point raises RuntimeError.
@@ -135,7 +136,8 @@ KERNEL_TAGS = {1: "k_scan_fast", 2: "k_scan_generic", 3: "k_block_exact", 4: "k_
                23: "k_pee_capacity", 24: "k_pee_embed_ss", 25: "k_pee_extract_ss",
                26: "k_pee_embed_ss_auto", 27: "k_pee_embed_res", 28: "k_scan_decide",
                29: "k_pee_lat_count", 30: "k_pee_lat_embed", 31: "k_pee_lat_dcount", 32: "k_pee_lat_recover",
-               33: "k_pee_lat_ss_embed", 34: "k_pee_lat_ss_extract", 35: "k_pee_lat_auto"}
+               33: "k_pee_lat_ss_embed", 34: "k_pee_lat_ss_extract", 35: "k_pee_lat_auto",
+               36: "k_crc32", 37: "k_crc32_combine"}
 EXPORTS = tuple(_SIGS)
 # include/codec_tcc_ext.h: entries added after codec_tcc.h's list (EXPORTS) was fixed
 _SIGS_EXT = {
@@ -143,6 +145,14 @@ _SIGS_EXT = {
                                              _VP, _VP, C.c_size_t, _VP]),
 }
 EXPORTS_EXT = tuple(_SIGS_EXT)
+# include/codec_tcc_crc.h: the CRC-32 entries (checksum.py)
+_SIGS_CRC = {
+    "codec_crc32_chunk_bytes": (C.c_size_t, []),
+    "codec_crc32_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "codec_crc32_slices": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "codec_crc32_combine": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32)]),
+}
+EXPORTS_CRC = tuple(_SIGS_CRC)
 
 _lib = None
 _load_error = None
@@ -171,7 +181,7 @@ def load(path: str = LIB_PATH):
     except OSError as e:  # pragma: no cover - environment specific
         _load_error = e
         raise RuntimeError(f"cannot load {path}: {e}") from e
-    for name, (res, args) in {**_SIGS, **_SIGS_EXT}.items():
+    for name, (res, args) in {**_SIGS, **_SIGS_EXT, **_SIGS_CRC}.items():
         fn = getattr(lib, name, None)
         if fn is None:
             if name == "codec_build_digest" and not in_tree:   # a diagnostic build (tools/)

@@ -23,7 +23,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 SRCS = [os.path.join(HERE, "csrc", "codec_hip.hip"), os.path.join(HERE, "csrc", "codec_pee.hip"),
-        os.path.join(HERE, "csrc", "codec_quality.hip"), os.path.join(HERE, "csrc", "codec_records.hip")]
+        os.path.join(HERE, "csrc", "codec_quality.hip"), os.path.join(HERE, "csrc", "codec_records.hip"),
+        os.path.join(HERE, "csrc", "codec_crc.hip")]
 HDRS = [os.path.join(HERE, "csrc", "codec_common.h")]
 OUT = os.path.join(HERE, "libcodec_hip.so")
 INC = os.path.join(REPO, "include")
@@ -50,7 +51,8 @@ def _obj(src: str) -> str:
 
 
 def _common_deps():
-    return HDRS + [os.path.join(INC, "codec_tcc.h"), os.path.join(INC, "codec_tcc_ext.h")]
+    return HDRS + [os.path.join(INC, "codec_tcc.h"), os.path.join(INC, "codec_tcc_ext.h"),
+                   os.path.join(INC, "codec_tcc_crc.h")]
 
 
 def _digest(paths, flags) -> str:

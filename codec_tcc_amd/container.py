@@ -32,6 +32,10 @@ MED-PEE scheme 2 (four sublattice passes, oracle/pee_cpu.py) sets the scheme byt
 
 so a reader of scheme-1 files (scheme byte 0) refuses scheme-2 files instead of misreading.
 
+Either MED-PEE header may end with the 10-byte checksum extension b"C1" + >II (CRC-32 of the
+cover, CRC-32 of the embedded payload bits; checksum.py).  Readers slice the fixed fields by
+size, so files with it read where it is unknown and files without it are unchanged.
+
 Stego payload codecs: the reference's ids (png 1, j2k 2, jls 3, jxl 4) are kept; id 0
 ("raw", unknown to the reference) stores the stego pixels little-endian, uncompressed.
 """
@@ -185,6 +189,29 @@ def _pee_header(data: bytes, fmt_bytes: int, what: str) -> Tuple[bytes, bytes]:
     return hdr, data[8 + hlen:]
 
 
+_PEE_CRC_TAG = b"C1"
+_PEE_CRC_FMT = ">II"
+
+
+def pee_crc_extension(cover_crc32: int, payload_crc32: int) -> bytes:
+    """The 10-byte header extension of a checksummed MED-PEE file: b"C1" + the cover's and the
+    payload's CRC-32 (checksum.py), appended after the header's fixed fields.  Readers slice the
+    header by its fixed size, so files with it read as before where it is not known."""
+    return _PEE_CRC_TAG + struct.pack(_PEE_CRC_FMT, int(cover_crc32) & 0xFFFFFFFF, int(payload_crc32) & 0xFFFFFFFF)
+
+
+def _pee_crc_fields(ext: bytes) -> Dict:
+    """{'cover_crc32', 'payload_crc32'} of the header bytes after the fixed fields ({} when they
+    do not start the checksum extension); ValueError for a header cut inside it."""
+    n = len(_PEE_CRC_TAG) + struct.calcsize(_PEE_CRC_FMT)
+    if not ext or ext[:2] != _PEE_CRC_TAG[:len(ext[:2])]:
+        return {}
+    if len(ext) < n:
+        raise ValueError(f"truncated MED-PEE header: a checksum extension of {len(ext)} bytes, {n} needed")
+    c, p = struct.unpack(_PEE_CRC_FMT, ext[2:n])
+    return {"cover_crc32": c, "payload_crc32": p}
+
+
 def _pee_shape_check(bpp: int, width: int, height: int):
     if bpp not in (1, 2):
         raise ValueError(f"MED-PEE header: {bpp} bytes per pixel (1 or 2)")
@@ -223,7 +250,8 @@ def pee_scheme(data: bytes) -> int:
 
 
 def parse_pee2_bytes(data: bytes) -> Tuple[Dict, List[bytes], bytes]:
-    """A scheme-2 version-16 STGC file -> (side information with 'passes', 4 lm blobs, stego bytes)."""
+    """A scheme-2 version-16 STGC file -> (side information with 'passes', 4 lm blobs, stego bytes);
+    'cover_crc32' / 'payload_crc32' when the header carries the checksum extension."""
     if pee_scheme(data) != 2:
         raise ValueError("not a scheme-2 MED-PEE container")
     n0 = struct.calcsize(_PEE2_FMT)
@@ -242,11 +270,13 @@ def parse_pee2_bytes(data: bytes) -> Tuple[Dict, List[bytes], bytes]:
     md = {"version": PEE_VERSION, "scheme": 2, "codec": CODEC_NAMES.get(cid, "raw" if cid == 0 else "unknown"),
           "bytes": bpp, "width": width, "height": height, "T": T, "maxval": maxval, "L": L, "status": status,
           "passes": passes}
+    md.update(_pee_crc_fields(hdr[n0 + 4 * struct.calcsize(_PEE2_PASS):]))
     return md, blobs, body[pos:]
 
 
 def parse_pee_bytes(data: bytes) -> Tuple[Dict, bytes, bytes]:
-    """A version-16 STGC file of scheme 1 -> (side information, lm_blob, stego bytes)."""
+    """A version-16 STGC file of scheme 1 -> (side information, lm_blob, stego bytes);
+    'cover_crc32' / 'payload_crc32' when the header carries the checksum extension."""
     if pee_scheme(data) != 1:
         raise ValueError("a scheme-2 MED-PEE container: use parse_pee2_bytes")
     hdr, body = _pee_header(data, struct.calcsize(_PEE_FMT), "MED-PEE file")
@@ -258,4 +288,5 @@ def parse_pee_bytes(data: bytes) -> Tuple[Dict, bytes, bytes]:
     md = {"version": PEE_VERSION, "codec": CODEC_NAMES.get(cid, "raw" if cid == 0 else "unknown"),
           "bytes": bpp, "width": width, "height": height, "T": T, "L": L, "end": end, "maxval": maxval,
           "status": status}
+    md.update(_pee_crc_fields(hdr[struct.calcsize(_PEE_FMT):]))
     return md, body[:blob_size], body[blob_size:]

@@ -21,7 +21,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from . import _lib, framing
+from . import _lib, checksum as _ck, framing
 from .codec import _elem_bytes, _require_gpu, _stream, _torch
 
 
@@ -159,6 +159,8 @@ class PeeEncoded:
     payload_words: int
     config: dict = field(default_factory=dict)   # the PeeCodec's T / tmax / maxval (decode())
     scheme: int = 1                              # 2: four sublattice passes (meta / lm per pass)
+    cover_crc: object = None                     # torch.int32 [B] (device): CRC-32 of each cover (checksum=True)
+    payload_crc: Optional[List[int]] = None      # CRC-32 of each slice's payload bits (checksum.payload_crc32)
 
     def records(self) -> List[_lib.PeeMeta]:
         """Scheme 1: one record per slice.  Scheme 2: 4 * B records, pass-major."""
@@ -276,14 +278,36 @@ class PeeCodec:
             self.workspace.numel(), _stream()), "codec_pee_capacity"))
         return caps
 
-    def embed(self, covers, payloads, *, stego=None, lm=None, meta=None, packed=None, check: bool = True) -> PeeEncoded:
+    def embed(self, covers, payloads, *, stego=None, lm=None, meta=None, packed=None, check: bool = True,
+              checksum: bool = False) -> PeeEncoded:
         """cover -> stego + location map + per-slice meta.  check=True (default) reads the
         per-slice status back (one sync) and raises RuntimeError if an in-place look-back
         gave up (CODEC_PEE_ELOOKBACK: the slice is not a valid stego); check=False keeps
-        the call asynchronous (benchmarks) -- inspect enc.records() afterwards."""
+        the call asynchronous (benchmarks) -- inspect enc.records() afterwards.
+        checksum=True: enc.cover_crc = crc32_slices(covers), launched on the same stream BEFORE
+        the embed (so an in-place embed checksums the cover, not the stego), and
+        enc.payload_crc from the bits on the host (None with caller-packed `packed=` payloads:
+        the bits are not here); decode(enc) then verifies both."""
         torch = _torch()
         if tuple(covers.shape) != (self.B, self.H, self.W) or _elem_bytes(covers) != self.bytes:
             raise ValueError("covers do not match the codec's shape/dtype")
+        cover_crc = payload_crc = None
+        if checksum:
+            cover_crc = _ck.crc32_slices(covers)   # queued first: the host work below runs beside it
+            if packed is None:   # pack here (what _embed would do) and checksum the packed rows
+                bits = [framing.to_bits(p) for p in payloads]
+                if len(bits) != self.B:
+                    raise ValueError("one payload per slice is required")
+                rows, lengths = framing.pack_bits(bits)
+                payload_crc = [_ck.payload_crc32_packed(rows[b], lengths[b]) for b in range(self.B)]
+                packed = (torch.from_numpy(rows).to(self.device), lengths,
+                          torch.tensor(lengths, dtype=torch.int32, device=self.device))
+        enc = self._embed(covers, payloads, stego, lm, meta, packed, check)
+        enc.cover_crc, enc.payload_crc = cover_crc, payload_crc
+        return enc
+
+    def _embed(self, covers, payloads, stego, lm, meta, packed, check) -> PeeEncoded:
+        torch = _torch()
         words, lengths, lens_t = packed if packed is not None else self.pack_payloads(payloads)
         if stego is None:
             stego = torch.empty_like(covers)
@@ -402,9 +426,53 @@ class PeeCodec:
         check_records(recs, self.H, self.W, scheme=self.scheme, payload_words=enc.payload_words,
                       lm_words=self.lm_words, bytes=self.bytes, lengths=lengths)
 
-    def decode(self, enc: PeeEncoded):
+    def _verify(self, enc: PeeEncoded, mode, cover, rows):
+        """Compare the restored cover's and the payloads' CRC-32 with enc's (after the payload
+        read-back: the checksum launch was queued behind the extract, so this read-back waits for nothing
+        more).  rows: the extract's payload words on the host.  mode: checksum.verify_mode()."""
+        if mode is None:
+            return
+        have_c, have_p = enc.cover_crc is not None, enc.payload_crc is not None
+        if mode == "require" and not (have_c and have_p):
+            missing = [n for n, h in (("cover", have_c), ("payload", have_p)) if not h]
+            raise _ck.IntegrityError(f"MED-PEE decode: verify='require' and the embedding carries no "
+                                     f"{' / '.join(missing)} checksum")
+        bad_c, bad_p = [], []
+        if have_c:
+            if hasattr(enc.cover_crc, "detach"):   # one read-back for both
+                if enc.cover_crc.numel() != self.B:
+                    raise ValueError(f"{enc.cover_crc.numel()} cover checksums for {self.B} slices")
+                both = _ck.crc_list(_torch().cat([self._cover_crc, enc.cover_crc.reshape(-1).to(self._cover_crc)]))
+                got, want = both[:self.B], both[self.B:]
+            else:
+                got, want = _ck.crc_list(self._cover_crc), [int(v) & 0xFFFFFFFF for v in enc.cover_crc]
+                if len(want) != self.B:
+                    raise ValueError(f"{len(want)} cover checksums for {self.B} slices")
+            bad_c = [b for b in range(self.B) if got[b] != want[b]]
+        if have_p:
+            if len(enc.payload_crc) != self.B:
+                raise ValueError(f"{len(enc.payload_crc)} payload checksums for {self.B} slices")
+            bad_p = [b for b in range(self.B)
+                     if _ck.payload_crc32_packed(rows[b], enc.lengths[b]) != int(enc.payload_crc[b]) & 0xFFFFFFFF]
+        _ck.raise_mismatch(bad_c, bad_p)
+
+    def decode(self, enc: PeeEncoded, verify=True):
         """(list of 0/1 bit vectors, restored cover tensor); raises if a slice overflowed, and
-        ValueError for records that are not an embed's (check_records)."""
+        ValueError for records that are not an embed's (check_records).
+        verify=True: the checksums enc carries (embed(..., checksum=True)) are compared with the
+        restored cover's (one crc32_slices launch behind the extract) and the payloads';
+        IntegrityError names the slices and which of cover / payload failed.  verify=False
+        skips it; verify='require' also raises when a checksum is absent."""
+        mode = _ck.verify_mode(verify)
+        if mode == "require" and (enc.cover_crc is None or enc.payload_crc is None):
+            self._verify(enc, mode, None, None)
+        bits, cover = self._decode(enc, mode is not None and enc.cover_crc is not None)
+        self._verify(enc, mode, cover, self._payload_rows)
+        return bits, cover
+
+    def _decode(self, enc: PeeEncoded, crc: bool):
+        """decode() without the comparison; crc: queue crc32_slices(restored cover) behind the
+        extract, before the payload read-back (self._cover_crc)."""
         if enc.scheme != self.scheme:
             raise ValueError(f"a scheme-{enc.scheme} embedding given to a scheme-{self.scheme} codec")
         if self.scheme == 2:
@@ -415,14 +483,16 @@ class PeeCodec:
                 raise ValueError(f"payload exceeds PEE capacity in slices {short} (scheme 2, {self._t_text()})")
             self._check(enc, prs, enc.lengths)
             words, cover = self.extract(enc.stego, enc.meta, enc.lm, payload_words=enc.payload_words)
-            host = words.cpu().numpy()   # the extract passes have no look-back (tile or slice-serial)
+            self._cover_crc = _ck.crc32_slices(cover) if crc else None
+            host = self._payload_rows = words.cpu().numpy()   # the extract passes have no look-back (tile or slice-serial)
             return [framing.unpack_bits(host[i], enc.lengths[i]) for i in range(self.B)], cover
         recs = enc.records()
         _raise_lookback(recs)
         _raise_status(recs, self._t_text())
         self._check(enc, recs)
         words, cover = self.extract(enc.stego, enc.meta, enc.lm, payload_words=enc.payload_words)
-        host = words.cpu().numpy()
+        self._cover_crc = _ck.crc32_slices(cover) if crc else None
+        host = self._payload_rows = words.cpu().numpy()
         if self.lookback_failed(enc.payload_words):
             self.reset()
             raise RuntimeError("codec_pee_extract: in-place cursor look-back timed out; the recovered "
@@ -514,12 +584,13 @@ def _config_from_records(enc: "PeeEncoded") -> dict:
 
 
 def encode(covers, payloads: Sequence, *, T=2, tmax: int = 16, maxval: Optional[int] = None,
-           scheme: int = 1, tmin: int = 1) -> PeeEncoded:
+           scheme: int = 1, tmin: int = 1, checksum: bool = False) -> PeeEncoded:
     """MED-PEE embed of one payload per slice (the package's `encode(..., method="pee")`).
     covers: [B,H,W] / [H,W] uint8/uint16 torch tensor or numpy array; T: expansion threshold
     or "auto" (smallest T <= tmax whose capacity holds each slice's payload); maxval: the
     largest legal pixel value (e.g. 4095 for 12-bit DICOM; default the dtype's maximum);
     scheme 2: four sublattice passes; its T="auto" tries T = tmin .. tmax per slice in one launch.
+    checksum=True: the encoding carries the covers' and payloads' CRC-32 and decode() verifies them.
     Raises ValueError when a payload exceeds its slice's capacity."""
     from .codec import _as_batch
     _require_gpu()
@@ -528,7 +599,7 @@ def encode(covers, payloads: Sequence, *, T=2, tmax: int = 16, maxval: Optional[
         payloads = [payloads]
     dt = "uint16" if _elem_bytes(covers) == 2 else "uint8"
     codec = _codec_for(tuple(covers.shape), dt, T=T, tmax=tmax, maxval=maxval, scheme=scheme, tmin=tmin)
-    enc = codec.embed(covers, payloads)
+    enc = codec.embed(covers, payloads, checksum=checksum)
     if scheme == 2:
         short = [i for i, (g, n) in enumerate(zip(enc.embedded(), enc.lengths)) if g < n]
         if short:
@@ -538,16 +609,17 @@ def encode(covers, payloads: Sequence, *, T=2, tmax: int = 16, maxval: Optional[
     return enc
 
 
-def decode(enc: PeeEncoded, *, restore: bool = True):
+def decode(enc: PeeEncoded, verify=True, *, restore: bool = True):
     """Exact extraction: (payload_bit_lists, cover) like the LSB decode() -- payload_bit_lists[b]
     is a numpy 0/1 vector of slice b's embedded bits, cover the restored [B,H,W] tensor
-    (None with restore=False)."""
+    (None with restore=False).  verify: PeeCodec.decode's (True checks the checksums the
+    encoding carries, False skips, 'require' insists on them; IntegrityError on a mismatch)."""
     _require_gpu()
     cfg = enc.config or _config_from_records(enc)
     codec = _codec_for(tuple(enc.stego.shape), cfg.get("dtype", "uint16"), T=cfg.get("T", 2),
                        tmax=cfg.get("tmax", 16), maxval=cfg.get("maxval"), scheme=int(getattr(enc, "scheme", 1)),
                        tmin=cfg.get("tmin", 1))
-    bits, cover = codec.decode(enc)
+    bits, cover = codec.decode(enc, verify)
     return bits, (cover if restore else None)
 
 

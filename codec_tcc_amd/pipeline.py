@@ -139,14 +139,18 @@ def decode_bin_exact(filepath: str, search_block_size: Optional[int] = None) -> 
 
 # ------------------------------------------------------------------ MED-PEE files
 def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxval: Optional[int] = None,
-                    codec: str = "raw", scheme: int = 1, tmin: int = 1) -> Dict:
+                    codec: str = "raw", scheme: int = 1, tmin: int = 1, checksum: bool = False) -> Dict:
     """MED-PEE embed of one slice into a version-16 STGC file.  `image` is an array or a
     DICOM path; maxval defaults to the DICOM's full scale 2**BitsStored - 1 (4095 for the
     reference's 12-bit pe.dcm), else the dtype maximum.  T = 'auto' picks the smallest
     T <= tmax whose capacity holds the payload.  A payload beyond the capacity is truncated
     (status 1, 'L' = bits embedded); the file stays exactly reversible.  scheme 2: four
     sublattice passes (container scheme byte 2); with T = 'auto' the smallest T in tmin..tmax whose
-    four passes hold the payload, which the header and the returned 'T' then carry."""
+    four passes hold the payload, which the header and the returned 'T' then carry.
+    checksum=True: the header ends with the checksum extension (container.pee_crc_extension:
+    CRC-32 of the cover, from the GPU pass queued before the embed, and of the embedded
+    payload bits), which decode_bin_pee verifies; without it the file's bytes are unchanged."""
+    from . import checksum as _ck
     from .pee import PeeCodec, lm_bits
     _require_gpu()
     torch = _torch()
@@ -161,7 +165,13 @@ def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxva
     h, w = img.shape
     bits = framing.to_bits(payload)
     pc = PeeCodec(1, h, w, dtype=str(img.dtype), T=T, tmin=tmin, tmax=tmax, maxval=maxval, scheme=scheme)
-    enc = pc.embed(torch.from_numpy(np.ascontiguousarray(img)[None]).cuda(), [bits])
+    enc = pc.embed(torch.from_numpy(np.ascontiguousarray(img)[None]).cuda(), [bits], checksum=checksum)
+
+    def ext(embedded: int) -> Tuple[bytes, Dict]:
+        if not checksum:
+            return b"", {}
+        crcs = {"cover_crc32": _ck.crc_list(enc.cover_crc)[0], "payload_crc32": _ck.payload_crc32(bits[:embedded])}
+        return container.pee_crc_extension(crcs["cover_crc32"], crcs["payload_crc32"]), crcs
     if scheme == 2:
         prs = [pr[0] for pr in enc.pass_records()]
         blobs = [container.lm_blob(lm_bits(enc, 0, p)) if prs[p].end >= 0 else b"" for p in range(4)]
@@ -171,19 +181,21 @@ def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxva
         t_used = int(prs[0].T)   # T = 'auto': the slice's chosen T (every pass records it)
         hdr = container.create_pee2_header(codec, img.dtype.itemsize, w, h, t_used, pc.maxval, embedded, status,
                                            [(r.L, r.end, r.status, len(b)) for r, b in zip(prs, blobs)])
-        size = container.create_binary_file(out_path, hdr, _compress(stego, codec), b"".join(blobs))
+        xb, crcs = ext(embedded)
+        size = container.create_binary_file(out_path, hdr + xb, _compress(stego, codec), b"".join(blobs))
         return {"path": out_path, "bytes": size, "T": t_used, "L": embedded, "maxval": pc.maxval, "status": status,
                 "scheme": 2, "passes": [{"L": r.L, "end": r.end, "status": r.status, "lm_count": r.lm_count}
-                                        for r in prs], "stego": stego}
+                                        for r in prs], "stego": stego, **crcs}
     r = enc.records()[0]
     embedded = min(len(bits), r.capacity) if r.status == 1 else len(bits)
     lmb = container.lm_blob(lm_bits(enc, 0)) if r.end >= 0 else b""
     stego = enc.stego.cpu().numpy()[0]
     hdr = container.create_pee_header(codec, img.dtype.itemsize, w, h, r.T, embedded, r.end, r.maxval, r.status,
                                       len(lmb))
-    size = container.create_binary_file(out_path, hdr, _compress(stego, codec), lmb)
+    xb, crcs = ext(embedded)
+    size = container.create_binary_file(out_path, hdr + xb, _compress(stego, codec), lmb)
     return {"path": out_path, "bytes": size, "T": r.T, "L": embedded, "end": r.end, "maxval": r.maxval,
-            "status": r.status, "lm_count": r.lm_count, "stego": stego}
+            "status": r.status, "lm_count": r.lm_count, "stego": stego, **crcs}
 
 
 @dataclass
@@ -233,15 +245,23 @@ def read_pee_bytes(raw: bytes) -> PeeFile:
     return PeeFile(md=md, scheme=scheme, records=records, lm=lm, stego=stego, payload_words=pw, lm_words=lm_words)
 
 
-def decode_bin_pee(filepath: str) -> Tuple[np.ndarray, np.ndarray]:
+def decode_bin_pee(filepath: str, verify=True) -> Tuple[np.ndarray, np.ndarray]:
     """(payload bits as a 0/1 uint8 vector, restored cover) from a version-16 STGC file
-    (either scheme): read_pee_bytes on the host, then one extract launch."""
+    (either scheme): read_pee_bytes on the host, then one extract launch.
+    verify=True: a file with the checksum extension is checked -- the restored cover's CRC-32
+    (one GPU pass behind the extract) and the payload's against the header's; IntegrityError
+    names what failed.  False skips it; 'require' also raises for a file without checksums."""
+    from . import checksum as _ck
     from .pee import PeeCodec
+    mode = _ck.verify_mode(verify)
     with open(filepath, "rb") as f:
         pf = read_pee_bytes(f.read())
     _require_gpu()
     torch = _torch()
     md, h, w = pf.md, pf.stego.shape[0], pf.stego.shape[1]
+    have = "cover_crc32" in md
+    if mode == "require" and not have:
+        raise _ck.IntegrityError("MED-PEE file: verify='require' and the header carries no checksums")
     pc = PeeCodec(1, h, w, dtype=str(pf.stego.dtype), T=md["T"], maxval=md["maxval"], scheme=pf.scheme)
     metas = b"".join(bytes(r) for pr in pf.records for r in pr)
     meta_t = torch.frombuffer(bytearray(metas), dtype=torch.uint8).view(len(pf.records), 1, -1).cuda()
@@ -250,4 +270,9 @@ def decode_bin_pee(filepath: str) -> Tuple[np.ndarray, np.ndarray]:
         meta_t, lm_t = meta_t[0], lm_t[0]
     words, cover = pc.extract(torch.from_numpy(np.ascontiguousarray(pf.stego)[None]).cuda(), meta_t, lm_t,
                               payload_words=pf.payload_words)
-    return framing.unpack_bits(words.cpu().numpy()[0], md["L"]), cover.cpu().numpy()[0]
+    crc = _ck.crc32_slices(cover) if (mode and have) else None
+    bits = framing.unpack_bits(words.cpu().numpy()[0], md["L"])
+    if crc is not None:
+        _ck.raise_mismatch([0] if _ck.crc_list(crc)[0] != md["cover_crc32"] else [],
+                           [0] if _ck.payload_crc32(bits) != md["payload_crc32"] else [], "MED-PEE file")
+    return bits, cover.cpu().numpy()[0]
