@@ -2855,8 +2855,13 @@ __global__ __launch_bounds__(NTH) void k_pee_embed_res(const uint16_t* __restric
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const uint32_t w = q == 0 ? v1.x : q == 1 ? v1.y : q == 2 ? v1.z : v1.w;
-                    const int y = (int)(w >> 16) + res_med3(__builtin_amdgcn_sbfe((int)ep, 8 * q, 6), -Tthr, Tthr);
-                    if (((nr_b >> (8 * q + 7)) & 1u) && (unsigned)y <= (unsigned)maxval) safe_b |= 0x80u << (8 * q);
+                    // side-specific, as pee_classify: a left shift needs x - T >= 0 only (a cover
+                    // pixel above maxval moves down whether or not it lands inside), a right
+                    // shift x + T <= maxval only
+                    const int e6 = __builtin_amdgcn_sbfe((int)ep, 8 * q, 6);
+                    const int y = (int)(w >> 16) + res_med3(e6, -Tthr, Tthr);
+                    const bool fits = e6 < 0 ? y >= 0 : y <= maxval;
+                    if (((nr_b >> (8 * q + 7)) & 1u) && fits) safe_b |= 0x80u << (8 * q);
                 }
             }
             const uint32_t sel_b = proc_b & safe_b;

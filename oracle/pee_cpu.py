@@ -18,7 +18,11 @@ Scheme (integer only):
   expansion   -T <= e < T  : x' = pred + 2e + bit         (one payload bit)
   shifting    e >= T       : x' = x + T ;  e < -T : x' = x - T
   overflow    a candidate whose transform could leave [0, maxval] is left unchanged and
-              flagged in the location map (LM)
+              flagged in the location map (LM).  Each test looks at the side the transform
+              moves towards only (classify): a right shift needs x + T <= maxval, a left shift
+              x - T >= 0.  So a cover pixel ABOVE maxval (nothing refuses one; DICOM files
+              exceed their BitsStored) with e < -T is shifted down even when x - T > maxval --
+              every kernel does the same (tests/test_pee_adversarial.py, kind "above")
   cursor      payload bit j goes to the j-th expandable, non-overflow candidate in index
               order; processing stops at that candidate for j = L-1 ("end"); candidates
               after `end` are untouched.  Side information: T, L, end, maxval, LM[0..end].

@@ -75,14 +75,19 @@ def test_moment_math_random_pairs():
         assert got["diferenca_max"] == exp["diferenca_max"] and got["pixels_diferentes"] == exp["pixels_diferentes"]
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("dt,h,w,bsz", [("uint16", 512, 512, 3), ("uint16", 37, 53, 2), ("uint8", 64, 96, 4),
-                                        ("uint8", 33, 31, 1), ("uint16", 2048, 2048, 2),
-                                        ("u16full", 512, 512, 2), ("u16full", 2048, 2048, 1)])
-def test_gpu_moments_exact(dt, h, w, bsz):
-    """Exact integer moments; "u16full" = uniform 16-bit noise (products up to 65535^2, the
-    kernel's per-thread float64 sums at their largest)."""
-    torch = pytest.importorskip("torch")
+def _moment_pair(dt, h, w, bsz):
+    """The two batches of a test_gpu_moments_exact case.  A plain dtype name: a synthetic cover
+    and a copy changed by at most +-3 in 5 000 pixels.  "flat-" / "checker-" / "ends-" + dtype:
+    full-scale pairs from tests/pee_covers.py (all 0 vs all maximum; a checkerboard vs its
+    inverse; range-end pixels vs the same kind with another seed)."""
+    import pee_covers as PC
+    pair, _, name = dt.rpartition("-")
+    if pair:
+        first, second = {"flat": ("flat_zero", "flat_max"), "checker": ("checker", "checker_inv"),
+                         "ends": ("ends", "ends")}[pair]
+        a = np.stack([PC.cover(first, h, w, name, seed=10 + i) for i in range(bsz)])
+        b = np.stack([PC.cover(second, h, w, name, seed=50 + i) for i in range(bsz)])
+        return a, b
     gen = {"uint16": synth.ct12, "u16full": synth.GENERATORS["u16"]}.get(dt, synth.GENERATORS["u8"])
     rng = np.random.default_rng(h * w)
     a = np.stack([gen(h, w, 10 + i) for i in range(bsz)])
@@ -90,10 +95,51 @@ def test_gpu_moments_exact(dt, h, w, bsz):
     for i in range(bsz):
         idx = rng.choice(h * w, min(h * w, 5000), replace=False)
         b[i].flat[idx] ^= np.asarray(rng.integers(0, 4, idx.size), dtype=a.dtype)
-    got = Q.moments(torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda())
+    return a, b
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dt,h,w,bsz", [("uint16", 512, 512, 3), ("uint16", 37, 53, 2), ("uint8", 64, 96, 4),
+                                        ("uint8", 33, 31, 1), ("uint16", 2048, 2048, 2),
+                                        ("u16full", 512, 512, 2), ("u16full", 2048, 2048, 1),
+                                        # 520 x 504: npx % 8 == 0 and two workgroup regions, the second of
+                                        # 16 376 vectors -- unrolled rounds of 1 024 plus a partial tail
+                                        ("uint16", 520, 504, 2), ("uint8", 520, 504, 2),
+                                        ("flat-uint16", 520, 504, 2), ("flat-uint8", 520, 504, 2),
+                                        ("flat-uint16", 37, 53, 2), ("checker-uint16", 520, 504, 2),
+                                        ("checker-uint8", 33, 31, 2), ("ends-uint16", 520, 504, 2),
+                                        ("ends-uint8", 64, 96, 2), ("ends-uint16", 37, 53, 2),
+                                        # "@1": the storage starts one element into a larger buffer
+                                        ("uint16@1", 520, 504, 2), ("ends-uint16@1", 520, 504, 2),
+                                        ("uint8@1", 64, 96, 4), ("flat-uint8@1", 520, 504, 2)])
+def test_gpu_moments_exact(dt, h, w, bsz):
+    """Exact integer moments; "u16full" = uniform 16-bit noise (products up to 65535^2, the
+    kernel's per-thread float64 sums at their largest); the full-scale pairs of _moment_pair;
+    "@1": contiguous batches whose data_ptr is not vector-aligned, which selects the scalar
+    kernel although npx % 8 == 0."""
+    torch = pytest.importorskip("torch")
+    dt, _, off = dt.partition("@")
+    a, b = _moment_pair(dt, h, w, bsz)
+    if off:
+        assert (h * w) % 8 == 0
+        dev = []
+        for host in (a, b):
+            buf = np.zeros(host.size + 8, host.dtype)
+            buf[int(off):int(off) + host.size] = host.ravel()
+            t = torch.from_numpy(buf).cuda()[int(off):int(off) + host.size].view(bsz, h, w)
+            assert t.is_contiguous() and t.data_ptr() % (8 * host.itemsize) != 0
+            dev.append(t)
+        got = Q.moments(dev[0], dev[1])
+    else:
+        got = Q.moments(torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda())
     for i in range(bsz):
         m = O.moments(a[i], b[i])
         assert [int(x) for x in got[i]] == [m[k] for k in Q.KEYS]
+    if dt.startswith("flat-"):
+        full = int(np.iinfo(a.dtype).max)
+        for i in range(bsz):
+            m = dict(zip(Q.KEYS, (int(x) for x in got[i])))
+            assert (m["max_absdiff"], m["sum_ab"], m["sum_bb"]) == (full, 0, h * w * full * full)
 
 
 @pytest.mark.gpu
