@@ -11,6 +11,13 @@ the running image, about four times the capacity at one T; enc.meta / enc.lm the
 record / map per pass ([4, B, ...], pass-major).  With T="auto" each slice's workgroup tries
 T = tmin .. tmax inside one launch and keeps the first T that holds the payload
 (include/codec_tcc_ext.h, codec_pee_multi_embed_auto).
+
+Volume payloads (scheme 1; include/codec_tcc_vol.h): one bitstream across the whole stack,
+
+    vol = codec.embed_volume(covers, payload, policy="even")   # device plan + cut + embed
+    bits, covers = codec.decode_volume(vol)
+
+with the per-slice bit counts and T chosen on the device from the capacity curves.
 """
 from __future__ import annotations
 
@@ -179,6 +186,55 @@ class PeeEncoded:
         if self.scheme == 1:
             return [int(min(r.L, r.capacity)) if r.status == 1 else int(r.L) for r in self.records()]
         return [sum(int(pr[b].L) for pr in self.pass_records()) for b in range(len(self.lengths))]
+
+
+VOLUME_NMAX = 2 ** 31 - 1   # include/codec_tcc_vol.h: bits of one volume stream, and B * (H//2) * (W//2)
+
+
+def check_volume_args(shape, nbits: int, policy: str = "even", scheme: int = 1) -> None:
+    """The argument rules of a volume embed (include/codec_tcc_vol.h), as ValueError before any
+    launch.  Pure host code: no GPU, no library load."""
+    if int(scheme) != 1:
+        raise ValueError("volume payloads are scheme 1's: scheme 2 has no cover-side capacity to plan with "
+                         "(DESIGN §3b-2)")
+    if policy not in _lib.VOL_POLICIES:
+        raise ValueError(f"policy must be one of {sorted(_lib.VOL_POLICIES)}, got {policy!r}")
+    if len(shape) != 3 or min(int(v) for v in shape) < 1:
+        raise ValueError(f"a volume is a [B, H, W] stack with no empty dimension, got shape {tuple(shape)}")
+    B, H, W = (int(v) for v in shape)
+    if B * (H // 2) * (W // 2) > VOLUME_NMAX:
+        raise ValueError(f"B * (H // 2) * (W // 2) = {B * (H // 2) * (W // 2)} candidates exceed 2^31 - 1")
+    if not 0 <= int(nbits) <= VOLUME_NMAX:
+        raise ValueError(f"a volume payload holds 0 .. 2^31 - 1 bits, got {int(nbits)}")
+
+
+@dataclass
+class PeeVolume:
+    """One bitstream embedded across a slice stack (PeeCodec.embed_volume).  enc is an ordinary
+    scheme-1 PeeEncoded -- every slice stays decodable and storable by the per-slice code;
+    enc.lengths holds the slices' bit counts once they were read back (check=True, or
+    decode_volume), zeros before."""
+    enc: PeeEncoded
+    total_bits: int                   # the stream's bits (what was asked for)
+    policy: str
+    plan: object                      # torch.int32 [3 B + 1] (device): n[B], T[B], off[B + 1]
+    info: object                      # torch.int32 [8] (device): codec_pee_volume_info
+    payload_crc: Optional[int] = None   # CRC-32 of the whole stream (checksum.payload_crc32)
+    embedded_bits: Optional[int] = None  # info.total, once read back (check=True): < total_bits when truncated
+
+    def plan_host(self) -> dict:
+        """n, t, off (numpy) and the info record's fields: one read-back."""
+        torch = _torch()
+        B = len(self.enc.lengths)
+        both = torch.cat([self.plan.reshape(-1), self.info.reshape(-1)]).cpu().numpy()
+        return _plan_dict(both[:3 * B + 1], both[3 * B + 1:], B)
+
+
+def _plan_dict(plan, info, B: int) -> dict:
+    i = _lib.PeeVolumeInfo.from_buffer_copy(np.ascontiguousarray(info, dtype=np.int32).tobytes())
+    return {"n": plan[:B].copy(), "t": plan[B:2 * B].copy(), "off": plan[2 * B:3 * B + 1].copy(),
+            "status": int(i.status), "T": int(i.T), "total": int(i.total), "requested": int(i.requested),
+            "capacity": int(i.capacity), "policy": {v: k for k, v in _lib.VOL_POLICIES.items()}[int(i.policy)]}
 
 
 class PeeCodec:
@@ -439,16 +495,7 @@ class PeeCodec:
                                      f"{' / '.join(missing)} checksum")
         bad_c, bad_p = [], []
         if have_c:
-            if hasattr(enc.cover_crc, "detach"):   # one read-back for both
-                if enc.cover_crc.numel() != self.B:
-                    raise ValueError(f"{enc.cover_crc.numel()} cover checksums for {self.B} slices")
-                both = _ck.crc_list(_torch().cat([self._cover_crc, enc.cover_crc.reshape(-1).to(self._cover_crc)]))
-                got, want = both[:self.B], both[self.B:]
-            else:
-                got, want = _ck.crc_list(self._cover_crc), [int(v) & 0xFFFFFFFF for v in enc.cover_crc]
-                if len(want) != self.B:
-                    raise ValueError(f"{len(want)} cover checksums for {self.B} slices")
-            bad_c = [b for b in range(self.B) if got[b] != want[b]]
+            bad_c = self._cover_mismatches(enc)
         if have_p:
             if len(enc.payload_crc) != self.B:
                 raise ValueError(f"{len(enc.payload_crc)} payload checksums for {self.B} slices")
@@ -498,6 +545,167 @@ class PeeCodec:
             raise RuntimeError("codec_pee_extract: in-place cursor look-back timed out; the recovered "
                                "payload is invalid (the restored cover is exact)")
         return [framing.unpack_bits(host[i], enc.lengths[i]) for i in range(self.B)], cover
+
+    # ---- volume payloads: one bitstream across the stack (include/codec_tcc_vol.h)
+    def _volume_workspace(self, payload_words: int, tmax: int):
+        """The volume workspace for this row pitch (capacity curves, payload rows, offsets); the
+        last few are kept, so a steady stream of equal-sized payloads allocates once per side."""
+        torch = _torch()
+        key = (int(payload_words), int(tmax))
+        cache = self.__dict__.setdefault("_vol_ws", OrderedDict())
+        if key not in cache:
+            n = int(_lib.load().codec_pee_volume_workspace_bytes(C.byref(self._params(payload_words)), tmax))
+            if n == 0:
+                _lib.check(-1, "codec_pee_volume_workspace_bytes")
+            cache[key] = torch.empty(n, dtype=torch.uint8, device=self.device)
+            while len(cache) > 4:
+                cache.popitem(last=False)
+        cache.move_to_end(key)
+        return cache[key]
+
+    def volume_buffers(self):
+        """(lm, side) for embed_volume(..., buffers=): the location map and the one int32 buffer
+        that holds records, plan and info, so that a caller (a captured graph) can preallocate."""
+        torch = _torch()
+        lm = torch.empty((self.B, self.lm_words), dtype=torch.int64, device=self.device)
+        side = torch.empty(self.B * _lib.PEE_META_BYTES // 4 + 3 * self.B + 1 + _lib.PEE_VOLUME_INFO_BYTES // 4,
+                           dtype=torch.int32, device=self.device)
+        return lm, side
+
+    def pack_volume(self, payload):
+        """(stream words on the device, bit count) for embed_volume(..., packed=): the upload a
+        caller does once when the same call is captured into a graph."""
+        bits = framing.to_bits(payload)
+        check_volume_args((self.B, self.H, self.W), bits.size, "even", self.scheme)
+        return _torch().from_numpy(framing.pack_bits([bits])[0].reshape(-1)).to(self.device), int(bits.size)
+
+    def embed_volume(self, covers, payload, *, policy: str = "even", stego=None, check: bool = True,
+                     checksum: bool = False, buffers=None, packed=None) -> "PeeVolume":
+        """One payload (str / bytes / 0-1 vector, framing.to_bits) embedded across the whole
+        stack: the device plans how many bits each slice takes and at which T (the rule of
+        include/codec_tcc_vol.h: policy "even" spreads the bits in proportion to the slices'
+        capacities at the smallest volume T that holds them, "fill" fills slices in order; each
+        slice then gets the smallest T that holds its share), cuts the stream into payload rows
+        and embeds them -- capacity pass, plan, cut and embed are queued on the current stream,
+        no host round trip.  tmax is the codec's; the T given at construction is
+        ignored here.  Scheme 1 only.
+        check=True (default): one read-back of records, plan and info fills enc.lengths and
+        embedded_bits, raises RuntimeError if an in-place look-back gave up (the workspace is
+        reset, as embed does); a payload beyond the volume's capacity at tmax is truncated to
+        it (info status 1, embedded_bits < total_bits; every slice stays reversible).
+        check=False keeps the call asynchronous.
+        checksum=True: enc.cover_crc per slice as embed, plus one payload CRC over the whole
+        stream (over the embedded prefix when check=True saw a truncation); decode_volume
+        verifies both.  stego may be the covers (in place).  buffers: volume_buffers();
+        packed: pack_volume()'s result instead of `payload` (no upload in the call; the payload
+        CRC is then absent, as with embed's packed=)."""
+        torch = _torch()
+        if tuple(covers.shape) != (self.B, self.H, self.W) or _elem_bytes(covers) != self.bytes:
+            raise ValueError("covers do not match the codec's shape/dtype")
+        bits = framing.to_bits(payload) if packed is None else None
+        N = int(bits.size) if packed is None else int(packed[1])
+        check_volume_args((self.B, self.H, self.W), N, policy, self.scheme)
+        pw = max(1, min((N + 63) // 64, self.lm_words))
+        words = packed[0] if packed is not None else \
+            torch.from_numpy(framing.pack_bits([bits])[0].reshape(-1)).to(self.device)
+        if words.element_size() != 8 or words.numel() < max(1, (N + 63) // 64) or not words.is_contiguous():
+            raise ValueError("the packed stream must hold ceil(bits / 64) contiguous 64-bit words")
+        cover_crc = _ck.crc32_slices(covers) if checksum else None   # before an in-place embed
+        if stego is None:
+            stego = torch.empty_like(covers)
+        lm, side = buffers if buffers is not None else self.volume_buffers()
+        nm = self.B * _lib.PEE_META_BYTES // 4
+        if tuple(lm.shape) != (self.B, self.lm_words) or lm.element_size() != 8 or not lm.is_contiguous() or \
+                side.dim() != 1 or side.numel() != nm + 3 * self.B + 1 + _lib.PEE_VOLUME_INFO_BYTES // 4 or \
+                side.element_size() != 4 or not side.is_contiguous():
+            raise ValueError("buffers must be what volume_buffers() returns")
+        meta = side[:nm].view(torch.uint8).view(self.B, _lib.PEE_META_BYTES)
+        plan, info = side[nm:nm + 3 * self.B + 1], side[nm + 3 * self.B + 1:]
+        vws = self._volume_workspace(pw, self.tmax)
+        P = self._params(pw)
+        n_ptr = plan.data_ptr()
+        self._guarded(lambda: _lib.check(_lib.load().codec_pee_volume_embed(
+            C.byref(P), covers.data_ptr(), stego.data_ptr(), words.data_ptr(), N, _lib.VOL_POLICIES[policy], self.tmax,
+            n_ptr, n_ptr + 4 * self.B, n_ptr + 8 * self.B, info.data_ptr(), meta.data_ptr(), lm.data_ptr(),
+            self.workspace.data_ptr(), self.workspace.numel(), vws.data_ptr(), vws.numel(), _stream()),
+            "codec_pee_volume_embed"))
+        enc = PeeEncoded(stego=stego, lm=lm, meta=meta, lengths=[0] * self.B, payload_words=pw,
+                         config=dict(self.config, T="auto"), cover_crc=cover_crc)
+        vol = PeeVolume(enc=enc, total_bits=N, policy=policy, plan=plan, info=info,
+                        payload_crc=_ck.payload_crc32(bits) if checksum and bits is not None else None)
+        if check:
+            host = side.cpu().numpy()   # records, plan and info: one read-back
+            raw = host[:nm].tobytes()
+            recs = [_lib.PeeMeta.from_buffer_copy(raw, i * _lib.PEE_META_BYTES) for i in range(self.B)]
+            if any(r.status not in (0, 1) for r in recs):
+                self.reset()
+            _raise_lookback(recs)
+            p = _plan_dict(host[nm:nm + 3 * self.B + 1], host[nm + 3 * self.B + 1:], self.B)
+            enc.lengths = [int(v) for v in p["n"]]
+            vol.embedded_bits = p["total"]
+            if checksum and bits is not None and p["total"] < N:
+                vol.payload_crc = _ck.payload_crc32(bits[:p["total"]])
+        return vol
+
+    def decode_volume(self, vol: "PeeVolume", verify=True):
+        """(bits, covers): the stream's embedded bits as one 0/1 vector (the first
+        embedded_bits of a truncated volume) and the restored stack.  The records are read back
+        and judged by check_records first; extract and the stream's reassembly are launches on
+        the current stream, then one read-back of the stream.  verify as decode(): the cover
+        CRCs per slice and the one payload CRC embed_volume(checksum=True) recorded."""
+        torch = _torch()
+        mode = _ck.verify_mode(verify)
+        enc = vol.enc
+        if enc.scheme != 1 or self.scheme != 1:
+            raise ValueError("volume payloads are scheme 1's")
+        have_c, have_p = enc.cover_crc is not None, vol.payload_crc is not None
+        if mode == "require" and not (have_c and have_p):
+            missing = [n for n, h in (("cover", have_c), ("payload", have_p)) if not h]
+            raise _ck.IntegrityError(f"MED-PEE decode: verify='require' and the volume carries no "
+                                     f"{' / '.join(missing)} checksum")
+        recs = enc.records()
+        _raise_lookback(recs)
+        _raise_status(recs, "volume, " + self._t_text())
+        self._check(enc, recs)
+        enc.lengths = [int(r.L) for r in recs]
+        sw = max(1, (int(vol.total_bits) + 63) // 64)
+        out = torch.empty(sw + 1, dtype=torch.int64, device=self.device)   # the stream, then the total
+        cover = torch.empty_like(enc.stego)
+        vws = self._volume_workspace(enc.payload_words, 1)
+        P = self._params(enc.payload_words)
+        self._guarded(lambda: _lib.check(_lib.load().codec_pee_volume_extract(
+            C.byref(P), enc.stego.data_ptr(), enc.meta.data_ptr(), enc.lm.data_ptr(), cover.data_ptr(), out.data_ptr(),
+            sw, out.data_ptr() + 8 * sw, self.workspace.data_ptr(), self.workspace.numel(), vws.data_ptr(),
+            vws.numel(), _stream()), "codec_pee_volume_extract"))
+        self._cover_crc = _ck.crc32_slices(cover) if (mode is not None and have_c) else None
+        host = out.cpu().numpy()
+        if self.lookback_failed(enc.payload_words):
+            self.reset()
+            raise RuntimeError("codec_pee_extract: in-place cursor look-back timed out; the recovered "
+                               "payload is invalid (the restored cover is exact)")
+        total = min(int(host[sw:].view(np.int32)[0]), int(vol.total_bits))
+        bits = framing.unpack_bits(host[:sw], total)
+        if mode is not None:
+            bad_c = self._cover_mismatches(enc) if have_c else []
+            parts = [f"cover checksum mismatch in slices {bad_c}"] if bad_c else []
+            if have_p and _ck.payload_crc32(bits) != int(vol.payload_crc) & 0xFFFFFFFF:
+                parts.append("the volume's payload checksum does not match")
+            if parts:
+                raise _ck.IntegrityError(f"MED-PEE decode: {'; '.join(parts)} (CRC-32: this is not what was embedded)")
+        return bits, cover
+
+    def _cover_mismatches(self, enc: PeeEncoded) -> List[int]:
+        """Slices whose restored cover's CRC-32 (self._cover_crc) differs from enc.cover_crc."""
+        if hasattr(enc.cover_crc, "detach"):   # one read-back for both
+            if enc.cover_crc.numel() != self.B:
+                raise ValueError(f"{enc.cover_crc.numel()} cover checksums for {self.B} slices")
+            both = _ck.crc_list(_torch().cat([self._cover_crc, enc.cover_crc.reshape(-1).to(self._cover_crc)]))
+            got, want = both[:self.B], both[self.B:]
+        else:
+            got, want = _ck.crc_list(self._cover_crc), [int(v) & 0xFFFFFFFF for v in enc.cover_crc]
+            if len(want) != self.B:
+                raise ValueError(f"{len(want)} cover checksums for {self.B} slices")
+        return [b for b in range(self.B) if got[b] != want[b]]
 
 
 def _check_multi_args(B: int, lm_words: int, meta, lm, *, payload=None, payload_words: Optional[int] = None):
@@ -620,6 +828,41 @@ def decode(enc: PeeEncoded, verify=True, *, restore: bool = True):
                        tmax=cfg.get("tmax", 16), maxval=cfg.get("maxval"), scheme=int(getattr(enc, "scheme", 1)),
                        tmin=cfg.get("tmin", 1))
     bits, cover = codec.decode(enc, verify)
+    return bits, (cover if restore else None)
+
+
+def encode_volume(covers, payload, *, policy: str = "even", tmax: int = 16, maxval: Optional[int] = None,
+                  checksum: bool = False, scheme: int = 1) -> PeeVolume:
+    """MED-PEE embed of ONE payload across a [B,H,W] stack (PeeCodec.embed_volume): the bits are
+    spread over the slices on the device (policy "even": in proportion to capacity; "fill": in
+    slice order), each slice at the smallest T <= tmax that holds its share.  Raises ValueError
+    when the volume cannot hold the payload at tmax, as encode() does per slice; argument errors
+    (policy, scheme 2, more than 2^31 - 1 bits or candidates, a shape that is no stack) are
+    ValueError before the GPU is touched."""
+    from .codec import _as_batch
+    shape = tuple(covers.shape)
+    bits = framing.to_bits(payload)
+    check_volume_args(shape if len(shape) != 2 else (1,) + shape, bits.size, policy, scheme)
+    _require_gpu()
+    covers = _as_batch(covers)
+    dt = "uint16" if _elem_bytes(covers) == 2 else "uint8"
+    codec = _codec_for(tuple(covers.shape), dt, T="auto", tmax=tmax, maxval=maxval)
+    vol = codec.embed_volume(covers, bits, policy=policy, checksum=checksum)
+    if vol.embedded_bits < vol.total_bits:
+        raise ValueError(f"payload of {vol.total_bits} bits exceeds the volume's PEE capacity "
+                         f"{vol.embedded_bits} (tmax={tmax})")
+    return vol
+
+
+def decode_volume(vol: PeeVolume, verify=True, *, restore: bool = True):
+    """(bits, covers) of an encode_volume / embed_volume result: the payload as one 0/1 vector and
+    the restored [B,H,W] stack (None with restore=False).  verify: as decode()."""
+    _require_gpu()
+    enc = vol.enc
+    cfg = enc.config or _config_from_records(enc)
+    codec = _codec_for(tuple(enc.stego.shape), cfg.get("dtype", "uint16"), T="auto", tmax=cfg.get("tmax", 16),
+                       maxval=cfg.get("maxval"))
+    bits, cover = codec.decode_volume(vol, verify)
     return bits, (cover if restore else None)
 
 
