@@ -137,7 +137,8 @@ KERNEL_TAGS = {1: "k_scan_fast", 2: "k_scan_generic", 3: "k_block_exact", 4: "k_
                26: "k_pee_embed_ss_auto", 27: "k_pee_embed_res", 28: "k_scan_decide",
                29: "k_pee_lat_count", 30: "k_pee_lat_embed", 31: "k_pee_lat_dcount", 32: "k_pee_lat_recover",
                33: "k_pee_lat_ss_embed", 34: "k_pee_lat_ss_extract", 35: "k_pee_lat_auto",
-               36: "k_crc32", 37: "k_crc32_combine", 38: "k_vol_plan", 39: "k_vol_scatter", 40: "k_vol_gather"}
+               36: "k_crc32", 37: "k_crc32_combine", 38: "k_vol_plan", 39: "k_vol_scatter", 40: "k_vol_gather",
+               41: "k_pee_gate_table"}
 EXPORTS = tuple(_SIGS)
 # include/codec_tcc_ext.h: entries added after codec_tcc.h's list (EXPORTS) was fixed
 _SIGS_EXT = {
@@ -175,6 +176,21 @@ _SIGS_VOL = {
                                            C.c_size_t, _VP, C.c_size_t, _VP]),
 }
 EXPORTS_VOL = tuple(_SIGS_VOL)
+# include/codec_tcc_gate.h: smoothness-gated MED-PEE (pee.py, PeeCodec(gate=...))
+GATES = (0, 1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64, 96, 128, 65535)   # the capacity table's ladder
+GATE_TMAX = 16            # CODEC_PEE_GATE_TMAX
+GATE_MAX = 65535          # CODEC_PEE_GATE_MAX
+GATE_MAX_NC = 1 << 26     # CODEC_PEE_GATE_MAX_NC
+_SIGS_GATE = {
+    "codec_pee_gate_workspace_bytes": (C.c_size_t, [C.POINTER(PeeParams), C.c_int32]),
+    "codec_pee_gate_capacity": (C.c_int, [C.POINTER(PeeParams), _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP,
+                                          _VP, _VP, _VP, C.c_size_t, _VP]),
+    "codec_pee_gate_embed": (C.c_int, [C.POINTER(PeeParams), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "codec_pee_gate_embed_auto": (C.c_int, [C.POINTER(PeeParams), _VP, _VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP,
+                                            _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "codec_pee_gate_extract": (C.c_int, [C.POINTER(PeeParams), _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+}
+EXPORTS_GATE = tuple(_SIGS_GATE)
 
 _lib = None
 _load_error = None
@@ -203,7 +219,7 @@ def load(path: str = LIB_PATH):
     except OSError as e:  # pragma: no cover - environment specific
         _load_error = e
         raise RuntimeError(f"cannot load {path}: {e}") from e
-    for name, (res, args) in {**_SIGS, **_SIGS_EXT, **_SIGS_CRC, **_SIGS_VOL}.items():
+    for name, (res, args) in {**_SIGS, **_SIGS_EXT, **_SIGS_CRC, **_SIGS_VOL, **_SIGS_GATE}.items():
         fn = getattr(lib, name, None)
         if fn is None:
             if name == "codec_build_digest" and not in_tree:   # a diagnostic build (tools/)

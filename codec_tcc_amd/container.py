@@ -234,8 +234,44 @@ def create_pee2_header(codec: str, bytes_per_px: int, width: int, height: int, T
     return hdr + b"".join(struct.pack(_PEE2_PASS, int(a), int(b), int(c), int(d)) for a, b, c, d in passes)
 
 
+PEE_SCHEME_GATE = 3
+_PEE_GATE_FMT = ">H"
+
+
+def create_pee_gate_header(codec: str, bytes_per_px: int, width: int, height: int, T: int, L: int, end: int,
+                           maxval: int, status: int, lm_blob_size: int, gate: int) -> bytes:
+    """Header of a smoothness-gated scheme-1 file (scheme byte 3): scheme 1's fixed fields, then
+    the gate as >H.  A reader that does not know the byte refuses the file, so a gated file is
+    never decoded ungated."""
+    if not 0 <= int(gate) <= 0xFFFF:
+        raise ValueError(f"gate = {gate}: 0..65535")
+    return struct.pack(_PEE_FMT, PEE_VERSION, CODEC_IDS.get(codec.lower(), 0), int(bytes_per_px), PEE_SCHEME_GATE,
+                       width, height, int(T), int(L), int(end), int(maxval), int(status), int(lm_blob_size)) + \
+        struct.pack(_PEE_GATE_FMT, int(gate))
+
+
+def parse_pee_gate_bytes(data: bytes) -> Tuple[Dict, bytes, bytes]:
+    """A gated version-16 STGC file (scheme byte 3) -> (side information with 'gate', lm_blob,
+    stego bytes); 'cover_crc32' / 'payload_crc32' when the header carries the checksum extension."""
+    if pee_scheme(data) != PEE_SCHEME_GATE:
+        raise ValueError("not a gated MED-PEE container (scheme byte 3)")
+    n0 = struct.calcsize(_PEE_FMT)
+    hdr, body = _pee_header(data, n0 + struct.calcsize(_PEE_GATE_FMT), "gated MED-PEE file")
+    (_v, cid, bpp, _s, width, height, T, L, end, maxval, status, blob_size) = struct.unpack(_PEE_FMT, hdr[:n0])
+    (gate,) = struct.unpack(_PEE_GATE_FMT, hdr[n0:n0 + struct.calcsize(_PEE_GATE_FMT)])
+    _pee_shape_check(bpp, width, height)
+    if blob_size > len(body):
+        raise ValueError(f"truncated MED-PEE file: a location-map blob of {blob_size} bytes, {len(body)} left")
+    md = {"version": PEE_VERSION, "scheme": PEE_SCHEME_GATE, "codec": CODEC_NAMES.get(cid, "raw" if cid == 0 else "unknown"),
+          "bytes": bpp, "width": width, "height": height, "T": T, "L": L, "end": end, "maxval": maxval,
+          "status": status, "gate": gate}
+    md.update(_pee_crc_fields(hdr[n0 + struct.calcsize(_PEE_GATE_FMT):]))
+    return md, body[:blob_size], body[blob_size:]
+
+
 def pee_scheme(data: bytes) -> int:
-    """1 or 2: the MED-PEE scheme of a version-16 STGC file (its scheme byte)."""
+    """1, 2 or 3: the MED-PEE scheme of a version-16 STGC file (its scheme byte; 3 = scheme 1
+    with a smoothness gate)."""
     if data[:4] != MAGIC:
         raise ValueError("Arquivo inválido ou com assinatura incorreta.")   # codec.py:698
     if len(data) < 8:
@@ -244,9 +280,9 @@ def pee_scheme(data: bytes) -> int:
     hdr = data[8:8 + hlen]
     if len(hdr) < 4 or hdr[0] != PEE_VERSION:
         raise ValueError("not a MED-PEE container (version 16)")
-    if hdr[3] not in (0, PEE_SCHEME2):
+    if hdr[3] not in (0, PEE_SCHEME2, PEE_SCHEME_GATE):
         raise ValueError(f"unknown MED-PEE scheme byte {hdr[3]}")
-    return 2 if hdr[3] == PEE_SCHEME2 else 1
+    return 1 if hdr[3] == 0 else int(hdr[3])
 
 
 def parse_pee2_bytes(data: bytes) -> Tuple[Dict, List[bytes], bytes]:
@@ -277,7 +313,10 @@ def parse_pee2_bytes(data: bytes) -> Tuple[Dict, List[bytes], bytes]:
 def parse_pee_bytes(data: bytes) -> Tuple[Dict, bytes, bytes]:
     """A version-16 STGC file of scheme 1 -> (side information, lm_blob, stego bytes);
     'cover_crc32' / 'payload_crc32' when the header carries the checksum extension."""
-    if pee_scheme(data) != 1:
+    scheme = pee_scheme(data)
+    if scheme == PEE_SCHEME_GATE:
+        raise ValueError("a gated MED-PEE container (scheme byte 3): use parse_pee_gate_bytes")
+    if scheme != 1:
         raise ValueError("a scheme-2 MED-PEE container: use parse_pee2_bytes")
     hdr, body = _pee_header(data, struct.calcsize(_PEE_FMT), "MED-PEE file")
     (_v, cid, bpp, _r, width, height, T, L, end, maxval, status, blob_size) = struct.unpack(

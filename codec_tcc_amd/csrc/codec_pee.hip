@@ -70,6 +70,36 @@ __device__ __forceinline__ PeeCand pee_classify(int x, int a, int b, int c, int 
     return r;
 }
 
+// ---- smoothness gate (tests/pee_gate_spec.py; include/codec_tcc_gate.h).  A candidate is
+// active iff the roughness D = max(a, b, c) - min(a, b, c) of its (never modified) MED
+// neighbours is <= G.  An inactive candidate is left alone, flags nothing and counts nowhere,
+// which is exactly the scheme at a threshold of 0: nothing expands (-0 <= e < 0 is empty) and
+// both shifts move by 0.  So every gated kernel runs the ungated arithmetic with the
+// candidate's own threshold pee_gate_t() = (D <= G ? T : 0); the embed side also forces `safe`
+// (a shift by 0 never overflows, whatever the cover holds above maxval).  GATE = false
+// instantiations compile to the code they were before.
+#define PEE_GATE_OFF 0x7FFFFFFF   // every candidate active
+template <bool GATE>
+__device__ __forceinline__ int pee_gate_t(int a, int b, int c, int T, int G) {
+    if constexpr (!GATE) return T;
+    const int d = max(max(a, b), c) - min(min(a, b), c);
+    return d <= G ? T : 0;
+}
+// classification at the candidate's own threshold *te
+template <bool GATE>
+__device__ __forceinline__ PeeCand pee_classify_g(int x, int a, int b, int c, int T, int maxval, int G, int* te) {
+    *te = pee_gate_t<GATE>(a, b, c, T, G);
+    PeeCand r = pee_classify(x, a, b, c, *te, maxval);
+    if constexpr (GATE) r.safe |= *te == 0;
+    return r;
+}
+// the gate a record carries: reserved[1] = G + 1, 0 = ungated (never above 65536 in a record
+// check_records() passed; any other value only changes which candidates count as active)
+__device__ __forceinline__ int pee_rec_gate(const codec_pee_meta* M) {
+    const int r = M->reserved[1];
+    return r > 0 ? r - 1 : PEE_GATE_OFF;
+}
+
 // candidate k of a slice (scalar access; used for prefix tiles and odd shapes)
 template <typename T>
 __device__ __forceinline__ void pee_load(const T* img, int W, int wc, int k, int* x, int* a, int* b, int* c) {
@@ -149,10 +179,11 @@ struct Quad {
 // 8 loads issued up front), tiles swept grid-stride over the whole batch in address order
 // (global tile g = slice * ntiles + t), so the resident waves read one moving window of
 // HBM; the wave's shuffle reduction writes the tile count directly (no LDS, no barrier).
-template <typename T, bool NT>
+template <typename T, bool NT, bool GATE = false>
 __global__ __launch_bounds__(256) void k_pee_scan(const T* __restrict__ cover, T* __restrict__ stego, int H, int W,
                                                   int T0, int maxval, uint32_t* __restrict__ tile_cnt_all,
-                                                  int ntiles_max, int B, const int32_t* __restrict__ tps) {
+                                                  int ntiles_max, int B, const int32_t* __restrict__ tps,
+                                                  const int32_t* __restrict__ gps) {
     typedef typename Vec8<T>::type V;
     const size_t npx = (size_t)H * W;
     const int CR = W / 8, hc = H / 2;
@@ -164,6 +195,7 @@ __global__ __launch_bounds__(256) void k_pee_scan(const T* __restrict__ cover, T
     for (uint32_t g = blockIdx.x * 4u + (threadIdx.x >> 6); g < total; g += wstride) {
         const uint32_t b = g / ntiles, t = g - b * ntiles;
         const int Tthr = tps ? tps[b] : T0;   // per-slice threshold (capacity control) or one for all
+        const int G = GATE ? gps[b] : PEE_GATE_OFF;
         const T* src = cover + b * npx;
         T* dst = stego + b * npx;
         V v0[4], v1[4];
@@ -194,7 +226,8 @@ __global__ __launch_bounds__(256) void k_pee_scan(const T* __restrict__ cover, T
                 } else {
                     x = (int)px8(v1[u], 2 * k + 1); a = (int)px8(v1[u], 2 * k); bb = (int)px8(v0[u], 2 * k + 1); cc = (int)px8(v0[u], 2 * k);
                 }
-                const PeeCand pc = pee_classify(x, a, bb, cc, Tthr, maxval);
+                int te;
+                const PeeCand pc = pee_classify_g<GATE>(x, a, bb, cc, Tthr, maxval, G, &te);
                 cnt += (pc.expand && pc.safe) ? 1u : 0u;
             }
         }
@@ -212,13 +245,15 @@ __global__ __launch_bounds__(256) void k_pee_scan(const T* __restrict__ cover, T
 }
 
 // ---- scan for any shape: counts only (the copy is a separate stream copy)
-template <typename T>
+template <typename T, bool GATE = false>
 __global__ __launch_bounds__(256) void k_pee_count(const T* __restrict__ img, int H, int W, int T0, int maxval,
                                                    int tiles_per_wg, uint32_t* __restrict__ tile_cnt_all,
-                                                   int ntiles_max, const int32_t* __restrict__ tps) {
+                                                   int ntiles_max, const int32_t* __restrict__ tps,
+                                                   const int32_t* __restrict__ gps) {
     __shared__ uint32_t sh[8];
     const int b = blockIdx.y;
     const int Tthr = tps ? tps[b] : T0;
+    const int G = GATE ? gps[b] : PEE_GATE_OFF;
     const T* src = img + (size_t)b * H * W;
     const int wc = W / 2, nc = (H / 2) * wc;
     const int ntiles = (nc + PEE_TILE - 1) / PEE_TILE;
@@ -233,7 +268,8 @@ __global__ __launch_bounds__(256) void k_pee_count(const T* __restrict__ img, in
             if (k < nc) {
                 int x, a, bb, cc;
                 pee_load(src, W, wc, k, &x, &a, &bb, &cc);
-                const PeeCand pc = pee_classify(x, a, bb, cc, Tthr, maxval);
+                int te;
+                const PeeCand pc = pee_classify_g<GATE>(x, a, bb, cc, Tthr, maxval, G, &te);
                 cnt += (pc.expand && pc.safe) ? 1u : 0u;
             }
         }
@@ -243,19 +279,21 @@ __global__ __launch_bounds__(256) void k_pee_count(const T* __restrict__ img, in
 }
 
 // ---- per slice: exclusive tile offsets, capacity, tile holding bit L-1, exact `end`
-template <typename T>
+template <typename T, bool GATE = false>
 __global__ __launch_bounds__(256) void k_pee_locate(const T* __restrict__ img, int H, int W, int T0, int maxval,
                                                     const int32_t* __restrict__ lengths,
                                                     const uint32_t* __restrict__ tile_cnt_all,
                                                     uint32_t* __restrict__ tile_off_all, int ntiles_max,
                                                     codec_pee_meta* __restrict__ meta_all,
-                                                    const int32_t* __restrict__ tps) {
+                                                    const int32_t* __restrict__ tps,
+                                                    const int32_t* __restrict__ gps) {
     __shared__ uint32_t sh[8];
     __shared__ int s_tile;
     __shared__ uint32_t s_base;
     __shared__ int s_end;
     const int b = blockIdx.x;
     const int Tthr = tps ? tps[b] : T0;
+    const int G = GATE ? gps[b] : PEE_GATE_OFF;
     const int wc = W / 2, nc = (H / 2) * wc;
     const int ntiles = (nc + PEE_TILE - 1) / PEE_TILE;
     const uint32_t* cnt = tile_cnt_all + (size_t)b * ntiles_max;
@@ -285,7 +323,8 @@ __global__ __launch_bounds__(256) void k_pee_locate(const T* __restrict__ img, i
             if (k < nc) {
                 int x, a, bb, cc;
                 pee_load(src, W, wc, k, &x, &a, &bb, &cc);
-                const PeeCand pc = pee_classify(x, a, bb, cc, Tthr, maxval);
+                int te;
+                const PeeCand pc = pee_classify_g<GATE>(x, a, bb, cc, Tthr, maxval, G, &te);
                 if (pc.expand && pc.safe) { flags |= 1u << u; ++local; }
             }
         }
@@ -322,11 +361,14 @@ __global__ __launch_bounds__(256) void k_pee_locate(const T* __restrict__ img, i
         }
         M->lm_count = 0;
         M->flags = 0;
+        // reserved[1] = 0 says "ungated" to every reader: written here too (the record buffer
+        // is the caller's, not zeroed on this path)
+        M->reserved[0] = 0; M->reserved[1] = GATE ? G + 1 : 0; M->reserved[2] = 0;
     }
 }
 
 // ---- embed: prefix tiles only
-template <typename T, bool VEC>
+template <typename T, bool VEC, bool GATE = false>
 __global__ __launch_bounds__(256) void k_pee_embed(const T* __restrict__ cover, T* __restrict__ stego, int H, int W,
                                                    const u64* __restrict__ payload_all, int pw,
                                                    const uint32_t* __restrict__ tile_off_all, int ntiles_max,
@@ -337,6 +379,7 @@ __global__ __launch_bounds__(256) void k_pee_embed(const T* __restrict__ cover, 
     const int b = blockIdx.y;
     codec_pee_meta* M = meta_all + b;
     const int tile_end = M->tile_end, end = M->end, Tthr = M->T, maxval = M->maxval;
+    const int G = GATE ? pee_rec_gate(M) : PEE_GATE_OFF;   // k_pee_locate wrote it
     const int wc = W / 2;
     const size_t npx = (size_t)H * W;
     const T* src = cover + b * npx;
@@ -350,12 +393,13 @@ __global__ __launch_bounds__(256) void k_pee_embed(const T* __restrict__ cover, 
         Quad<T, VEC> q;
         q.load(src, W, wc, k0, end);
         PeeCand pc[4];
+        int te[4] = {Tthr, Tthr, Tthr, Tthr};   // each candidate's own threshold (pee_gate_t)
         uint32_t local = 0;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             pc[u].expand = pc[u].safe = pc[u].right = false;
             if (k0 + u <= end) {
-                pc[u] = pee_classify(q.x[u], q.a[u], q.b[u], q.c[u], Tthr, maxval);
+                pc[u] = pee_classify_g<GATE>(q.x[u], q.a[u], q.b[u], q.c[u], Tthr, maxval, G, &te[u]);
                 local += (pc[u].expand && pc[u].safe) ? 1u : 0u;
             }
         }
@@ -373,7 +417,8 @@ __global__ __launch_bounds__(256) void k_pee_embed(const T* __restrict__ cover, 
                 ++cur;
                 nv = pc[u].p + 2 * (pc[u].x - pc[u].p) + bit;
             } else {
-                nv = pc[u].right ? pc[u].x + Tthr : pc[u].x - Tthr;
+                const int ts = GATE ? te[u] : Tthr;   // ungated: the uniform threshold, as before
+                nv = pc[u].right ? pc[u].x + ts : pc[u].x - ts;
             }
             q.put(dst, W, wc, k, u, nv);
         }
@@ -563,7 +608,7 @@ __global__ __launch_bounds__(256) void k_pee_ehist(const T* __restrict__ img, in
 // workgroup-per-tile k_pee_dcount at 256 x 2048^2).  (A wave-per-tile embed measured
 // slower than k_pee_embed -- 0.109 vs 0.099 ms: its cursor needs a scan per item slot
 // followed by a dependent payload load -- and was dropped.)
-template <typename T>
+template <typename T, bool GATE = false>
 __global__ __launch_bounds__(256) void k_pee_dcount_w(const T* __restrict__ stego, int H, int W,
                                                       const codec_pee_meta* __restrict__ meta_all,
                                                       const u64* __restrict__ lm_all, int lmw,
@@ -573,6 +618,7 @@ __global__ __launch_bounds__(256) void k_pee_dcount_w(const T* __restrict__ steg
     const codec_pee_meta* M = meta_all + b;
     const int end = pee_clamp_end(M->end, (H / 2) * (W / 2)), tile_end = pee_clamp_tile_end(M->tile_end, end);
     const int Tthr = M->T;
+    const int G = GATE ? pee_rec_gate(M) : PEE_GATE_OFF;
     const T* src = stego + (size_t)b * H * W;
     const u64* lm = lm_all + (size_t)b * lmw;
     const int lane = threadIdx.x & 63;
@@ -601,9 +647,10 @@ __global__ __launch_bounds__(256) void k_pee_dcount_w(const T* __restrict__ steg
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 if (k0 + e > end || ((nib >> e) & 1u)) continue;
-                const int e2 = (int)get_px(v1[u], 2 * e + 1) -
-                               med3((int)get_px(v1[u], 2 * e), (int)get_px(v0[u], 2 * e + 1), (int)get_px(v0[u], 2 * e));
-                local += (e2 >= -2 * Tthr && e2 < 2 * Tthr) ? 1u : 0u;
+                const int na = (int)get_px(v1[u], 2 * e), nb = (int)get_px(v0[u], 2 * e + 1), nw = (int)get_px(v0[u], 2 * e);
+                const int e2 = (int)get_px(v1[u], 2 * e + 1) - med3(na, nb, nw);
+                const int te = pee_gate_t<GATE>(na, nb, nw, Tthr, G);
+                local += (e2 >= -2 * te && e2 < 2 * te) ? 1u : 0u;
             }
         }
 #pragma unroll
@@ -616,7 +663,7 @@ __global__ __launch_bounds__(256) void k_pee_dcount_w(const T* __restrict__ steg
 // instead of seven -- the bit cursor is a wave scan plus the (double-buffered) totals of
 // the tile's earlier waves, location-map words are OR-reduced over 16 lanes with shuffles
 // and stored directly, the unsafe count goes out with one atomic per wave at the end.
-template <typename T>
+template <typename T, bool GATE = false>
 __global__ __launch_bounds__(256) void k_pee_embed_v(const T* __restrict__ cover, T* __restrict__ stego, int H, int W,
                                                      const u64* __restrict__ payload_all, int pw,
                                                      const uint32_t* __restrict__ tile_off_all, int ntiles_max,
@@ -627,6 +674,7 @@ __global__ __launch_bounds__(256) void k_pee_embed_v(const T* __restrict__ cover
     const int b = blockIdx.y;
     codec_pee_meta* M = meta_all + b;
     const int tile_end = M->tile_end, end = M->end, Tthr = M->T, maxval = M->maxval;
+    const int G = GATE ? pee_rec_gate(M) : PEE_GATE_OFF;   // k_pee_locate wrote it
     const size_t npx = (size_t)H * W;
     const T* src = cover + b * npx;
     T* dst = stego + b * npx;
@@ -649,13 +697,14 @@ __global__ __launch_bounds__(256) void k_pee_embed_v(const T* __restrict__ cover
         }
         const uint32_t tbase = off[t];
         PeeCand pc[4];
+        int te[4] = {Tthr, Tthr, Tthr, Tthr};   // each candidate's own threshold (pee_gate_t)
         uint32_t local = 0;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             pc[u].expand = pc[u].safe = pc[u].right = false;
             if (ok && k0 + u <= end) {
-                pc[u] = pee_classify((int)get_px(v1, 2 * u + 1), (int)get_px(v1, 2 * u), (int)get_px(v0, 2 * u + 1),
-                                     (int)get_px(v0, 2 * u), Tthr, maxval);
+                pc[u] = pee_classify_g<GATE>((int)get_px(v1, 2 * u + 1), (int)get_px(v1, 2 * u), (int)get_px(v0, 2 * u + 1),
+                                             (int)get_px(v0, 2 * u), Tthr, maxval, G, &te[u]);
                 local += (pc[u].expand && pc[u].safe) ? 1u : 0u;
             }
         }
@@ -685,7 +734,8 @@ __global__ __launch_bounds__(256) void k_pee_embed_v(const T* __restrict__ cover
                 ++cur;
                 nv = pc[u].p + 2 * (pc[u].x - pc[u].p) + bit;
             } else {
-                nv = pc[u].right ? pc[u].x + Tthr : pc[u].x - Tthr;
+                const int ts = GATE ? te[u] : Tthr;   // ungated: the uniform threshold, as before
+                nv = pc[u].right ? pc[u].x + ts : pc[u].x - ts;
             }
             set_px(v1, 2 * u + 1, (uint32_t)nv);
             any = true;
@@ -730,7 +780,7 @@ __device__ __forceinline__ bool lm_bit(const u64* lm, int k, int lmw) {
     return (k >> 6) < lmw && ((lm[k >> 6] >> (k & 63)) & 1ull);
 }
 
-template <typename T, bool VEC>
+template <typename T, bool VEC, bool GATE = false>
 __global__ __launch_bounds__(256) void k_pee_dcount(const T* __restrict__ stego, int H, int W,
                                                     const codec_pee_meta* __restrict__ meta_all,
                                                     const u64* __restrict__ lm_all, int lmw,
@@ -741,6 +791,7 @@ __global__ __launch_bounds__(256) void k_pee_dcount(const T* __restrict__ stego,
     const int wc = W / 2;
     const int end = pee_clamp_end(M->end, (H / 2) * wc), tile_end = pee_clamp_tile_end(M->tile_end, end);
     const int Tthr = M->T;
+    const int G = GATE ? pee_rec_gate(M) : PEE_GATE_OFF;
     const T* src = stego + (size_t)b * H * W;
     const u64* lm = lm_all + (size_t)b * lmw;
     for (int t = blockIdx.x; t <= tile_end; t += gridDim.x) {
@@ -753,7 +804,8 @@ __global__ __launch_bounds__(256) void k_pee_dcount(const T* __restrict__ stego,
             const int k = k0 + u;
             if (k <= end && !lm_bit(lm, k, lmw)) {
                 const int e2 = q.x[u] - med3(q.a[u], q.b[u], q.c[u]);
-                local += (e2 >= -2 * Tthr && e2 < 2 * Tthr) ? 1u : 0u;
+                const int te = pee_gate_t<GATE>(q.a[u], q.b[u], q.c[u], Tthr, G);
+                local += (e2 >= -2 * te && e2 < 2 * te) ? 1u : 0u;
             }
         }
         const uint32_t tot = block_sum_u32<256>(local, sh);
@@ -782,7 +834,7 @@ __global__ __launch_bounds__(256) void k_pee_offsets(const codec_pee_meta* __res
     }
 }
 
-template <typename T, bool VEC>
+template <typename T, bool VEC, bool GATE = false>
 __global__ __launch_bounds__(256) void k_pee_recover(const T* __restrict__ stego, T* __restrict__ cover, int H, int W,
                                                      const codec_pee_meta* __restrict__ meta_all,
                                                      const u64* __restrict__ lm_all, int lmw,
@@ -794,6 +846,7 @@ __global__ __launch_bounds__(256) void k_pee_recover(const T* __restrict__ stego
     const int wc = W / 2;
     const int end = pee_clamp_end(M->end, (H / 2) * wc), tile_end = pee_clamp_tile_end(M->tile_end, end);
     const int Tthr = M->T;
+    const int G = GATE ? pee_rec_gate(M) : PEE_GATE_OFF;
     const uint32_t plim = pee_bit_limit(M->L, pw);   // bits of rank >= min(L, 64 pw) are dropped
     const size_t npx = (size_t)H * W;
     const T* src = stego + b * npx;
@@ -806,6 +859,7 @@ __global__ __launch_bounds__(256) void k_pee_recover(const T* __restrict__ stego
         Quad<T, VEC> q;
         q.load(src, W, wc, k0, end);
         int ps[4];
+        int te[4] = {Tthr, Tthr, Tthr, Tthr};   // each candidate's own threshold (pee_gate_t)
         bool act[4], inner[4];
         uint32_t local = 0;
 #pragma unroll
@@ -816,8 +870,9 @@ __global__ __launch_bounds__(256) void k_pee_recover(const T* __restrict__ stego
             ps[u] = 0;
             if (act[u]) {
                 ps[u] = med3(q.a[u], q.b[u], q.c[u]);
+                te[u] = pee_gate_t<GATE>(q.a[u], q.b[u], q.c[u], Tthr, G);
                 const int e2 = q.x[u] - ps[u];
-                inner[u] = e2 >= -2 * Tthr && e2 < 2 * Tthr;
+                inner[u] = e2 >= -2 * te[u] && e2 < 2 * te[u];
                 local += inner[u] ? 1u : 0u;
             }
         }
@@ -843,7 +898,8 @@ __global__ __launch_bounds__(256) void k_pee_recover(const T* __restrict__ stego
                 ++cur;
                 x = ps[u] + (e2 >> 1);
             } else {
-                x = e2 >= 2 * Tthr ? q.x[u] - Tthr : q.x[u] + Tthr;
+                const int ts = GATE ? te[u] : Tthr;   // ungated: the uniform threshold, as before
+                x = e2 >= 2 * ts ? q.x[u] - ts : q.x[u] + ts;
             }
             q.put(dst, W, wc, k0 + u, u, x);
             any = true;
@@ -857,7 +913,7 @@ __global__ __launch_bounds__(256) void k_pee_recover(const T* __restrict__ stego
 // batch in address order; a workgroup iteration covers 4 whole tiles (u-slot u = tile
 // base/256 + u), and slots whose tile lies in the slice's prefix (<= tile_end) recover
 // bits and pixels in registers with a block scan for the cursor.
-template <typename T, bool NT>
+template <typename T, bool NT, bool GATE = false>
 __global__ __launch_bounds__(256) void k_pee_restore_gs(const T* __restrict__ stego, T* __restrict__ cover, int H, int W,
                                                         uint32_t items_per_slice, uint32_t total_items,
                                                         const codec_pee_meta* __restrict__ meta_all,
@@ -893,10 +949,12 @@ __global__ __launch_bounds__(256) void k_pee_restore_gs(const T* __restrict__ st
             if ((int)t <= M->tile_end) {                                 // uniform per slot
                 // t < tiles_per_slice bounds every candidate index by nc whatever `end` says
                 const int end = M->end, Tthr = M->T;
+                const int G = GATE ? pee_rec_gate(M) : PEE_GATE_OFF;
                 const uint32_t plim = pee_bit_limit(M->L, pw);   // as k_pee_recover
                 const u64* lm = lm_all + (size_t)b * lmw;
                 const int k0 = (int)t * PEE_TILE + 4 * threadIdx.x;
                 int ps[4], xs[4];
+                int te[4] = {Tthr, Tthr, Tthr, Tthr};   // each candidate's own threshold (pee_gate_t)
                 bool act[4], inner[4];
                 uint32_t local = 0;
 #pragma unroll
@@ -907,9 +965,11 @@ __global__ __launch_bounds__(256) void k_pee_restore_gs(const T* __restrict__ st
                     inner[q] = false;
                     ps[q] = 0;
                     if (act[q]) {
-                        ps[q] = med3((int)get_px(a1[u], 2 * q), (int)get_px(a0[u], 2 * q + 1), (int)get_px(a0[u], 2 * q));
+                        const int na = (int)get_px(a1[u], 2 * q), nb = (int)get_px(a0[u], 2 * q + 1), nw = (int)get_px(a0[u], 2 * q);
+                        ps[q] = med3(na, nb, nw);
+                        te[q] = pee_gate_t<GATE>(na, nb, nw, Tthr, G);
                         const int e2 = xs[q] - ps[q];
-                        inner[q] = e2 >= -2 * Tthr && e2 < 2 * Tthr;
+                        inner[q] = e2 >= -2 * te[q] && e2 < 2 * te[q];
                         local += inner[q] ? 1u : 0u;
                     }
                 }
@@ -935,7 +995,8 @@ __global__ __launch_bounds__(256) void k_pee_restore_gs(const T* __restrict__ st
                         ++cur;
                         x = ps[q] + (e2 >> 1);
                     } else {
-                        x = e2 >= 2 * Tthr ? xs[q] - Tthr : xs[q] + Tthr;
+                        const int ts = GATE ? te[q] : Tthr;   // ungated: the uniform threshold, as before
+                        x = e2 >= 2 * ts ? xs[q] - ts : xs[q] + ts;
                     }
                     set_px(a1[u], 2 * q + 1, (uint32_t)x);
                 }
@@ -1000,13 +1061,14 @@ struct NoFallback {
 
 // expandable, non-overflow candidates of chunk j (the embed's aggregate), counted by the
 // calling wave (16 items per lane) and returned to every lane
-template <typename T>
+template <typename T, bool GATE = false>
 struct EmbedCount {
     static constexpr bool can = true;
     const T* src;
     int W, CR;
     uint32_t items;
     int Tthr, maxval;
+    int G = PEE_GATE_OFF;   // GATE: the slice's gate (inactive candidates count nowhere)
     __device__ u64 operator()(int j) const {   // expandable | unsafe << 32 (a status word's value)
         typedef typename Vec8<T>::type V;
         const int lane = threadIdx.x & 63;
@@ -1020,8 +1082,9 @@ struct EmbedCount {
             const V v1 = *reinterpret_cast<const V*>(src + o0 + W);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const PeeCand pc = pee_classify((int)get_px(v1, 2 * q + 1), (int)get_px(v1, 2 * q), (int)get_px(v0, 2 * q + 1),
-                                                (int)get_px(v0, 2 * q), Tthr, maxval);
+                int te;
+                const PeeCand pc = pee_classify_g<GATE>((int)get_px(v1, 2 * q + 1), (int)get_px(v1, 2 * q),
+                                                        (int)get_px(v0, 2 * q + 1), (int)get_px(v0, 2 * q), Tthr, maxval, G, &te);
                 n += (pc.expand && pc.safe) ? 1u : 0u;
                 un += pc.safe ? 0u : 1u;
             }
@@ -1037,7 +1100,7 @@ struct EmbedCount {
 
 // inner candidates of chunk j (the extract's aggregate): not in the location map, k <= end,
 // -2T <= e' < 2T -- counted from the stego by the calling wave
-template <typename T>
+template <typename T, bool GATE = false>
 struct ExtractCount {
     static constexpr bool can = true;
     const T* src;
@@ -1045,6 +1108,7 @@ struct ExtractCount {
     int W, CR;
     uint32_t items;
     int end, Tthr;
+    int G = PEE_GATE_OFF;   // GATE: the record's gate
     __device__ u64 operator()(int j) const {
         typedef typename Vec8<T>::type V;
         const int lane = threadIdx.x & 63;
@@ -1060,8 +1124,10 @@ struct ExtractCount {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 if ((int)(4 * it) + q > end || ((lw >> q) & 1ull)) continue;
-                const int e2 = (int)get_px(v1, 2 * q + 1) - med3((int)get_px(v1, 2 * q), (int)get_px(v0, 2 * q + 1), (int)get_px(v0, 2 * q));
-                n += (e2 >= -2 * Tthr && e2 < 2 * Tthr) ? 1u : 0u;
+                const int na = (int)get_px(v1, 2 * q), nb = (int)get_px(v0, 2 * q + 1), nw = (int)get_px(v0, 2 * q);
+                const int e2 = (int)get_px(v1, 2 * q + 1) - med3(na, nb, nw);
+                const int te = pee_gate_t<GATE>(na, nb, nw, Tthr, G);
+                n += (e2 >= -2 * te && e2 < 2 * te) ? 1u : 0u;
             }
         }
 #pragma unroll
@@ -1353,14 +1419,15 @@ __device__ __forceinline__ int pee_sc_tag(int epoch) { return epoch % 63 + 1; }
 #else
 #define PEE_X1_LB __launch_bounds__(256)
 #endif
-template <typename T, bool NT, bool INPLACE, bool SC = false>
+// GATE (codec_pee_gate_embed; never with SC): gps[b] is slice b's gate
+template <typename T, bool NT, bool INPLACE, bool SC = false, bool GATE = false>
 __global__ PEE_E1_LB void k_pee_embed1(const T* __restrict__ cover, T* stego, int H, int W, int T0,
                                                     int maxval, const int32_t* __restrict__ lengths,
                                                     const u64* __restrict__ payload_all, int pw, int nchunks, int B,
                                                     u64* status_all, uint32_t* ctl, codec_pee_meta* meta_all,
                                                     u64* __restrict__ lm_all, int lmw, int mode, uint32_t spin_max,
                                                     int dbg_skip, uint32_t* diag, const int32_t* __restrict__ tps,
-                                                    int sc_epoch, int dbg_stale) {
+                                                    int sc_epoch, int dbg_stale, const int32_t* __restrict__ gps) {
     typedef typename Vec8<T>::type V;
     __shared__ u64 sh64[8];
     __shared__ uint32_t sh[8];
@@ -1389,6 +1456,7 @@ __global__ PEE_E1_LB void k_pee_embed1(const T* __restrict__ cover, T* stego, in
         const size_t stride = (size_t)B * nchunks;   // one status-word buffer
         const uint32_t L = (uint32_t)max(0, lengths[b]);
         const int Tthr = tps ? tps[b] : T0;   // per-slice threshold (capacity control) or one for all
+        const int G = GATE ? gps[b] : PEE_GATE_OFF;
         codec_pee_meta* M = meta_all + b;
         const T* src = cover + b * npx;
         T* dst = stego + b * npx;
@@ -1485,8 +1553,10 @@ __global__ PEE_E1_LB void k_pee_embed1(const T* __restrict__ cover, T* stego, in
                 uint32_t n = 0;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const PeeCand pc = pee_classify((int)get_px(a1[u], 2 * q + 1), (int)get_px(a1[u], 2 * q),
-                                                    (int)get_px(a0[u], 2 * q + 1), (int)get_px(a0[u], 2 * q), Tthr, maxval);
+                    int te;
+                    const PeeCand pc = pee_classify_g<GATE>((int)get_px(a1[u], 2 * q + 1), (int)get_px(a1[u], 2 * q),
+                                                            (int)get_px(a0[u], 2 * q + 1), (int)get_px(a0[u], 2 * q), Tthr,
+                                                            maxval, G, &te);
                     const uint32_t bit = 1u << (4 * u + q);
                     if (pc.safe) safem |= bit;
                     if (pc.right) rightm |= bit;
@@ -1523,8 +1593,8 @@ __global__ PEE_E1_LB void k_pee_embed1(const T* __restrict__ cover, T* stego, in
                 bool to = false, fb = false;
                 LbSum ex;
                 if (INPLACE) ex = lb_exclusive(st, c, &to, &fb, spin_max, NoFallback(), fin_flag, L);
-                else ex = lb_exclusive<sc>(st, c, &to, &fb, spin_max, EmbedCount<T>{src, W, CR, items, Tthr, maxval}, fin_flag, L,
-                                           tag, fin_val);
+                else ex = lb_exclusive<sc>(st, c, &to, &fb, spin_max, EmbedCount<T, GATE>{src, W, CR, items, Tthr, maxval, G},
+                                           fin_flag, L, tag, fin_val);
                 if (tid == 0) {
                     if constexpr (sc) {
                         // inclusive prefix; past `end` saturated to L (successors only compare it with L)
@@ -1554,6 +1624,7 @@ __global__ PEE_E1_LB void k_pee_embed1(const T* __restrict__ cover, T* stego, in
                 M->T = Tthr; M->maxval = maxval; M->L = (int)L; M->nc = nc; M->ntiles = ntiles; M->h = H; M->w = W;
                 if (L == 0) { M->end = -1; M->tile_end = -1; }   // status: below (out of place) / memset (in place)
                 if (sc) M->reserved[0] = M->reserved[1] = M->reserved[2] = 0;
+                if constexpr (GATE) M->reserved[1] = G + 1;   // the rest of the record was zeroed before the pass
             }
             // the chunk holding `end` (or the last one on overflow) reports the capacity seen so
             // far: exact when it is the last chunk, else a lower bound (later chunks are not counted)
@@ -1625,9 +1696,11 @@ __global__ PEE_E1_LB void k_pee_embed1(const T* __restrict__ cover, T* stego, in
                     procm |= proc ? bit : 0u;
                     nib |= (proc & !(sb & bit)) ? bit : 0u;
                     const int x = (int)get_px(a1[u], 2 * q + 1);
-                    const int pr = med3((int)get_px(a1[u], 2 * q), (int)get_px(a0[u], 2 * q + 1), (int)get_px(a0[u], 2 * q));
+                    const int na = (int)get_px(a1[u], 2 * q), nb = (int)get_px(a0[u], 2 * q + 1), nw = (int)get_px(a0[u], 2 * q);
+                    const int pr = med3(na, nb, nw);
+                    const int te = pee_gate_t<GATE>(na, nb, nw, Tthr, G);   // 0: the shift of an inactive candidate
                     const int nv_e = 2 * x - pr + (int)((field >> pre) & 1ull);   // p + 2e + bit
-                    const int nv_s = (rb & bit) ? x + Tthr : x - Tthr;
+                    const int nv_s = (rb & bit) ? x + te : x - te;
                     const int nv = (proc & ((sb & bit) != 0u)) ? ((eb & bit) ? nv_e : nv_s) : x;
                     set_px(a1[u], 2 * q + 1, (uint32_t)nv);
                 }
@@ -1746,7 +1819,8 @@ struct PeeReadAhead {
 
 // extract: chunks up to the one holding `end` recover bits + pixels (look-back over the
 // inner-candidate counts); later chunks are a plain copy (out of place) or skipped.
-template <typename T, bool NT, bool INPLACE, bool SC = false>
+// GATE (codec_pee_gate_extract; never with SC): the gate is the record's (pee_rec_gate)
+template <typename T, bool NT, bool INPLACE, bool SC = false, bool GATE = false>
 __global__ PEE_X1_LB void k_pee_extract1(const T* stego, T* cover, int H, int W,
                                                       const codec_pee_meta* __restrict__ meta_all,
                                                       const u64* __restrict__ lm_all, int lmw, int nchunks, int B,
@@ -1762,6 +1836,7 @@ __global__ PEE_X1_LB void k_pee_extract1(const T* stego, T* cover, int H, int W,
     // the payload written without atomics or a zeroed buffer -- every word by the chunk holding
     // its first bit, which reads the word's later bits ahead from the following chunks' pixels
     constexpr bool sc = !INPLACE && SC;   // a separate instantiation: the read-ahead's registers
+    static_assert(!(GATE && SC), "the read-ahead (PeeReadAhead) is ungated: gated calls zero first");
     const size_t stride = (size_t)B * nchunks;
     // the chunk's recovered bits: ranks [excl, excl + agg), agg <= 4096, from word excl / 64
     __shared__ u64 pbuf[PEE_CHUNK * 4 / 64 + 2];
@@ -1791,6 +1866,7 @@ __global__ PEE_X1_LB void k_pee_extract1(const T* stego, T* cover, int H, int W,
         if (!valid) continue;
         const codec_pee_meta* M = meta_all + b;
         const int end = pee_clamp_end(M->end, (int)(4u * items)), Tthr = M->T;   // nc = 4 items (8 | W)
+        const int G = GATE ? pee_rec_gate(M) : PEE_GATE_OFF;
         const uint32_t plim = pee_bit_limit(M->L, pw);   // bits of rank >= min(L, 64 pw) are dropped
 #ifdef PEE_X_COPYONLY   // diagnostic build (tools): every chunk a plain copy
         const int cend = -1;
@@ -1868,9 +1944,11 @@ __global__ PEE_X1_LB void k_pee_extract1(const T* stego, T* cover, int H, int W,
                     const int k = (int)(4 * it) + q;
                     if (k > end || ((lw >> q) & 1ull)) continue;
                     actm |= 1u << (4 * u + q);
-                    const int p = med3((int)get_px(a1[u], 2 * q), (int)get_px(a0[u], 2 * q + 1), (int)get_px(a0[u], 2 * q));
+                    const int na = (int)get_px(a1[u], 2 * q), nb = (int)get_px(a0[u], 2 * q + 1), nw = (int)get_px(a0[u], 2 * q);
+                    const int p = med3(na, nb, nw);
+                    const int te = pee_gate_t<GATE>(na, nb, nw, Tthr, G);
                     const int e2 = (int)get_px(a1[u], 2 * q + 1) - p;
-                    if (e2 >= -2 * Tthr && e2 < 2 * Tthr) { innm |= 1u << (4 * u + q); ++n; }
+                    if (e2 >= -2 * te && e2 < 2 * te) { innm |= 1u << (4 * u + q); ++n; }
                 }
                 packed |= (u64)n << (16 * u);
             }
@@ -1888,7 +1966,7 @@ __global__ PEE_X1_LB void k_pee_extract1(const T* stego, T* cover, int H, int W,
                     bool to = false, fb = false;
                     LbSum ex;
                     if (INPLACE) ex = lb_exclusive(st, c, &to, &fb, spin_max, NoFallback());
-                    else ex = lb_exclusive(st, c, &to, &fb, spin_max, ExtractCount<T>{src, lm, W, CR, items, end, Tthr},
+                    else ex = lb_exclusive(st, c, &to, &fb, spin_max, ExtractCount<T, GATE>{src, lm, W, CR, items, end, Tthr, G},
                                            nullptr, 0u, sc ? tag : -1);
                     if (tid == 0) {
                         if (publish) lb_store(st + c, LB_INC | ((ex.e + agg) & 0xFFFFFFFFull) | tagw);
@@ -1915,11 +1993,13 @@ __global__ PEE_X1_LB void k_pee_extract1(const T* stego, T* cover, int H, int W,
                 for (int q = 0; q < 4; ++q) {
                     const uint32_t bit = 1u << q;
                     const int x = (int)get_px(a1[u], 2 * q + 1);
-                    const int p = med3((int)get_px(a1[u], 2 * q), (int)get_px(a0[u], 2 * q + 1), (int)get_px(a0[u], 2 * q));
+                    const int na = (int)get_px(a1[u], 2 * q), nb = (int)get_px(a0[u], 2 * q + 1), nw = (int)get_px(a0[u], 2 * q);
+                    const int p = med3(na, nb, nw);
+                    const int te = pee_gate_t<GATE>(na, nb, nw, Tthr, G);   // 0: an inactive candidate stays
                     const int e2 = x - p;
                     const bool inner = (im & bit) != 0u;
                     bits |= (inner ? (uint32_t)(e2 & 1) : 0u) << __popc(im & (bit - 1u));
-                    const int nx = inner ? p + (e2 >> 1) : (e2 >= 2 * Tthr ? x - Tthr : x + Tthr);
+                    const int nx = inner ? p + (e2 >> 1) : (e2 >= 2 * te ? x - te : x + te);
                     set_px(a1[u], 2 * q + 1, (uint32_t)((am & bit) ? nx : x));
                 }
                 if (bits) {
@@ -3405,13 +3485,38 @@ int codec_pee_embed(const codec_pee_params* P, const void* cover, void* stego, c
     return codec_pee_embed_ts(P, cover, stego, payload, lengths, nullptr, meta, lm, workspace, workspace_bytes, stream);
 }
 
+static int pee_embed_impl(const codec_pee_params* P, const void* cover, void* stego, const uint64_t* payload,
+                          const int32_t* lengths, const int32_t* tps, const int32_t* gps, codec_pee_meta* meta,
+                          uint64_t* lm, void* workspace, size_t workspace_bytes, void* stream);
+
 int codec_pee_embed_ts(const codec_pee_params* P, const void* cover, void* stego, const uint64_t* payload,
                        const int32_t* lengths, const int32_t* tps, codec_pee_meta* meta, uint64_t* lm, void* workspace,
                        size_t workspace_bytes, void* stream) {
+    return pee_embed_impl(P, cover, stego, payload, lengths, tps, nullptr, meta, lm, workspace, workspace_bytes, stream);
+}
+
+// include/codec_tcc_gate.h: the embed with a per-slice smoothness gate.  Same routes as the
+// ungated call but the slice-serial kernels (ungated only) and the self-cleaning mode of the
+// flat look-back (its extract reads ahead with ungated counts): a gated call zeroes its
+// status words first, as the in-place calls do, so the workspace rules are unchanged.
+int codec_pee_gate_embed(const codec_pee_params* P, const void* cover, void* stego, const uint64_t* payload,
+                         const int32_t* lengths, const int32_t* t_slices, const int32_t* g_slices, codec_pee_meta* meta,
+                         uint64_t* lm, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!t_slices || !g_slices) return set_err(CODEC_EINVAL, "codec_pee_gate_embed: NULL pointer argument");
+    return pee_embed_impl(P, cover, stego, payload, lengths, t_slices, g_slices, meta, lm, workspace, workspace_bytes, stream);
+}
+
+}  // extern "C"
+
+// gps: per-slice gates on the device (codec_pee_gate_embed), or NULL for the ungated call
+static int pee_embed_impl(const codec_pee_params* P, const void* cover, void* stego, const uint64_t* payload,
+                          const int32_t* lengths, const int32_t* tps, const int32_t* gps, codec_pee_meta* meta,
+                          uint64_t* lm, void* workspace, size_t workspace_bytes, void* stream) {
     int rc = pee_check(P);
     if (rc) return rc;
     if (!cover || !stego || !payload || !lengths || !meta || !lm || !workspace)
         return set_err(CODEC_EINVAL, "codec_pee_embed: NULL pointer argument");
+    const bool gate = gps != nullptr;
     const PeeWs L = pee_ws(P);
     if (workspace_bytes < L.total) return set_err(CODEC_EINVAL, "workspace too small");
     HIP_TRY(pee_ws_enter(workspace, P, L, as_stream(stream)));   // another shape's state: zeroed first
@@ -3450,7 +3555,7 @@ int codec_pee_embed_ts(const codec_pee_params* P, const void* cover, void* stego
     // look-back progressing, as in the lane order; 256 tickets on one line cost 8 us at B=1).
     const long long onepass = knob("CODEC_PEE_ONEPASS", -1);
     const bool flat = !inplace && P->B < 32 && P->B <= knob("CODEC_PEE_FLAT_MAXB", 7);
-    if (vec && items > 0 && onepass != 0 && pee_use_slice_serial(P, inplace)) {
+    if (!gate && vec && items > 0 && onepass != 0 && pee_use_slice_serial(P, inplace)) {
         // slice-serial single pass: one workgroup per slice, no look-back, no memsets
         ProfScope prof(st, CODEC_K_PEE_EMBED_SS);
         const bool pay_lds = P->payload_words <= SS_PAY_WORDS && knob("CODEC_PEE_SS_PAYLDS", 1) != 0;
@@ -3511,7 +3616,7 @@ int codec_pee_embed_ts(const codec_pee_params* P, const void* cover, void* stego
         // small out-of-place batches (flat slots, no ticket) clean up after themselves: no
         // zeroing launch (C2: one launch of ~2 us fewer per call); meta is written without
         // atomics out of place, so only in place (and the ticket modes) zero it
-        if (flat && (mode & PEE_MODE_NOTICKET) && knob("CODEC_PEE_SELFCLEAN", 1) && pee_sc_fits(P, st, workspace)) mode |= PEE_MODE_SC;
+        if (!gate && flat && (mode & PEE_MODE_NOTICKET) && knob("CODEC_PEE_SELFCLEAN", 1) && pee_sc_fits(P, st, workspace)) mode |= PEE_MODE_SC;
         if (!(mode & PEE_MODE_SC))
             HIP_TRY(pee_zero(st, stw, L.ctl - L.st + PEE_CTL_WORDS(P->B, L.nchunks) * 4, meta, (size_t)P->B * sizeof(codec_pee_meta),
                              inplace ? lm : nullptr, inplace ? (size_t)P->B * P->lm_words * 8 : 0));
@@ -3531,8 +3636,17 @@ int codec_pee_embed_ts(const codec_pee_params* P, const void* cover, void* stego
 #define PE1S(TT, NTV, IP, SCV) hipLaunchKernelGGL((k_pee_embed1<TT, NTV, IP, SCV>), dim3((unsigned)g), dim3(256), 0, st, \
             static_cast<const TT*>(cover), static_cast<TT*>(stego), P->H, P->W, P->T, P->maxval, lengths, \
             reinterpret_cast<const u64*>(payload), P->payload_words, L.nchunks, P->B, stw, ctl, meta, \
-            reinterpret_cast<u64*>(lm), P->lm_words, mode, spin_max, dbg_skip, diag, tps, sc_epoch, dbg_stale)
+            reinterpret_cast<u64*>(lm), P->lm_words, mode, spin_max, dbg_skip, diag, tps, sc_epoch, dbg_stale, gps)
 #define PE1(TT, NTV, IP) do { if (!(IP) && (mode & PEE_MODE_SC)) PE1S(TT, NTV, false, true); else PE1S(TT, NTV, IP, false); } while (0)
+        // gated: non-temporal accesses only (CODEC_NT is an A/B knob of the ungated kernels)
+#define PE1G(TT, IP) hipLaunchKernelGGL((k_pee_embed1<TT, true, IP, false, true>), dim3((unsigned)g), dim3(256), 0, st, \
+            static_cast<const TT*>(cover), static_cast<TT*>(stego), P->H, P->W, P->T, P->maxval, lengths, \
+            reinterpret_cast<const u64*>(payload), P->payload_words, L.nchunks, P->B, stw, ctl, meta, \
+            reinterpret_cast<u64*>(lm), P->lm_words, mode, spin_max, dbg_skip, diag, tps, sc_epoch, dbg_stale, gps)
+        if (gate) {
+            if (P->bytes == 2) { if (inplace) PE1G(uint16_t, true); else PE1G(uint16_t, false); }
+            else { if (inplace) PE1G(uint8_t, true); else PE1G(uint8_t, false); }
+        } else
         if (P->bytes == 2) {
             if (inplace) { if (nt) PE1(uint16_t, true, true); else PE1(uint16_t, false, true); }
             else { if (nt) PE1(uint16_t, true, false); else PE1(uint16_t, false, false); }
@@ -3542,6 +3656,7 @@ int codec_pee_embed_ts(const codec_pee_params* P, const void* cover, void* stego
         }
 #undef PE1
 #undef PE1S
+#undef PE1G
         LAUNCH_CHECK("k_pee_embed1");
         // odd H: the last row of each slice belongs to no row pair (no candidate, no MED
         // neighbour); out of place it is copied verbatim
@@ -3561,30 +3676,29 @@ int codec_pee_embed_ts(const codec_pee_params* P, const void* cover, void* stego
             long long gw = knob("CODEC_PEE_SCAN_GS_WGS", 32768);   // tools/tune_pee.py
             if (gw > (tot + 3) / 4) gw = (tot + 3) / 4;
             if (gw < 1) gw = 1;
-#define PSCAN(TT, NTV) hipLaunchKernelGGL((k_pee_scan<TT, NTV>), dim3((unsigned)gw), dim3(256), 0, st, static_cast<const TT*>(cover), static_cast<TT*>(stego), P->H, P->W, P->T, P->maxval, cnt, L.ntiles_max, P->B, tps)
-            if (P->bytes == 2) { if (nt) PSCAN(uint16_t, true); else PSCAN(uint16_t, false); }
-            else { if (nt) PSCAN(uint8_t, true); else PSCAN(uint8_t, false); }
+#define PSCAN(TT, NTV, GV) hipLaunchKernelGGL((k_pee_scan<TT, NTV, GV>), dim3((unsigned)gw), dim3(256), 0, st, static_cast<const TT*>(cover), static_cast<TT*>(stego), P->H, P->W, P->T, P->maxval, cnt, L.ntiles_max, P->B, tps, gps)
+            if (gate) { if (P->bytes == 2) PSCAN(uint16_t, true, true); else PSCAN(uint8_t, true, true); }
+            else if (P->bytes == 2) { if (nt) PSCAN(uint16_t, true, false); else PSCAN(uint16_t, false, false); }
+            else { if (nt) PSCAN(uint8_t, true, false); else PSCAN(uint8_t, false, false); }
 #undef PSCAN
             LAUNCH_CHECK("k_pee_scan");
         } else {
             if (!inplace) HIP_TRY(hipMemcpyAsync(stego, cover, (size_t)npx * P->B * P->bytes, hipMemcpyDeviceToDevice, st));
-            if (P->bytes == 2)
-                hipLaunchKernelGGL(k_pee_count<uint16_t>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(cover),
-                                   P->H, P->W, P->T, P->maxval, per, cnt, L.ntiles_max, tps);
-            else
-                hipLaunchKernelGGL(k_pee_count<uint8_t>, grid, dim3(256), 0, st, static_cast<const uint8_t*>(cover),
-                                   P->H, P->W, P->T, P->maxval, per, cnt, L.ntiles_max, tps);
+#define PCNT(TT, GV) hipLaunchKernelGGL((k_pee_count<TT, GV>), grid, dim3(256), 0, st, static_cast<const TT*>(cover), \
+                                        P->H, P->W, P->T, P->maxval, per, cnt, L.ntiles_max, tps, gps)
+            if (P->bytes == 2) { if (gate) PCNT(uint16_t, true); else PCNT(uint16_t, false); }
+            else { if (gate) PCNT(uint8_t, true); else PCNT(uint8_t, false); }
+#undef PCNT
             LAUNCH_CHECK("k_pee_count");
         }
     }
     {
         ProfScope prof(st, CODEC_K_PEE_LOCATE);
-        if (P->bytes == 2)
-            hipLaunchKernelGGL(k_pee_locate<uint16_t>, dim3(P->B), dim3(256), 0, st, static_cast<const uint16_t*>(cover),
-                               P->H, P->W, P->T, P->maxval, lengths, cnt, off, L.ntiles_max, meta, tps);
-        else
-            hipLaunchKernelGGL(k_pee_locate<uint8_t>, dim3(P->B), dim3(256), 0, st, static_cast<const uint8_t*>(cover),
-                               P->H, P->W, P->T, P->maxval, lengths, cnt, off, L.ntiles_max, meta, tps);
+#define PLOC(TT, GV) hipLaunchKernelGGL((k_pee_locate<TT, GV>), dim3(P->B), dim3(256), 0, st, static_cast<const TT*>(cover), \
+                                        P->H, P->W, P->T, P->maxval, lengths, cnt, off, L.ntiles_max, meta, tps, gps)
+        if (P->bytes == 2) { if (gate) PLOC(uint16_t, true); else PLOC(uint16_t, false); }
+        else { if (gate) PLOC(uint8_t, true); else PLOC(uint8_t, false); }
+#undef PLOC
         LAUNCH_CHECK("k_pee_locate");
     }
     {
@@ -3592,27 +3706,31 @@ int codec_pee_embed_ts(const codec_pee_params* P, const void* cover, void* stego
         const int g = (int)knob("CODEC_PEE_EMBED_WGS", 64);
         dim3 grid(g < L.ntiles_max ? g : L.ntiles_max, P->B);
         if (vec && knob("CODEC_PEE_EMBED_V", 1)) {
-            if (P->bytes == 2)
-                hipLaunchKernelGGL(k_pee_embed_v<uint16_t>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(cover),
-                                   static_cast<uint16_t*>(stego), P->H, P->W, reinterpret_cast<const u64*>(payload),
-                                   P->payload_words, off, L.ntiles_max, meta, reinterpret_cast<u64*>(lm), P->lm_words);
-            else
-                hipLaunchKernelGGL(k_pee_embed_v<uint8_t>, grid, dim3(256), 0, st, static_cast<const uint8_t*>(cover),
-                                   static_cast<uint8_t*>(stego), P->H, P->W, reinterpret_cast<const u64*>(payload),
-                                   P->payload_words, off, L.ntiles_max, meta, reinterpret_cast<u64*>(lm), P->lm_words);
+#define PEMV(TT, GV) hipLaunchKernelGGL((k_pee_embed_v<TT, GV>), grid, dim3(256), 0, st, static_cast<const TT*>(cover), \
+                                        static_cast<TT*>(stego), P->H, P->W, reinterpret_cast<const u64*>(payload), \
+                                        P->payload_words, off, L.ntiles_max, meta, reinterpret_cast<u64*>(lm), P->lm_words)
+            if (P->bytes == 2) { if (gate) PEMV(uint16_t, true); else PEMV(uint16_t, false); }
+            else { if (gate) PEMV(uint8_t, true); else PEMV(uint8_t, false); }
+#undef PEMV
             LAUNCH_CHECK("k_pee_embed_v");
             return 0;
         }
-#define PEMB(TT, VV) hipLaunchKernelGGL((k_pee_embed<TT, VV>), grid, dim3(256), 0, st, static_cast<const TT*>(cover), \
+#define PEMB(TT, VV, GV) hipLaunchKernelGGL((k_pee_embed<TT, VV, GV>), grid, dim3(256), 0, st, static_cast<const TT*>(cover), \
                                static_cast<TT*>(stego), P->H, P->W, reinterpret_cast<const u64*>(payload), \
                                P->payload_words, off, L.ntiles_max, meta, reinterpret_cast<u64*>(lm), P->lm_words)
-        if (P->bytes == 2) { if (vec) PEMB(uint16_t, true); else PEMB(uint16_t, false); }
-        else { if (vec) PEMB(uint8_t, true); else PEMB(uint8_t, false); }
+        if (gate) {
+            if (P->bytes == 2) { if (vec) PEMB(uint16_t, true, true); else PEMB(uint16_t, false, true); }
+            else { if (vec) PEMB(uint8_t, true, true); else PEMB(uint8_t, false, true); }
+        }
+        else if (P->bytes == 2) { if (vec) PEMB(uint16_t, true, false); else PEMB(uint16_t, false, false); }
+        else { if (vec) PEMB(uint8_t, true, false); else PEMB(uint8_t, false, false); }
 #undef PEMB
         LAUNCH_CHECK("k_pee_embed");
     }
     return 0;
 }
+
+extern "C" {
 
 int codec_pee_embed_auto(const codec_pee_params* P, const void* cover, void* stego, const uint64_t* payload,
                          const int32_t* lengths, int32_t tmax, int32_t* t_out, codec_pee_meta* meta, uint64_t* lm,
@@ -3700,8 +3818,13 @@ int codec_pee_embed_auto(const codec_pee_params* P, const void* cover, void* ste
     return 0;
 }
 
-int codec_pee_extract(const codec_pee_params* P, const void* stego, const codec_pee_meta* meta, const uint64_t* lm,
-                      void* cover_out, uint64_t* payload_out, void* workspace, size_t workspace_bytes, void* stream) {
+}  // extern "C"
+
+// gate: the kernels read each record's gate (reserved[1]; codec_pee_gate_extract) -- the same
+// routes as the ungated call but the slice-serial kernels and the self-cleaning look-back
+static int pee_extract_impl(const codec_pee_params* P, const void* stego, const codec_pee_meta* meta, const uint64_t* lm,
+                            void* cover_out, uint64_t* payload_out, void* workspace, size_t workspace_bytes, void* stream,
+                            bool gate) {
     int rc = pee_check(P);
     if (rc) return rc;
     if (!stego || !meta || !lm || !cover_out || !payload_out || !workspace)
@@ -3719,7 +3842,7 @@ int codec_pee_extract(const codec_pee_params* P, const void* stego, const codec_
     const long long items = (long long)(P->H / 2) * (P->W / 8);
     const bool inplace = stego == cover_out;
     const long long onepass = knob("CODEC_PEE_ONEPASS", -1);   // as in codec_pee_embed
-    if (vec && items > 0 && onepass != 0 && pee_use_slice_serial(P, inplace)) {
+    if (!gate && vec && items > 0 && onepass != 0 && pee_use_slice_serial(P, inplace)) {
         // slice-serial: writes every payload word itself (no memset) and never sets the flag
         uint32_t* ctl = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + L.ctl);
         ProfScope prof(st, CODEC_K_PEE_EXTRACT_SS);
@@ -3782,7 +3905,7 @@ int codec_pee_extract(const codec_pee_params* P, const void* stego, const codec_
                         : (knob("CODEC_PEE_X_CHUNK_MAJOR", knob("CODEC_PEE_1P_CHUNK_MAJOR", 1)) ? PEE_MODE_CMAJOR : 0) |
                               (knob("CODEC_PEE_X_NOTICKET", 1) ? PEE_MODE_NOTICKET : 0) |
                               ((int)(knob("CODEC_PEE_X_GROUP", 32) / 8) << 8);
-        if (flat && (mode & PEE_MODE_NOTICKET) && knob("CODEC_PEE_SELFCLEAN", 1) && pee_sc_fits(P, st, workspace)) mode |= PEE_MODE_SC;
+        if (!gate && flat && (mode & PEE_MODE_NOTICKET) && knob("CODEC_PEE_SELFCLEAN", 1) && pee_sc_fits(P, st, workspace)) mode |= PEE_MODE_SC;
         if (!(mode & PEE_MODE_SC))
             HIP_TRY(pee_zero(st, payload_out, (size_t)P->B * P->payload_words * 8, stw, L.ctl - L.st + PEE_CTL_WORDS(P->B, L.nchunks) * 4));
         bool sc_fresh = false;
@@ -3803,6 +3926,15 @@ int codec_pee_extract(const codec_pee_params* P, const void* stego, const codec_
             P->lm_words, L.nchunks, P->B, stw, ctl, reinterpret_cast<u64*>(payload_out), P->payload_words, mode, spin_max, \
             dbg_skip, diag, sc_epoch, dbg_stale)
 #define PX1(TT, NTV, IP) do { if (!(IP) && (mode & PEE_MODE_SC)) PX1S(TT, NTV, false, true); else PX1S(TT, NTV, IP, false); } while (0)
+        // gated: non-temporal accesses only, as the gated embed
+#define PX1G(TT, IP) hipLaunchKernelGGL((k_pee_extract1<TT, true, IP, false, true>), dim3((unsigned)g), dim3(256), 0, st, \
+            static_cast<const TT*>(stego), static_cast<TT*>(cover_out), P->H, P->W, meta, reinterpret_cast<const u64*>(lm), \
+            P->lm_words, L.nchunks, P->B, stw, ctl, reinterpret_cast<u64*>(payload_out), P->payload_words, mode, spin_max, \
+            dbg_skip, diag, sc_epoch, dbg_stale)
+        if (gate) {
+            if (P->bytes == 2) { if (inplace) PX1G(uint16_t, true); else PX1G(uint16_t, false); }
+            else { if (inplace) PX1G(uint8_t, true); else PX1G(uint8_t, false); }
+        } else
         if (P->bytes == 2) {
             if (inplace) { if (nt) PX1(uint16_t, true, true); else PX1(uint16_t, false, true); }
             else { if (nt) PX1(uint16_t, true, false); else PX1(uint16_t, false, false); }
@@ -3812,6 +3944,7 @@ int codec_pee_extract(const codec_pee_params* P, const void* stego, const codec_
         }
 #undef PX1
 #undef PX1S
+#undef PX1G
         LAUNCH_CHECK("k_pee_extract1");
         if ((P->H & 1) && !inplace) HIP_TRY(pee_copy_last_rows(P, stego, cover_out, st));
         return 0;
@@ -3831,14 +3964,16 @@ int codec_pee_extract(const codec_pee_params* P, const void* stego, const codec_
             if (knob("CODEC_PEE_WAVE_TILES", 1)) {
                 const int gw = (int)knob("CODEC_PEE_DCOUNT_W_WGS", 8);   // 4 waves (tiles) per workgroup
                 dim3 gridw(gw, P->B);
-#define PDCW(TT) hipLaunchKernelGGL((k_pee_dcount_w<TT>), gridw, dim3(256), 0, st, static_cast<const TT*>(stego), P->H, P->W, \
+#define PDCW(TT, GV) hipLaunchKernelGGL((k_pee_dcount_w<TT, GV>), gridw, dim3(256), 0, st, static_cast<const TT*>(stego), P->H, P->W, \
                                meta, reinterpret_cast<const u64*>(lm), P->lm_words, cnt, L.ntiles_max)
-                if (P->bytes == 2) PDCW(uint16_t); else PDCW(uint8_t);
+                if (P->bytes == 2) { if (gate) PDCW(uint16_t, true); else PDCW(uint16_t, false); }
+                else { if (gate) PDCW(uint8_t, true); else PDCW(uint8_t, false); }
 #undef PDCW
             } else {
-#define PDC2(TT) hipLaunchKernelGGL((k_pee_dcount<TT, true>), grid, dim3(256), 0, st, static_cast<const TT*>(stego), P->H, P->W, \
+#define PDC2(TT, GV) hipLaunchKernelGGL((k_pee_dcount<TT, true, GV>), grid, dim3(256), 0, st, static_cast<const TT*>(stego), P->H, P->W, \
                                meta, reinterpret_cast<const u64*>(lm), P->lm_words, cnt, L.ntiles_max)
-                if (P->bytes == 2) PDC2(uint16_t); else PDC2(uint8_t);
+                if (P->bytes == 2) { if (gate) PDC2(uint16_t, true); else PDC2(uint16_t, false); }
+                else { if (gate) PDC2(uint8_t, true); else PDC2(uint8_t, false); }
 #undef PDC2
             }
             LAUNCH_CHECK("k_pee_dcount");
@@ -3850,11 +3985,12 @@ int codec_pee_extract(const codec_pee_params* P, const void* stego, const codec_
         long long gg = (total + 1023) / 1024;
         const long long cap = knob("CODEC_PEE_RESTORE_WGS", 1 << 30);
         if (gg > cap) gg = cap;
-#define PRG(TT, NTV) hipLaunchKernelGGL((k_pee_restore_gs<TT, NTV>), dim3((unsigned)gg), dim3(256), 0, st, static_cast<const TT*>(stego), \
+#define PRG(TT, NTV, GV) hipLaunchKernelGGL((k_pee_restore_gs<TT, NTV, GV>), dim3((unsigned)gg), dim3(256), 0, st, static_cast<const TT*>(stego), \
                 static_cast<TT*>(cover_out), P->H, P->W, (uint32_t)items, total, meta, reinterpret_cast<const u64*>(lm), P->lm_words, \
                 off, L.ntiles_max, reinterpret_cast<u64*>(payload_out), P->payload_words)
-        if (P->bytes == 2) { if (nt) PRG(uint16_t, true); else PRG(uint16_t, false); }
-        else { if (nt) PRG(uint8_t, true); else PRG(uint8_t, false); }
+        if (gate) { if (P->bytes == 2) PRG(uint16_t, true, true); else PRG(uint8_t, true, true); }
+        else if (P->bytes == 2) { if (nt) PRG(uint16_t, true, false); else PRG(uint16_t, false, false); }
+        else { if (nt) PRG(uint8_t, true, false); else PRG(uint8_t, false, false); }
 #undef PRG
         LAUNCH_CHECK("k_pee_restore_gs");
         return 0;
@@ -3879,10 +4015,14 @@ int codec_pee_extract(const codec_pee_params* P, const void* stego, const codec_
     dim3 grid(g < L.ntiles_max ? g : L.ntiles_max, P->B);
     {
         ProfScope prof(st, CODEC_K_PEE_DCOUNT);
-#define PDC(TT, VV) hipLaunchKernelGGL((k_pee_dcount<TT, VV>), grid, dim3(256), 0, st, static_cast<const TT*>(stego), P->H, P->W, \
+#define PDC(TT, VV, GV) hipLaunchKernelGGL((k_pee_dcount<TT, VV, GV>), grid, dim3(256), 0, st, static_cast<const TT*>(stego), P->H, P->W, \
                                meta, reinterpret_cast<const u64*>(lm), P->lm_words, cnt, L.ntiles_max)
-        if (P->bytes == 2) { if (vec) PDC(uint16_t, true); else PDC(uint16_t, false); }
-        else { if (vec) PDC(uint8_t, true); else PDC(uint8_t, false); }
+        if (gate) {
+            if (P->bytes == 2) { if (vec) PDC(uint16_t, true, true); else PDC(uint16_t, false, true); }
+            else { if (vec) PDC(uint8_t, true, true); else PDC(uint8_t, false, true); }
+        }
+        else if (P->bytes == 2) { if (vec) PDC(uint16_t, true, false); else PDC(uint16_t, false, false); }
+        else { if (vec) PDC(uint8_t, true, false); else PDC(uint8_t, false, false); }
 #undef PDC
         LAUNCH_CHECK("k_pee_dcount");
         hipLaunchKernelGGL(k_pee_offsets, dim3(P->B), dim3(256), 0, st, meta, cnt, off, L.ntiles_max);
@@ -3890,15 +4030,33 @@ int codec_pee_extract(const codec_pee_params* P, const void* stego, const codec_
     }
     {
         ProfScope prof(st, CODEC_K_PEE_RECOVER);
-#define PREC(TT, VV) hipLaunchKernelGGL((k_pee_recover<TT, VV>), grid, dim3(256), 0, st, static_cast<const TT*>(stego), \
+#define PREC(TT, VV, GV) hipLaunchKernelGGL((k_pee_recover<TT, VV, GV>), grid, dim3(256), 0, st, static_cast<const TT*>(stego), \
                                static_cast<TT*>(cover_out), P->H, P->W, meta, reinterpret_cast<const u64*>(lm), \
                                P->lm_words, off, L.ntiles_max, reinterpret_cast<u64*>(payload_out), P->payload_words)
-        if (P->bytes == 2) { if (vec) PREC(uint16_t, true); else PREC(uint16_t, false); }
-        else { if (vec) PREC(uint8_t, true); else PREC(uint8_t, false); }
+        if (gate) {
+            if (P->bytes == 2) { if (vec) PREC(uint16_t, true, true); else PREC(uint16_t, false, true); }
+            else { if (vec) PREC(uint8_t, true, true); else PREC(uint8_t, false, true); }
+        }
+        else if (P->bytes == 2) { if (vec) PREC(uint16_t, true, false); else PREC(uint16_t, false, false); }
+        else { if (vec) PREC(uint8_t, true, false); else PREC(uint8_t, false, false); }
 #undef PREC
         LAUNCH_CHECK("k_pee_recover");
     }
     return 0;
+}
+
+extern "C" {
+
+int codec_pee_extract(const codec_pee_params* P, const void* stego, const codec_pee_meta* meta, const uint64_t* lm,
+                      void* cover_out, uint64_t* payload_out, void* workspace, size_t workspace_bytes, void* stream) {
+    return pee_extract_impl(P, stego, meta, lm, cover_out, payload_out, workspace, workspace_bytes, stream, false);
+}
+
+// include/codec_tcc_gate.h: T and the gate are each record's (reserved[1] = G + 1; a record
+// with reserved[1] = 0 decodes ungated, so this call reads every scheme-1 record)
+int codec_pee_gate_extract(const codec_pee_params* P, const void* stego, const codec_pee_meta* meta, const uint64_t* lm,
+                           void* cover_out, uint64_t* payload_out, void* workspace, size_t workspace_bytes, void* stream) {
+    return pee_extract_impl(P, stego, meta, lm, cover_out, payload_out, workspace, workspace_bytes, stream, true);
 }
 
 }  // extern "C"

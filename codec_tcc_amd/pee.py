@@ -40,10 +40,12 @@ def lattice_geometry(lattice: int, H: int, W: int):
     return y0, x0, max(0, (H - y0 + 1) // 2), max(0, (W - x0 + 1) // 2)
 
 
-def make_record(H: int, W: int, *, T: int, maxval: int, L: int, end: int, status: int, lattice: int = 0) -> _lib.PeeMeta:
+def make_record(H: int, W: int, *, T: int, maxval: int, L: int, end: int, status: int, lattice: int = 0,
+                gate: Optional[int] = None) -> _lib.PeeMeta:
     """The codec_pee_meta an embed of lattice `lattice` writes for this side information (what a
     file header or a side dict of oracle/pee_cpu.py carries); the geometry fields follow from H x W.  The
-    values are stored as given -- check_records() judges them."""
+    values are stored as given -- check_records() judges them.  gate: the smoothness gate G of a
+    gated scheme-1 embedding (reserved[1] = G + 1; include/codec_tcc_gate.h), None = ungated."""
     _y0, _x0, hc, wc = lattice_geometry(lattice, H, W)
     nc = hc * wc
     m = _lib.PeeMeta()
@@ -52,6 +54,8 @@ def make_record(H: int, W: int, *, T: int, maxval: int, L: int, end: int, status
     m.tile_end = int(end) // 1024 if int(end) >= 0 else -1
     m.status, m.capacity, m.h, m.w = int(status), int(L), int(H), int(W)
     m.reserved[0] = lattice
+    if gate is not None:
+        m.reserved[1] = int(gate) + 1
     return m
 
 
@@ -70,7 +74,9 @@ def check_records(records, H: int, W: int, *, scheme: int, payload_words: int, l
     The invariants are those of the records oracle/pee_cpu.py and tests/pee_scalar.py write
     (nc_p = the lattice's candidate count):
       1 <= T <= 64; 1 <= maxval <= the dtype's maximum (the library refuses maxval 0);
-      h, w, nc, ntiles = the geometry's; scheme 2: reserved[0] = the pass;
+      h, w, nc, ntiles = the geometry's; scheme 2: reserved[0] = the pass; scheme 1:
+        reserved[1] in 0..65536 (0 = ungated, else the smoothness gate G + 1; a gated record
+        obeys every rule below unchanged -- `end` indexes all candidates, active or not);
       status 0: L = 0 and end = -1, or 1 <= L <= end + 1 <= nc_p;
       status 1 (the pass filled up): end = nc_p - 1 and 0 <= L <= nc_p (L = 0 when the
         capacity is 0 and bits were left over);
@@ -121,6 +127,8 @@ def check_records(records, H: int, W: int, *, scheme: int, payload_words: int, l
                     bad(b, p, name, int(got), f"the geometry's is {want}")
             if scheme == 2 and int(r.reserved[0]) != p:
                 bad(b, p, "reserved[0]", int(r.reserved[0]), "the pass's lattice")
+            if scheme == 1 and not 0 <= int(r.reserved[1]) <= _lib.GATE_MAX + 1:
+                bad(b, p, "reserved[1]", int(r.reserved[1]), f"0 (ungated) or a gate + 1 in 1..{_lib.GATE_MAX + 1}")
             if status == 0:
                 if L == 0:
                     if end != -1:
@@ -208,6 +216,27 @@ def check_volume_args(shape, nbits: int, policy: str = "even", scheme: int = 1) 
         raise ValueError(f"a volume payload holds 0 .. 2^31 - 1 bits, got {int(nbits)}")
 
 
+def check_gate_args(gate, T, tmax: int, nc: int, scheme: int = 1) -> None:
+    """The argument rules of a smoothness gate (include/codec_tcc_gate.h), as ValueError before
+    any launch.  Pure host code: no GPU, no library load.  gate: None, 0..65535 or "auto"."""
+    if gate is None:
+        return
+    if int(scheme) != 1:
+        raise ValueError("the smoothness gate is scheme 1's: scheme 2's neighbours are modified by its earlier "
+                         "passes (DESIGN §3f)")
+    if isinstance(gate, str):
+        if gate != "auto":
+            raise ValueError("gate must be None, an integer in 0..65535 or 'auto'")
+    elif isinstance(gate, bool) or int(gate) != gate or not 0 <= int(gate) <= _lib.GATE_MAX:
+        raise ValueError(f"gate must be None, an integer in 0..{_lib.GATE_MAX} or 'auto', got {gate!r}")
+    if not 1 <= int(tmax) <= _lib.GATE_TMAX:
+        raise ValueError(f"a gated codec takes tmax in 1..{_lib.GATE_TMAX} (the selection's 64-bit products), got {tmax}")
+    if gate == "auto" and not isinstance(T, str) and not 1 <= int(T) <= int(tmax):
+        raise ValueError(f"gate='auto' with a fixed T takes T in 1..tmax = {int(tmax)}, got {T}")
+    if int(nc) > _lib.GATE_MAX_NC:
+        raise ValueError(f"{int(nc)} candidates per slice exceed the gated selection's 2^26")
+
+
 @dataclass
 class PeeVolume:
     """One bitstream embedded across a slice stack (PeeCodec.embed_volume).  enc is an ordinary
@@ -239,8 +268,18 @@ def _plan_dict(plan, info, B: int) -> dict:
 
 class PeeCodec:
     def __init__(self, batch: int, height: int, width: int, dtype="uint16", *, T=2, tmin: int = 1, tmax: int = 16,
-                 maxval: Optional[int] = None, device=None, scheme: int = 1):
-        """T: the expansion threshold for every slice, or "auto" -- capacity control: each
+                 maxval: Optional[int] = None, device=None, scheme: int = 1, gate=None):
+        """gate (scheme 1; include/codec_tcc_gate.h): None, a smoothness gate G in 0..65535, or
+        "auto".  A candidate whose MED neighbours W, N, NW span more than G (max - min) is left
+        alone: it is not shifted, flags nothing and carries nothing, and the decoder, reading the
+        same never-modified neighbours, skips it too -- the shifts of busy regions, most of the
+        distortion on real images, are gone at no cost in side information.  "auto" picks, per
+        slice on the device, the (T, G) of the 16-gate ladder with the least modelled distortion
+        per embedded bit among those that hold the payload (with an integer T: the best G for
+        that T); an integer gate with T="auto" picks the smallest T that holds the payload under
+        that gate.  meta.reserved[1] = G + 1 records the choice, g_slices holds it per slice
+        (t_slices the T).  Needs tmax <= 16 and at most 2^26 candidates per slice.
+        T: the expansion threshold for every slice, or "auto" -- capacity control: each
         slice gets the smallest T <= tmax whose capacity holds its payload (meta.T records
         the choice, t_slices holds it per slice).  Scheme 1 reads it off the cover's capacity
         curve (codec_pee_capacity, one extra read-only pass); scheme 2's capacity depends on
@@ -253,6 +292,8 @@ class PeeCodec:
         if scheme == 1 and int(tmin) != 1:
             raise ValueError("tmin is scheme 2's (scheme 1's capacity control starts at T = 1)")
         self.scheme = int(scheme)
+        check_gate_args(gate, T, tmax, (height // 2) * (width // 2), scheme)
+        self.gate = gate if gate is None or isinstance(gate, str) else int(gate)
         _require_gpu()
         torch = _torch()
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -278,14 +319,27 @@ class PeeCodec:
                            dtype="uint16" if nbytes == 2 else "uint8", scheme=self.scheme)
         if self.scheme == 2:
             self.config["tmin"] = self.tmin
+        if self.gate is not None:
+            self.config["gate"] = self.gate
         P = self._params(1)
-        ws = _lib.load().codec_pee_workspace_bytes(C.byref(P))
+        # a gated codec's workspace is the codec_pee one with the capacity table's bins behind
+        # it (every codec_pee call accepts it)
+        if self.gate is not None:
+            ws = _lib.load().codec_pee_gate_workspace_bytes(C.byref(P), self.tmax)
+        else:
+            ws = _lib.load().codec_pee_workspace_bytes(C.byref(P))
         if ws == 0:
             _lib.check(-1, "codec_pee_workspace_bytes")
         # zeroed by the reset below (codec_pee_reset: the whole workspace, the cumulative
         # look-back diagnostics included -- codec_pee_diag_offset)
         self.workspace = torch.empty(int(ws), dtype=torch.uint8, device=self.device)
-        self.t_slices = torch.empty(self.B, dtype=torch.int32, device=self.device) if self.auto else None
+        self.t_slices = torch.empty(self.B, dtype=torch.int32, device=self.device) \
+            if self.auto or self.gate is not None else None
+        self.g_slices = torch.empty(self.B, dtype=torch.int32, device=self.device) if self.gate is not None else None
+        if self.gate is not None and not self.auto:
+            self.t_slices.fill_(self.T)
+        if isinstance(self.gate, int):
+            self.g_slices.fill_(self.gate)
         # register the fresh workspace with the library: an allocation at an address
         # an earlier workspace used would otherwise inherit that one's call-to-call state record
         self.reset()
@@ -322,12 +376,51 @@ class PeeCodec:
         return (torch.from_numpy(packed).to(self.device), lengths,
                 torch.tensor(lengths, dtype=torch.int32, device=self.device))
 
-    def capacity(self, covers, tmax: Optional[int] = None):
+    def _table_workspace(self, tmax: int):
+        """The workspace of a codec_pee_gate_capacity call: the codec's own when it is a gated
+        one's, else a table-only one kept beside it (the call uses the tail alone)."""
+        torch = _torch()
+        need = int(_lib.load().codec_pee_gate_workspace_bytes(C.byref(self._params(1)), int(tmax)))
+        if need == 0:
+            _lib.check(-1, "codec_pee_gate_workspace_bytes")
+        if self.workspace.numel() >= need:
+            return self.workspace
+        ws = self.__dict__.get("_gate_ws")
+        if ws is None or ws.numel() < need:
+            ws = self._gate_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return ws
+
+    def gate_table(self, covers, tmax: Optional[int] = None, gate: Optional[int] = None):
+        """(n, hs): the gated capacity table of every slice as int32 device tensors [B, 16] and
+        [B, tmax, 16] (include/codec_tcc_gate.h): n[b, j] = candidates of roughness class j
+        (first j with D <= _lib.GATES[j]), hs[b, u, j] = those whose expansion is safe and whose
+        folded error is u.  hs.cumsum(1).cumsum(2)[b, T - 1, j] is the capacity at
+        (T, GATES[j]).  gate: the two-class table of one gate instead (class 0 = D <= gate)."""
+        torch = _torch()
+        if self.scheme != 1:
+            raise ValueError("the smoothness gate is scheme 1's")
+        tmax = self.tmax if tmax is None else int(tmax)
+        check_gate_args(0 if gate is None else gate, 1, tmax, self.nc)
+        if tuple(covers.shape) != (self.B, self.H, self.W) or _elem_bytes(covers) != self.bytes:
+            raise ValueError("covers do not match the codec's shape/dtype")
+        n = torch.empty((self.B, 16), dtype=torch.int32, device=self.device)
+        hs = torch.empty((self.B, tmax, 16), dtype=torch.int32, device=self.device)
+        ws = self._table_workspace(tmax)
+        _lib.check(_lib.load().codec_pee_gate_capacity(
+            C.byref(self._params(1)), covers.data_ptr(), tmax, 0, -1 if gate is None else int(gate), None, n.data_ptr(),
+            hs.data_ptr(), None, None, None, ws.data_ptr(), ws.numel(), _stream()), "codec_pee_gate_capacity")
+        return n, hs
+
+    def capacity(self, covers, tmax: Optional[int] = None, gate: Optional[int] = None):
         """int32 [B, tmax] device tensor: exact capacity of each slice at T = 1..tmax.
         Bounded by the candidate lattice: at most (H // 2) * (W // 2) bits per slice -- a
-        quarter of the pixels; the other three quarters are the MED context, never modified."""
+        quarter of the pixels; the other three quarters are the MED context, never modified.
+        gate: the capacities under that smoothness gate (active candidates only)."""
         torch = _torch()
         tmax = self.tmax if tmax is None else int(tmax)
+        if gate is not None:
+            _n, hs = self.gate_table(covers, tmax, gate)
+            return hs[:, :, 0].cumsum(1).to(torch.int32)
         caps = torch.empty((self.B, tmax), dtype=torch.int32, device=self.device)
         self._guarded(lambda: _lib.check(_lib.load().codec_pee_capacity(
             C.byref(self._params(1)), covers.data_ptr(), tmax, None, caps.data_ptr(), None, self.workspace.data_ptr(),
@@ -377,7 +470,20 @@ class PeeCodec:
         lib = _lib.load()
 
         def launch():
-            if self.auto:   # capacity control: per-slice T on the device (fused into the embed
+            if self.gate is not None and (self.auto or self.gate == "auto"):
+                # the gated table, the (T, G) selection and the embed queued on this stream
+                tmax = self.tmax if self.auto else self.T
+                _lib.check(lib.codec_pee_gate_embed_auto(
+                    C.byref(P), covers.data_ptr(), stego.data_ptr(), words.data_ptr(), lens_t.data_ptr(), tmax,
+                    0 if self.auto else self.T, -1 if self.gate == "auto" else self.gate, self.t_slices.data_ptr(),
+                    self.g_slices.data_ptr(), meta.data_ptr(), lm.data_ptr(), self.workspace.data_ptr(),
+                    self.workspace.numel(), _stream()), "codec_pee_gate_embed_auto")
+            elif self.gate is not None:   # T and G given: t_slices / g_slices were filled at construction
+                _lib.check(lib.codec_pee_gate_embed(
+                    C.byref(P), covers.data_ptr(), stego.data_ptr(), words.data_ptr(), lens_t.data_ptr(),
+                    self.t_slices.data_ptr(), self.g_slices.data_ptr(), meta.data_ptr(), lm.data_ptr(),
+                    self.workspace.data_ptr(), self.workspace.numel(), _stream()), "codec_pee_gate_embed")
+            elif self.auto:   # capacity control: per-slice T on the device (fused into the embed
                 # launch where it runs slice-serial, else one read-only capacity pass first)
                 _lib.check(lib.codec_pee_embed_auto(C.byref(P), covers.data_ptr(), stego.data_ptr(), words.data_ptr(),
                                                     lens_t.data_ptr(), self.tmax, self.t_slices.data_ptr(),
@@ -432,7 +538,10 @@ class PeeCodec:
             _raise_lookback(recs)
         return enc
 
-    def extract(self, stego, meta, lm, *, payload_words: int, cover=None, payload=None):
+    def extract(self, stego, meta, lm, *, payload_words: int, cover=None, payload=None, gated: Optional[bool] = None):
+        """gated: decode through codec_pee_gate_extract, which takes each record's gate
+        (reserved[1]; it reads ungated records too).  None: this codec's own setting; decode()
+        passes what the records say."""
         torch = _torch()
         if cover is None:
             cover = torch.empty_like(stego)
@@ -441,9 +550,12 @@ class PeeCodec:
         if self.scheme == 2:
             return self._extract_multi(stego, meta, lm, payload_words, cover, payload)
         P = self._params(payload_words)
-        self._guarded(lambda: _lib.check(_lib.load().codec_pee_extract(
+        gated = self.gate is not None if gated is None else bool(gated)
+        fn, what = (_lib.load().codec_pee_gate_extract, "codec_pee_gate_extract") if gated else \
+            (_lib.load().codec_pee_extract, "codec_pee_extract")
+        self._guarded(lambda: _lib.check(fn(
             C.byref(P), stego.data_ptr(), meta.data_ptr(), lm.data_ptr(), cover.data_ptr(), payload.data_ptr(),
-            self.workspace.data_ptr(), self.workspace.numel(), _stream()), "codec_pee_extract"))
+            self.workspace.data_ptr(), self.workspace.numel(), _stream()), what))
         return payload, cover
 
     def _extract_multi(self, stego, meta, lm, payload_words, cover, payload):
@@ -475,7 +587,8 @@ class PeeCodec:
         return d["embed_fallback_chunks"] + d["extract_fallback_chunks"]
 
     def _t_text(self) -> str:
-        return f"T={'auto, tmax=%d' % self.tmax if self.auto else self.T}"
+        gate = "" if self.gate is None else f", gate={self.gate}"
+        return f"T={'auto, tmax=%d' % self.tmax if self.auto else self.T}{gate}"
 
     def _check(self, enc: PeeEncoded, recs, lengths=None):
         """check_records() on records already read back (decode: no extra sync)."""
@@ -537,7 +650,9 @@ class PeeCodec:
         _raise_lookback(recs)
         _raise_status(recs, self._t_text())
         self._check(enc, recs)
-        words, cover = self.extract(enc.stego, enc.meta, enc.lm, payload_words=enc.payload_words)
+        # the gate is the records': a gated embedding decodes on any scheme-1 codec of the shape
+        words, cover = self.extract(enc.stego, enc.meta, enc.lm, payload_words=enc.payload_words,
+                                    gated=any(int(r.reserved[1]) != 0 for r in recs))
         self._cover_crc = _ck.crc32_slices(cover) if crc else None
         host = self._payload_rows = words.cpu().numpy()
         if self.lookback_failed(enc.payload_words):
@@ -600,6 +715,9 @@ class PeeCodec:
         packed: pack_volume()'s result instead of `payload` (no upload in the call; the payload
         CRC is then absent, as with embed's packed=)."""
         torch = _torch()
+        if self.gate is not None:
+            raise ValueError("volume payloads are ungated: planning a gated volume needs a plan over (T, G) "
+                             "(DESIGN §3f); use a codec without gate=")
         if tuple(covers.shape) != (self.B, self.H, self.W) or _elem_bytes(covers) != self.bytes:
             raise ValueError("covers do not match the codec's shape/dtype")
         bits = framing.to_bits(payload) if packed is None else None
@@ -742,14 +860,15 @@ def clear_codec_cache():
     _CODECS.clear()
 
 
-def _codec_for(shape, dtype: str, *, T, tmax: int, maxval: Optional[int], scheme: int = 1, tmin: int = 1) -> PeeCodec:
+def _codec_for(shape, dtype: str, *, T, tmax: int, maxval: Optional[int], scheme: int = 1, tmin: int = 1,
+               gate=None) -> PeeCodec:
     torch = _torch()
     if maxval is None:
         maxval = 65535 if "16" in dtype else 255
-    key = (tuple(shape), dtype, T, int(tmin), int(tmax), int(maxval), int(scheme), torch.cuda.current_device())
+    key = (tuple(shape), dtype, T, int(tmin), int(tmax), int(maxval), int(scheme), torch.cuda.current_device(), gate)
     c = _CODECS.get(key)
     if c is None:
-        c = PeeCodec(*shape, dtype=dtype, T=T, tmin=tmin, tmax=tmax, maxval=maxval, scheme=scheme)
+        c = PeeCodec(*shape, dtype=dtype, T=T, tmin=tmin, tmax=tmax, maxval=maxval, scheme=scheme, gate=gate)
         _CODECS[key] = c
         while len(_CODECS) > _CODECS_MAX:
             _CODECS.popitem(last=False)
@@ -788,25 +907,32 @@ def _config_from_records(enc: "PeeEncoded") -> dict:
     ts = {int(r.T) for r in recs}
     T = ts.pop() if len(ts) == 1 else "auto"
     tmax = max(16, max(int(r.T) for r in recs))
-    return dict(method="pee", T=T, tmax=min(tmax, 64), maxval=maxvals.pop(), dtype=dt)
+    cfg = dict(method="pee", T=T, tmax=min(tmax, 64), maxval=maxvals.pop(), dtype=dt)
+    gs = {int(r.reserved[1]) - 1 for r in recs if int(r.reserved[1]) != 0}
+    if gs:   # informational: decode() takes each slice's gate from its record
+        cfg["gate"] = gs.pop() if len(gs) == 1 else "auto"
+    return cfg
 
 
 def encode(covers, payloads: Sequence, *, T=2, tmax: int = 16, maxval: Optional[int] = None,
-           scheme: int = 1, tmin: int = 1, checksum: bool = False) -> PeeEncoded:
+           scheme: int = 1, tmin: int = 1, checksum: bool = False, gate=None) -> PeeEncoded:
     """MED-PEE embed of one payload per slice (the package's `encode(..., method="pee")`).
     covers: [B,H,W] / [H,W] uint8/uint16 torch tensor or numpy array; T: expansion threshold
     or "auto" (smallest T <= tmax whose capacity holds each slice's payload); maxval: the
     largest legal pixel value (e.g. 4095 for 12-bit DICOM; default the dtype's maximum);
     scheme 2: four sublattice passes; its T="auto" tries T = tmin .. tmax per slice in one launch.
     checksum=True: the encoding carries the covers' and payloads' CRC-32 and decode() verifies them.
+    gate (scheme 1): a smoothness gate 0..65535 or "auto" (PeeCodec); decode() reads it from the records.
     Raises ValueError when a payload exceeds its slice's capacity."""
     from .codec import _as_batch
+    shape = tuple(covers.shape)
+    check_gate_args(gate, T, tmax, (int(shape[-2]) // 2) * (int(shape[-1]) // 2) if len(shape) >= 2 else 0, scheme)
     _require_gpu()
     covers = _as_batch(covers)
     if isinstance(payloads, (str, bytes, bytearray)):
         payloads = [payloads]
     dt = "uint16" if _elem_bytes(covers) == 2 else "uint8"
-    codec = _codec_for(tuple(covers.shape), dt, T=T, tmax=tmax, maxval=maxval, scheme=scheme, tmin=tmin)
+    codec = _codec_for(tuple(covers.shape), dt, T=T, tmax=tmax, maxval=maxval, scheme=scheme, tmin=tmin, gate=gate)
     enc = codec.embed(covers, payloads, checksum=checksum)
     if scheme == 2:
         short = [i for i, (g, n) in enumerate(zip(enc.embedded(), enc.lengths)) if g < n]

@@ -139,7 +139,7 @@ def decode_bin_exact(filepath: str, search_block_size: Optional[int] = None) -> 
 
 # ------------------------------------------------------------------ MED-PEE files
 def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxval: Optional[int] = None,
-                    codec: str = "raw", scheme: int = 1, tmin: int = 1, checksum: bool = False) -> Dict:
+                    codec: str = "raw", scheme: int = 1, tmin: int = 1, checksum: bool = False, gate=None) -> Dict:
     """MED-PEE embed of one slice into a version-16 STGC file.  `image` is an array or a
     DICOM path; maxval defaults to the DICOM's full scale 2**BitsStored - 1 (4095 for the
     reference's 12-bit pe.dcm), else the dtype maximum.  T = 'auto' picks the smallest
@@ -149,9 +149,15 @@ def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxva
     four passes hold the payload, which the header and the returned 'T' then carry.
     checksum=True: the header ends with the checksum extension (container.pee_crc_extension:
     CRC-32 of the cover, from the GPU pass queued before the embed, and of the embedded
-    payload bits), which decode_bin_pee verifies; without it the file's bytes are unchanged."""
+    payload bits), which decode_bin_pee verifies; without it the file's bytes are unchanged.
+    gate (scheme 1): a smoothness gate 0..65535 or 'auto' (PeeCodec): the file then carries scheme
+    byte 3 and the chosen gate after scheme 1's fixed header fields ('gate' in the result);
+    without it the file's bytes are unchanged."""
     from . import checksum as _ck
-    from .pee import PeeCodec, lm_bits
+    from .pee import PeeCodec, check_gate_args, lm_bits
+    if gate is not None:
+        shape = getattr(image, "shape", (0, 0))
+        check_gate_args(gate, T, tmax, (int(shape[-2]) // 2) * (int(shape[-1]) // 2) if len(shape) >= 2 else 0, scheme)
     _require_gpu()
     torch = _torch()
     if isinstance(image, np.ndarray):
@@ -164,7 +170,7 @@ def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxva
         raise ValueError("A imagem deve ser 2D uint8 ou uint16.")
     h, w = img.shape
     bits = framing.to_bits(payload)
-    pc = PeeCodec(1, h, w, dtype=str(img.dtype), T=T, tmin=tmin, tmax=tmax, maxval=maxval, scheme=scheme)
+    pc = PeeCodec(1, h, w, dtype=str(img.dtype), T=T, tmin=tmin, tmax=tmax, maxval=maxval, scheme=scheme, gate=gate)
     enc = pc.embed(torch.from_numpy(np.ascontiguousarray(img)[None]).cuda(), [bits], checksum=checksum)
 
     def ext(embedded: int) -> Tuple[bytes, Dict]:
@@ -190,12 +196,18 @@ def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxva
     embedded = min(len(bits), r.capacity) if r.status == 1 else len(bits)
     lmb = container.lm_blob(lm_bits(enc, 0)) if r.end >= 0 else b""
     stego = enc.stego.cpu().numpy()[0]
-    hdr = container.create_pee_header(codec, img.dtype.itemsize, w, h, r.T, embedded, r.end, r.maxval, r.status,
-                                      len(lmb))
+    gated = {}
+    if gate is None:
+        hdr = container.create_pee_header(codec, img.dtype.itemsize, w, h, r.T, embedded, r.end, r.maxval, r.status,
+                                          len(lmb))
+    else:   # the gate the record carries (gate='auto': the slice's chosen one)
+        gated = {"gate": int(r.reserved[1]) - 1, "scheme": container.PEE_SCHEME_GATE}
+        hdr = container.create_pee_gate_header(codec, img.dtype.itemsize, w, h, r.T, embedded, r.end, r.maxval,
+                                               r.status, len(lmb), gated["gate"])
     xb, crcs = ext(embedded)
     size = container.create_binary_file(out_path, hdr + xb, _compress(stego, codec), lmb)
     return {"path": out_path, "bytes": size, "T": r.T, "L": embedded, "end": r.end, "maxval": r.maxval,
-            "status": r.status, "lm_count": r.lm_count, "stego": stego, **crcs}
+            "status": r.status, "lm_count": r.lm_count, "stego": stego, **gated, **crcs}
 
 
 @dataclass
@@ -218,9 +230,14 @@ def read_pee_bytes(raw: bytes) -> PeeFile:
     records), before anything reaches a kernel."""
     from .pee import check_records, make_record
     scheme = container.pee_scheme(raw)
+    gate = None
     if scheme == 2:
         md, blobs, data = container.parse_pee2_bytes(raw)
         passes = md["passes"]
+    elif scheme == container.PEE_SCHEME_GATE:   # scheme 1 with a smoothness gate: one gated record
+        md, blob, data = container.parse_pee_gate_bytes(raw)
+        blobs, passes = [blob], [{"L": md["L"], "end": md["end"], "status": md["status"]}]
+        scheme, gate = 1, md["gate"]
     else:
         md, blob, data = container.parse_pee_bytes(raw)
         blobs, passes = [blob], [{"L": md["L"], "end": md["end"], "status": md["status"]}]
@@ -233,7 +250,7 @@ def read_pee_bytes(raw: bytes) -> PeeFile:
     lm_words = max(1, ((h // 2) * (w // 2) + 63) // 64)
     pw = max(1, (md["L"] + 63) // 64)
     records = [[make_record(h, w, T=md["T"], maxval=md["maxval"], L=ps["L"], end=ps["end"], status=ps["status"],
-                            lattice=p)] for p, ps in enumerate(passes)]
+                            lattice=p, gate=gate)] for p, ps in enumerate(passes)]
     check_records(records, h, w, scheme=scheme, payload_words=pw, lm_words=lm_words, bytes=md["bytes"],
                   lengths=[md["L"]] if scheme == 2 else None)
     if md["status"] not in (0, 1) or any(ps["status"] not in (0, 1) for ps in passes):
@@ -269,7 +286,7 @@ def decode_bin_pee(filepath: str, verify=True) -> Tuple[np.ndarray, np.ndarray]:
     if pf.scheme == 1:
         meta_t, lm_t = meta_t[0], lm_t[0]
     words, cover = pc.extract(torch.from_numpy(np.ascontiguousarray(pf.stego)[None]).cuda(), meta_t, lm_t,
-                              payload_words=pf.payload_words)
+                              payload_words=pf.payload_words, **({"gated": True} if "gate" in md else {}))
     crc = _ck.crc32_slices(cover) if (mode and have) else None
     bits = framing.unpack_bits(words.cpu().numpy()[0], md["L"])
     if crc is not None:
