@@ -17,6 +17,7 @@
 
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 
 #define PEE_TILE 1024
@@ -476,7 +477,7 @@ __device__ __forceinline__ void ehist_add4(uint32_t* cnt, int lane_ix, const int
         const int p = med3(a[q], bb[q], cc[q]), e = x[q] - p;
         const int uq = e >= 0 ? e : -e - 1;
         u[q] = uq;
-        c[q] = (q < nq) & (uq < tmax) & (p + 2 * e >= 0) & (p + 2 * e + 1 <= maxval) ? 1u : 0u;
+        c[q] = ((q < nq) & (uq < tmax) & (p + 2 * e >= 0) & (p + 2 * e + 1 <= maxval)) ? 1u : 0u;
     }
 #pragma unroll
     for (int q = 1; q < 4; ++q)
@@ -3231,6 +3232,14 @@ static PeeWs pee_ws(const codec_pee_params* P) {
     return L;
 }
 
+// the batch gives every CU a slice (one workgroup per slice: the slice-serial kernels of both
+// schemes), with the last round of workgroups nearly full
+static bool pee_fills_chip(int B) {
+    const long long ncu = device_cu_count();
+    if (B < ncu) return false;
+    const long long rounds = (B + ncu - 1) / ncu;
+    return (double)B / (double)(rounds * ncu) >= 0.85;
+}
 
 // Measured at B = 256 (profiles/r02/ss_vs_lookback.json): in place the slice-serial pass
 // wins at every size (2048^2 embed 0.145 -> 0.111 ms, extract 0.115 -> 0.109); out of place
@@ -3241,10 +3250,7 @@ static bool pee_use_slice_serial(const codec_pee_params* P, bool inplace) {
     const long long k = knob("CODEC_PEE_SS", -1);
     if (k == 0) return false;
     if (k == 1) return true;
-    const long long ncu = device_cu_count();
-    if (P->B < ncu) return false;
-    const long long rounds = (P->B + ncu - 1) / ncu;
-    if ((double)P->B / (double)(rounds * ncu) < 0.85) return false;   // the last round nearly full
+    if (!pee_fills_chip(P->B)) return false;
     if (inplace) return true;
     const long long items = (long long)(P->H / 2) * (P->W / 8);
     return (items + SS_THREADS - 1) / SS_THREADS <= knob("CODEC_PEE_SS_OOP_MAXCH", 64);
@@ -3393,6 +3399,124 @@ static hipError_t pee_copy_last_rows(const codec_pee_params* P, const void* src,
                             (size_t)P->B, hipMemcpyDeviceToDevice, st);
 }
 
+static int pee_multi_check(const codec_pee_params* P, int pass) {
+    int rc = pee_check(P);
+    if (rc) return rc;
+    if (pass < 0 || pass > 3) return set_err(CODEC_EINVAL, "pass must be in 0..3");
+    if ((long long)P->B * P->H * P->W * P->bytes > (1LL << 40)) return set_err(CODEC_EINVAL, "batch too large");
+    return 0;
+}
+
+// ---- launch dispatch.  Every launch route below writes its kernel argument list once, in a
+// lambda `go(kern)`; the template arguments are chosen around it.  pee_pixel hands the pixel
+// type of P->bytes to a generic lambda (`[&](auto px) { using TT = decltype(px); ... }`) and
+// pee_flag up to three run-time flags as std::bool_constant values (`ip()` is a constant
+// expression).  The kernels instantiated are exactly those named in a go(...): a route that
+// exists for uint16_t only sits under `if constexpr (std::is_same_v<TT, uint16_t>)`.
+template <class F> static inline auto pee_pixel(int bytes, F&& f) { return bytes == 2 ? f(uint16_t{}) : f(uint8_t{}); }
+template <class F> static inline void pee_flag(bool a, F&& f) {
+    if (a) f(std::true_type{}); else f(std::false_type{});
+}
+template <class F> static inline void pee_flag(bool a, bool b, F&& f) {
+    pee_flag(a, [&](auto A) { pee_flag(b, [&](auto B) { f(A, B); }); });
+}
+template <class F> static inline void pee_flag(bool a, bool b, bool c, F&& f) {
+    pee_flag(a, b, [&](auto A, auto B) { pee_flag(c, [&](auto C) { f(A, B, C); }); });
+}
+template <int N> using pee_int = std::integral_constant<int, N>;
+
+// ---- the entry sequence of the workspace-taking calls, in the order their errors are
+// reported: the params (`checked` = what pee_check / pee_multi_check returned: the call site
+// names the check), the pointers (`who` names the entry point), the call's own argument checks
+// (`more`), the workspace size; then, with PEE_ENTER, the registry (another shape's state:
+// zeroed first).  PEE_NO_ENTER: a callee enters it, or the call keeps no state in the workspace
+struct PeeCall {
+    PeeWs L;
+    hipStream_t st;
+};
+enum PeeEnter { PEE_NO_ENTER, PEE_ENTER };
+static int pee_no_more() { return 0; }
+template <class More>
+static int pee_begin(PeeCall* C, const codec_pee_params* P, int checked, bool any_null, const char* who, More more,
+                     void* workspace, size_t workspace_bytes, void* stream, PeeEnter enter) {
+    int rc = checked;
+    if (rc) return rc;
+    if (any_null) return set_err(CODEC_EINVAL, "%s: NULL pointer argument", who);
+    if ((rc = more())) return rc;
+    C->L = pee_ws(P);
+    if (workspace_bytes < C->L.total) return set_err(CODEC_EINVAL, "workspace too small");
+    C->st = as_stream(stream);
+    if (enter == PEE_ENTER) HIP_TRY(pee_ws_enter(workspace, P, C->L, C->st));
+    return 0;
+}
+
+// ---- what the scheme-1 routes are chosen by.  vec: the 8-pixel vector kernels apply (W % 8
+// == 0 and both images aligned to `align` bytes; 0: one 8-pixel vector of P->bytes, 16 or 8);
+// items: 8-pixel row-pair chunks per slice; onepass: CODEC_PEE_ONEPASS (0 forces the two-pass
+// path); flat: B <= CODEC_PEE_FLAT_MAXB (7) out of place, see pee_embed_t
+struct PeeRoute {
+    bool vec, inplace, flat;
+    long long items, onepass;
+};
+static PeeRoute pee_route(const codec_pee_params* P, const void* src, const void* dst, size_t align = 0) {
+    if (!align) align = P->bytes == 2 ? 16 : 8;
+    PeeRoute R;
+    R.vec = (P->W % 8) == 0 && ((uintptr_t)src % align) == 0 && ((uintptr_t)dst % align) == 0;
+    R.inplace = src == dst;
+    R.items = (long long)(P->H / 2) * (P->W / 8);
+    R.onepass = knob("CODEC_PEE_ONEPASS", -1);
+    R.flat = !R.inplace && P->B < 32 && P->B <= knob("CODEC_PEE_FLAT_MAXB", 7);
+    return R;
+}
+static bool pee_lookback_fits(const PeeRoute& R, const PeeWs& L, int B) {
+    return R.vec && R.items > 0 && (long long)L.nchunks * B < 0x7FFFFFFFLL && R.onepass != 0;
+}
+
+// ---- launch set-up of the look-back pass (k_pee_embed1 / k_pee_extract1): the mode word, the
+// self-cleaning decision and its epoch, the zeroing, the grid and the debug knobs.  The embed
+// and the extract differ in their order knobs (k_cmajor falls back to the embed's
+// CODEC_PEE_1P_CHUNK_MAJOR) and in what is zeroed with the status words when the call does not
+// clean up after itself (z1, z2: 8-byte-aligned spans, bytes).
+struct PeeLb {
+    u64* stw;
+    uint32_t *ctl, *diag;
+    int mode, sc_epoch, dbg_skip, dbg_stale;
+    long long g;
+    uint32_t spin_max;
+    bool sc() const { return (mode & PEE_MODE_SC) != 0; }
+};
+static int pee_lookback_setup(PeeLb* S, const codec_pee_params* P, const PeeCall& C, const PeeRoute& R, bool gate,
+                              void* workspace, const char* k_cmajor, const char* k_noticket, const char* k_group,
+                              void* z1, size_t z1bytes, void* z2, size_t z2bytes) {
+    const PeeWs& L = C.L;
+    S->stw = reinterpret_cast<u64*>(static_cast<char*>(workspace) + L.st);
+    S->ctl = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + L.ctl);
+    S->diag = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + L.diag);
+    const size_t state = L.ctl - L.st + PEE_CTL_WORDS(P->B, L.nchunks) * 4;   // status words + ctl
+    int mode = R.flat ? PEE_MODE_FLAT | (knob("CODEC_PEE_FLAT_TICKET", 0) ? 0 : PEE_MODE_NOTICKET)
+                      : (knob(k_cmajor, knob("CODEC_PEE_1P_CHUNK_MAJOR", 1)) ? PEE_MODE_CMAJOR : 0) |
+                            (knob(k_noticket, 1) ? PEE_MODE_NOTICKET : 0) | ((int)(knob(k_group, 32) / 8) << 8);
+    // small out-of-place batches (flat slots, no ticket) clean up after themselves: no
+    // zeroing launch (C2: one launch of ~2 us fewer per call); meta is written without
+    // atomics out of place, so only in place (and the ticket modes) zero it
+    if (!gate && R.flat && (mode & PEE_MODE_NOTICKET) && knob("CODEC_PEE_SELFCLEAN", 1) && pee_sc_fits(P, C.st, workspace))
+        mode |= PEE_MODE_SC;
+    S->mode = mode;
+    if (!S->sc()) HIP_TRY(pee_zero(C.st, S->stw, state, z1, z1bytes, z2, z2bytes));
+    bool sc_fresh = false;
+    S->sc_epoch = S->sc() ? pee_ws_epoch(workspace, &sc_fresh) : 0;
+    if (sc_fresh)   // a pointer never seen: start its self-cleaning state clean
+        HIP_TRY(pee_zero(C.st, S->stw, state));
+    const long long total = pee_total_slots(P->B, L.nchunks, pee_group8(P->B, mode, R.inplace));
+    long long g = knob(R.inplace ? "CODEC_PEE_IP_WGS" : "CODEC_PEE_1P_WGS", R.inplace ? 2048 : (1 << 30));
+    if (g > total) g = total;
+    S->g = (g + 7) / 8 * 8;   // keep every workgroup on one slot lane (pee_slot)
+    S->spin_max = (uint32_t)debug_knob("CODEC_PEE_LB_SPINS", R.inplace ? (1 << 22) : (1 << 14));
+    S->dbg_skip = (int)debug_knob("CODEC_PEE_DEBUG_SKIP", 0) - 1;
+    S->dbg_stale = (int)debug_knob("CODEC_PEE_DEBUG_STALE", 0) - 1;
+    return 0;
+}
+
 extern "C" {
 
 size_t codec_pee_workspace_bytes(const codec_pee_params* P) {
@@ -3425,15 +3549,15 @@ int codec_debug_ss_trace(unsigned long long* out, int n) {   // diagnostic build
 
 int codec_pee_capacity(const codec_pee_params* P, const void* cover, int32_t tmax, const int32_t* lengths,
                        int32_t* caps, int32_t* t_out, void* workspace, size_t workspace_bytes, void* stream) {
-    int rc = pee_check(P);
+    PeeCall C;
+    int rc = pee_begin(&C, P, pee_check(P), !cover || !workspace, "codec_pee_capacity", [&] {
+        if (tmax < 1 || tmax > PEE_TMAX_MAX) return set_err(CODEC_EINVAL, "tmax must be in 1..64");
+        if (t_out && !lengths) return set_err(CODEC_EINVAL, "codec_pee_capacity: t_out needs lengths");
+        return 0;
+    }, workspace, workspace_bytes, stream, PEE_ENTER);
     if (rc) return rc;
-    if (!cover || !workspace) return set_err(CODEC_EINVAL, "codec_pee_capacity: NULL pointer argument");
-    if (tmax < 1 || tmax > PEE_TMAX_MAX) return set_err(CODEC_EINVAL, "tmax must be in 1..64");
-    if (t_out && !lengths) return set_err(CODEC_EINVAL, "codec_pee_capacity: t_out needs lengths");
-    const PeeWs L = pee_ws(P);
-    if (workspace_bytes < L.total) return set_err(CODEC_EINVAL, "workspace too small");
-    HIP_TRY(pee_ws_enter(workspace, P, L, as_stream(stream)));   // another shape's state: zeroed first
-    hipStream_t st = as_stream(stream);
+    const PeeWs& L = C.L;
+    hipStream_t st = C.st;
     uint32_t* hist = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + L.hist);
     // no memset: bins and arrival counters are zero on entry (zeroed workspace; each slice's
     // last workgroup clears them)
@@ -3447,11 +3571,13 @@ int codec_pee_capacity(const codec_pee_params* P, const void* cover, int32_t tma
         dim3 grid((unsigned)max(1LL, (units + per - 1) / per), (unsigned)P->B);
         const size_t lds = (size_t)tmax * 256 * 4;   // lane-private counters
         uint32_t* arrivals = hist + (size_t)P->B * PEE_TMAX_MAX;
-#define PEH(TT, VV) hipLaunchKernelGGL((k_pee_ehist<TT, VV>), grid, dim3(256), lds, st, static_cast<const TT*>(cover), P->H, \
-                                       P->W, P->maxval, (int)tmax, (int)per, hist, arrivals, lengths, caps, t_out, dbg_delay)
-        if (P->bytes == 2) { if (vec) PEH(uint16_t, true); else PEH(uint16_t, false); }
-        else { if (vec) PEH(uint8_t, true); else PEH(uint8_t, false); }
-#undef PEH
+        pee_pixel(P->bytes, [&](auto px) {
+            using TT = decltype(px);
+            pee_flag(vec, [&](auto v) {
+                hipLaunchKernelGGL((k_pee_ehist<TT, v()>), grid, dim3(256), lds, st, static_cast<const TT*>(cover), P->H,
+                                   P->W, P->maxval, (int)tmax, (int)per, hist, arrivals, lengths, caps, t_out, dbg_delay);
+            });
+        });
         LAUNCH_CHECK("k_pee_ehist");
     }
     return 0;
@@ -3508,27 +3634,20 @@ int codec_pee_gate_embed(const codec_pee_params* P, const void* cover, void* ste
 
 }  // extern "C"
 
-// gps: per-slice gates on the device (codec_pee_gate_embed), or NULL for the ungated call
-static int pee_embed_impl(const codec_pee_params* P, const void* cover, void* stego, const uint64_t* payload,
-                          const int32_t* lengths, const int32_t* tps, const int32_t* gps, codec_pee_meta* meta,
-                          uint64_t* lm, void* workspace, size_t workspace_bytes, void* stream) {
-    int rc = pee_check(P);
-    if (rc) return rc;
-    if (!cover || !stego || !payload || !lengths || !meta || !lm || !workspace)
-        return set_err(CODEC_EINVAL, "codec_pee_embed: NULL pointer argument");
+// the embed's routes for one pixel type; gps: per-slice gates on the device
+// (codec_pee_gate_embed), or NULL for the ungated call
+template <typename TT>
+static int pee_embed_t(const codec_pee_params* P, const PeeCall& C, const TT* cover, TT* stego, const u64* payload,
+                       const int32_t* lengths, const int32_t* tps, const int32_t* gps, codec_pee_meta* meta, u64* lm,
+                       void* workspace) {
+    constexpr bool U16 = std::is_same_v<TT, uint16_t>;
     const bool gate = gps != nullptr;
-    const PeeWs L = pee_ws(P);
-    if (workspace_bytes < L.total) return set_err(CODEC_EINVAL, "workspace too small");
-    HIP_TRY(pee_ws_enter(workspace, P, L, as_stream(stream)));   // another shape's state: zeroed first
-    hipStream_t st = as_stream(stream);
+    const PeeWs& L = C.L;
+    hipStream_t st = C.st;
     uint32_t* cnt = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + L.cnt);
     uint32_t* off = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + L.off);
     const long long npx = (long long)P->H * P->W;
-    const size_t va = P->bytes == 2 ? 16 : 8;
-    const bool vec = (P->W % 8) == 0 && ((uintptr_t)cover % va) == 0 && ((uintptr_t)stego % va) == 0;
     const bool nt = knob("CODEC_NT", 1) != 0;
-    const bool inplace = cover == stego;
-    const long long items = (long long)(P->H / 2) * (P->W / 8);
     // single pass (default wherever W % 8 == 0 and the buffers are 16-B aligned): in place it
     // stops reading after `end`; out of place large batches walk chunk-major slot order (all
     // slices' chunk 0 first, then chunk 1 ...: every slice's look-back chain advances one hop
@@ -3553,17 +3672,12 @@ static int pee_embed_impl(const codec_pee_params* P, const void* cover, void* st
     // a lone slice's chunks would otherwise all sit on one XCD); no ticket by default (the
     // predecessors of a chunk have lower slot numbers, so in-order dispatch per XCD keeps the
     // look-back progressing, as in the lane order; 256 tickets on one line cost 8 us at B=1).
-    const long long onepass = knob("CODEC_PEE_ONEPASS", -1);
-    const bool flat = !inplace && P->B < 32 && P->B <= knob("CODEC_PEE_FLAT_MAXB", 7);
-    if (!gate && vec && items > 0 && onepass != 0 && pee_use_slice_serial(P, inplace)) {
+    const PeeRoute R = pee_route(P, cover, stego);
+    const bool vec = R.vec, inplace = R.inplace;
+    if (!gate && vec && R.items > 0 && R.onepass != 0 && pee_use_slice_serial(P, inplace)) {
         // slice-serial single pass: one workgroup per slice, no look-back, no memsets
         ProfScope prof(st, CODEC_K_PEE_EMBED_SS);
         const bool pay_lds = P->payload_words <= SS_PAY_WORDS && knob("CODEC_PEE_SS_PAYLDS", 1) != 0;
-#define PES1(TT, NTV, IP, PL) hipLaunchKernelGGL((k_pee_embed_ss<TT, NTV, IP, 4, PL>), dim3((unsigned)P->B), dim3(SS_THREADS), 0, st, \
-            static_cast<const TT*>(cover), static_cast<TT*>(stego), P->H, P->W, P->T, P->maxval, lengths, tps, \
-            reinterpret_cast<const u64*>(payload), P->payload_words, meta, reinterpret_cast<u64*>(lm), P->lm_words, \
-            static_cast<char*>(workspace) + L.sink, 0, nullptr)
-#define PES(TT, NTV, IP) do { if (pay_lds) PES1(TT, NTV, IP, true); else PES1(TT, NTV, IP, false); } while (0)
         // ring depth of the in-place embed: it does not know `end` in advance, so the D - 1
         // chunks it has in flight past it are wasted reads; at 256 x 2048^2 the steady state
         // is HBM-bound (~5 TB/s of reads + writes), and D = 2 keeps enough in flight:
@@ -3571,92 +3685,48 @@ static int pee_embed_impl(const codec_pee_params* P, const void* cover, void* st
         // next chunk's loads go out before this chunk's barrier and compute): 0.0746 -> 0.0726
         // ms (profiles/r04/ip_early_ab.log).  CODEC_PEE_SS_D=2 / 4 restore the late refill.
         const long long ss_d = pay_lds ? knob("CODEC_PEE_SS_D", 1) : 4;
-#define PES1D(TT, NTV, IP, DD) hipLaunchKernelGGL((k_pee_embed_ss<TT, NTV, IP, DD, true>), dim3((unsigned)P->B), dim3(SS_THREADS), 0, st, \
-            static_cast<const TT*>(cover), static_cast<TT*>(stego), P->H, P->W, P->T, P->maxval, lengths, tps, \
-            reinterpret_cast<const u64*>(payload), P->payload_words, meta, reinterpret_cast<u64*>(lm), P->lm_words, \
-            static_cast<char*>(workspace) + L.sink, 0, nullptr)
         // in place, early ring of one: the load and store cache policies (CODEC_PEE_IP_NTL /
         // CODEC_PEE_IP_NTS; default non-temporal loads, plain stores, profiles/r05/ab_policy.txt)
         const bool ip_ntl = knob("CODEC_PEE_IP_NTL", 1) != 0, ip_nts = knob("CODEC_PEE_IP_NTS", 0) != 0;
-#define PES1P(NTL, NTSV) hipLaunchKernelGGL((k_pee_embed_ss<uint16_t, NTL, true, 1, true, false, NTSV>), dim3((unsigned)P->B), \
-            dim3(SS_THREADS), 0, st, static_cast<const uint16_t*>(cover), static_cast<uint16_t*>(stego), P->H, P->W, P->T, \
-            P->maxval, lengths, tps, reinterpret_cast<const u64*>(payload), P->payload_words, meta, reinterpret_cast<u64*>(lm), \
-            P->lm_words, static_cast<char*>(workspace) + L.sink, 0, nullptr)
-        if (P->bytes == 2) {
-            if (inplace) {
-                if (ss_d == 2 && nt) PES1D(uint16_t, true, true, 2);
-                else if (ss_d == 1 && nt) {
-                    if (ip_ntl && ip_nts) PES1P(true, true);
-                    else if (ip_ntl) PES1P(true, false);
-                    else if (ip_nts) PES1P(false, true);
-                    else PES1P(false, false);
-                }
-                else if (nt) PES(uint16_t, true, true); else PES(uint16_t, false, true);
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3((unsigned)P->B), dim3(SS_THREADS), 0, st, cover, stego, P->H, P->W, P->T,
+                               P->maxval, lengths, tps, payload, P->payload_words, meta, lm, P->lm_words,
+                               static_cast<char*>(workspace) + L.sink, 0, nullptr);
+        };
+        bool ring4 = true;   // the ring of 4 (late refill), every pixel type and placement
+        if constexpr (U16) {   // the in-place rings of 2 and of 1: uint16_t, non-temporal, payload in LDS
+            if (inplace && nt && ss_d == 2) {
+                go(k_pee_embed_ss<TT, true, true, 2, true>);
+                ring4 = false;
+            } else if (inplace && nt && ss_d == 1) {
+                pee_flag(ip_ntl, ip_nts,
+                         [&](auto ntl, auto nts) { go(k_pee_embed_ss<TT, ntl(), true, 1, true, false, nts()>); });
+                ring4 = false;
             }
-            else { if (nt) PES(uint16_t, true, false); else PES(uint16_t, false, false); }
-        } else {
-            if (inplace) { if (nt) PES(uint8_t, true, true); else PES(uint8_t, false, true); }
-            else { if (nt) PES(uint8_t, true, false); else PES(uint8_t, false, false); }
         }
-#undef PES
-#undef PES1
-#undef PES1D
-#undef PES1P
+        if (ring4)
+            pee_flag(nt, inplace, pay_lds, [&](auto n, auto ip, auto pl) { go(k_pee_embed_ss<TT, n(), ip(), 4, pl()>); });
         LAUNCH_CHECK("k_pee_embed_ss");
         if ((P->H & 1) && !inplace) HIP_TRY(pee_copy_last_rows(P, cover, stego, st));
         return 0;
     }
-    if (vec && items > 0 && (long long)L.nchunks * P->B < 0x7FFFFFFFLL && onepass != 0) {
-        u64* stw = reinterpret_cast<u64*>(static_cast<char*>(workspace) + L.st);
-        uint32_t* ctl = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + L.ctl);
-        int mode = flat ? PEE_MODE_FLAT | (knob("CODEC_PEE_FLAT_TICKET", 0) ? 0 : PEE_MODE_NOTICKET)
-                        : (knob("CODEC_PEE_1P_CHUNK_MAJOR", 1) ? PEE_MODE_CMAJOR : 0) |
-                              (knob("CODEC_PEE_1P_NOTICKET", 1) ? PEE_MODE_NOTICKET : 0) |
-                              ((int)(knob("CODEC_PEE_1P_GROUP", 32) / 8) << 8);
-        // small out-of-place batches (flat slots, no ticket) clean up after themselves: no
-        // zeroing launch (C2: one launch of ~2 us fewer per call); meta is written without
-        // atomics out of place, so only in place (and the ticket modes) zero it
-        if (!gate && flat && (mode & PEE_MODE_NOTICKET) && knob("CODEC_PEE_SELFCLEAN", 1) && pee_sc_fits(P, st, workspace)) mode |= PEE_MODE_SC;
-        if (!(mode & PEE_MODE_SC))
-            HIP_TRY(pee_zero(st, stw, L.ctl - L.st + PEE_CTL_WORDS(P->B, L.nchunks) * 4, meta, (size_t)P->B * sizeof(codec_pee_meta),
-                             inplace ? lm : nullptr, inplace ? (size_t)P->B * P->lm_words * 8 : 0));
-        bool sc_fresh = false;
-        const int sc_epoch = (mode & PEE_MODE_SC) ? pee_ws_epoch(workspace, &sc_fresh) : 0;
-        if (sc_fresh)   // a pointer never seen: start its self-cleaning state clean
-            HIP_TRY(pee_zero(st, stw, L.ctl - L.st + PEE_CTL_WORDS(P->B, L.nchunks) * 4));
+    if (pee_lookback_fits(R, L, P->B)) {
+        PeeLb S;
+        int rc = pee_lookback_setup(&S, P, C, R, gate, workspace, "CODEC_PEE_1P_CHUNK_MAJOR", "CODEC_PEE_1P_NOTICKET",
+                                    "CODEC_PEE_1P_GROUP", meta, (size_t)P->B * sizeof(codec_pee_meta),
+                                    inplace ? lm : nullptr, inplace ? (size_t)P->B * P->lm_words * 8 : 0);
+        if (rc) return rc;
         ProfScope prof(st, CODEC_K_PEE_EMBED1);
-        const long long total = pee_total_slots(P->B, L.nchunks, pee_group8(P->B, mode, inplace));
-        long long g = knob(inplace ? "CODEC_PEE_IP_WGS" : "CODEC_PEE_1P_WGS", inplace ? 2048 : (1 << 30));
-        if (g > total) g = total;
-        g = (g + 7) / 8 * 8;   // keep every workgroup on one slot lane (pee_slot)
-        const uint32_t spin_max = (uint32_t)debug_knob("CODEC_PEE_LB_SPINS", inplace ? (1 << 22) : (1 << 14));
-        const int dbg_skip = (int)debug_knob("CODEC_PEE_DEBUG_SKIP", 0) - 1;
-        const int dbg_stale = (int)debug_knob("CODEC_PEE_DEBUG_STALE", 0) - 1;
-        uint32_t* diag = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + L.diag);
-#define PE1S(TT, NTV, IP, SCV) hipLaunchKernelGGL((k_pee_embed1<TT, NTV, IP, SCV>), dim3((unsigned)g), dim3(256), 0, st, \
-            static_cast<const TT*>(cover), static_cast<TT*>(stego), P->H, P->W, P->T, P->maxval, lengths, \
-            reinterpret_cast<const u64*>(payload), P->payload_words, L.nchunks, P->B, stw, ctl, meta, \
-            reinterpret_cast<u64*>(lm), P->lm_words, mode, spin_max, dbg_skip, diag, tps, sc_epoch, dbg_stale, gps)
-#define PE1(TT, NTV, IP) do { if (!(IP) && (mode & PEE_MODE_SC)) PE1S(TT, NTV, false, true); else PE1S(TT, NTV, IP, false); } while (0)
-        // gated: non-temporal accesses only (CODEC_NT is an A/B knob of the ungated kernels)
-#define PE1G(TT, IP) hipLaunchKernelGGL((k_pee_embed1<TT, true, IP, false, true>), dim3((unsigned)g), dim3(256), 0, st, \
-            static_cast<const TT*>(cover), static_cast<TT*>(stego), P->H, P->W, P->T, P->maxval, lengths, \
-            reinterpret_cast<const u64*>(payload), P->payload_words, L.nchunks, P->B, stw, ctl, meta, \
-            reinterpret_cast<u64*>(lm), P->lm_words, mode, spin_max, dbg_skip, diag, tps, sc_epoch, dbg_stale, gps)
-        if (gate) {
-            if (P->bytes == 2) { if (inplace) PE1G(uint16_t, true); else PE1G(uint16_t, false); }
-            else { if (inplace) PE1G(uint8_t, true); else PE1G(uint8_t, false); }
-        } else
-        if (P->bytes == 2) {
-            if (inplace) { if (nt) PE1(uint16_t, true, true); else PE1(uint16_t, false, true); }
-            else { if (nt) PE1(uint16_t, true, false); else PE1(uint16_t, false, false); }
-        } else {
-            if (inplace) { if (nt) PE1(uint8_t, true, true); else PE1(uint8_t, false, true); }
-            else { if (nt) PE1(uint8_t, true, false); else PE1(uint8_t, false, false); }
-        }
-#undef PE1
-#undef PE1S
-#undef PE1G
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3((unsigned)S.g), dim3(256), 0, st, cover, stego, P->H, P->W, P->T, P->maxval,
+                               lengths, payload, P->payload_words, L.nchunks, P->B, S.stw, S.ctl, meta, lm, P->lm_words,
+                               S.mode, S.spin_max, S.dbg_skip, S.diag, tps, S.sc_epoch, S.dbg_stale, gps);
+        };
+        // gated: non-temporal accesses only (CODEC_NT is an A/B knob of the ungated kernels);
+        // self-cleaning: out of place only (flat)
+        if (gate) pee_flag(inplace, [&](auto ip) { go(k_pee_embed1<TT, true, ip(), false, true>); });
+        else if (S.sc() && !inplace) pee_flag(nt, [&](auto n) { go(k_pee_embed1<TT, n(), false, true>); });
+        else pee_flag(nt, inplace, [&](auto n, auto ip) { go(k_pee_embed1<TT, n(), ip(), false>); });
         LAUNCH_CHECK("k_pee_embed1");
         // odd H: the last row of each slice belongs to no row pair (no candidate, no MED
         // neighbour); out of place it is copied verbatim
@@ -3676,58 +3746,62 @@ static int pee_embed_impl(const codec_pee_params* P, const void* cover, void* st
             long long gw = knob("CODEC_PEE_SCAN_GS_WGS", 32768);   // tools/tune_pee.py
             if (gw > (tot + 3) / 4) gw = (tot + 3) / 4;
             if (gw < 1) gw = 1;
-#define PSCAN(TT, NTV, GV) hipLaunchKernelGGL((k_pee_scan<TT, NTV, GV>), dim3((unsigned)gw), dim3(256), 0, st, static_cast<const TT*>(cover), static_cast<TT*>(stego), P->H, P->W, P->T, P->maxval, cnt, L.ntiles_max, P->B, tps, gps)
-            if (gate) { if (P->bytes == 2) PSCAN(uint16_t, true, true); else PSCAN(uint8_t, true, true); }
-            else if (P->bytes == 2) { if (nt) PSCAN(uint16_t, true, false); else PSCAN(uint16_t, false, false); }
-            else { if (nt) PSCAN(uint8_t, true, false); else PSCAN(uint8_t, false, false); }
-#undef PSCAN
+            auto go = [&](auto kern) {
+                hipLaunchKernelGGL(kern, dim3((unsigned)gw), dim3(256), 0, st, cover, stego, P->H, P->W, P->T, P->maxval,
+                                   cnt, L.ntiles_max, P->B, tps, gps);
+            };
+            if (gate) go(k_pee_scan<TT, true, true>);   // gated: non-temporal only
+            else pee_flag(nt, [&](auto n) { go(k_pee_scan<TT, n(), false>); });
             LAUNCH_CHECK("k_pee_scan");
         } else {
             if (!inplace) HIP_TRY(hipMemcpyAsync(stego, cover, (size_t)npx * P->B * P->bytes, hipMemcpyDeviceToDevice, st));
-#define PCNT(TT, GV) hipLaunchKernelGGL((k_pee_count<TT, GV>), grid, dim3(256), 0, st, static_cast<const TT*>(cover), \
-                                        P->H, P->W, P->T, P->maxval, per, cnt, L.ntiles_max, tps, gps)
-            if (P->bytes == 2) { if (gate) PCNT(uint16_t, true); else PCNT(uint16_t, false); }
-            else { if (gate) PCNT(uint8_t, true); else PCNT(uint8_t, false); }
-#undef PCNT
+            pee_flag(gate, [&](auto gv) {
+                hipLaunchKernelGGL((k_pee_count<TT, gv()>), grid, dim3(256), 0, st, cover, P->H, P->W, P->T, P->maxval, per,
+                                   cnt, L.ntiles_max, tps, gps);
+            });
             LAUNCH_CHECK("k_pee_count");
         }
     }
     {
         ProfScope prof(st, CODEC_K_PEE_LOCATE);
-#define PLOC(TT, GV) hipLaunchKernelGGL((k_pee_locate<TT, GV>), dim3(P->B), dim3(256), 0, st, static_cast<const TT*>(cover), \
-                                        P->H, P->W, P->T, P->maxval, lengths, cnt, off, L.ntiles_max, meta, tps, gps)
-        if (P->bytes == 2) { if (gate) PLOC(uint16_t, true); else PLOC(uint16_t, false); }
-        else { if (gate) PLOC(uint8_t, true); else PLOC(uint8_t, false); }
-#undef PLOC
+        pee_flag(gate, [&](auto gv) {
+            hipLaunchKernelGGL((k_pee_locate<TT, gv()>), dim3(P->B), dim3(256), 0, st, cover, P->H, P->W, P->T, P->maxval,
+                               lengths, cnt, off, L.ntiles_max, meta, tps, gps);
+        });
         LAUNCH_CHECK("k_pee_locate");
     }
     {
         ProfScope prof(st, CODEC_K_PEE_EMBED);
         const int g = (int)knob("CODEC_PEE_EMBED_WGS", 64);
         dim3 grid(g < L.ntiles_max ? g : L.ntiles_max, P->B);
+        auto go = [&](auto kern) {   // k_pee_embed_v and k_pee_embed take the same arguments
+            hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, cover, stego, P->H, P->W, payload, P->payload_words, off,
+                               L.ntiles_max, meta, lm, P->lm_words);
+        };
         if (vec && knob("CODEC_PEE_EMBED_V", 1)) {
-#define PEMV(TT, GV) hipLaunchKernelGGL((k_pee_embed_v<TT, GV>), grid, dim3(256), 0, st, static_cast<const TT*>(cover), \
-                                        static_cast<TT*>(stego), P->H, P->W, reinterpret_cast<const u64*>(payload), \
-                                        P->payload_words, off, L.ntiles_max, meta, reinterpret_cast<u64*>(lm), P->lm_words)
-            if (P->bytes == 2) { if (gate) PEMV(uint16_t, true); else PEMV(uint16_t, false); }
-            else { if (gate) PEMV(uint8_t, true); else PEMV(uint8_t, false); }
-#undef PEMV
+            pee_flag(gate, [&](auto gv) { go(k_pee_embed_v<TT, gv()>); });
             LAUNCH_CHECK("k_pee_embed_v");
             return 0;
         }
-#define PEMB(TT, VV, GV) hipLaunchKernelGGL((k_pee_embed<TT, VV, GV>), grid, dim3(256), 0, st, static_cast<const TT*>(cover), \
-                               static_cast<TT*>(stego), P->H, P->W, reinterpret_cast<const u64*>(payload), \
-                               P->payload_words, off, L.ntiles_max, meta, reinterpret_cast<u64*>(lm), P->lm_words)
-        if (gate) {
-            if (P->bytes == 2) { if (vec) PEMB(uint16_t, true, true); else PEMB(uint16_t, false, true); }
-            else { if (vec) PEMB(uint8_t, true, true); else PEMB(uint8_t, false, true); }
-        }
-        else if (P->bytes == 2) { if (vec) PEMB(uint16_t, true, false); else PEMB(uint16_t, false, false); }
-        else { if (vec) PEMB(uint8_t, true, false); else PEMB(uint8_t, false, false); }
-#undef PEMB
+        pee_flag(vec, gate, [&](auto v, auto gv) { go(k_pee_embed<TT, v(), gv()>); });
         LAUNCH_CHECK("k_pee_embed");
     }
     return 0;
+}
+
+static int pee_embed_impl(const codec_pee_params* P, const void* cover, void* stego, const uint64_t* payload,
+                          const int32_t* lengths, const int32_t* tps, const int32_t* gps, codec_pee_meta* meta,
+                          uint64_t* lm, void* workspace, size_t workspace_bytes, void* stream) {
+    PeeCall C;
+    int rc = pee_begin(&C, P, pee_check(P), !cover || !stego || !payload || !lengths || !meta || !lm || !workspace,
+                       "codec_pee_embed", pee_no_more, workspace, workspace_bytes, stream, PEE_ENTER);
+    if (rc) return rc;
+    return pee_pixel(P->bytes, [&](auto px) {
+        using TT = decltype(px);
+        return pee_embed_t(P, C, static_cast<const TT*>(cover), static_cast<TT*>(stego),
+                           reinterpret_cast<const u64*>(payload), lengths, tps, gps, meta, reinterpret_cast<u64*>(lm),
+                           workspace);
+    });
 }
 
 extern "C" {
@@ -3735,22 +3809,21 @@ extern "C" {
 int codec_pee_embed_auto(const codec_pee_params* P, const void* cover, void* stego, const uint64_t* payload,
                          const int32_t* lengths, int32_t tmax, int32_t* t_out, codec_pee_meta* meta, uint64_t* lm,
                          void* workspace, size_t workspace_bytes, void* stream) {
-    int rc = pee_check(P);
+    PeeCall C;
+    int rc = pee_begin(&C, P, pee_check(P), !cover || !stego || !payload || !lengths || !t_out || !meta || !lm || !workspace,
+                       "codec_pee_embed_auto", [&] {
+        return tmax < 1 || tmax > PEE_TMAX_MAX ? set_err(CODEC_EINVAL, "tmax must be in 1..64") : 0;
+    }, workspace, workspace_bytes, stream, PEE_ENTER);
     if (rc) return rc;
-    if (!cover || !stego || !payload || !lengths || !t_out || !meta || !lm || !workspace)
-        return set_err(CODEC_EINVAL, "codec_pee_embed_auto: NULL pointer argument");
-    if (tmax < 1 || tmax > PEE_TMAX_MAX) return set_err(CODEC_EINVAL, "tmax must be in 1..64");
-    const PeeWs L = pee_ws(P);
-    if (workspace_bytes < L.total) return set_err(CODEC_EINVAL, "workspace too small");
-    HIP_TRY(pee_ws_enter(workspace, P, L, as_stream(stream)));   // another shape's state: zeroed first
-    hipStream_t st = as_stream(stream);
-    const bool inplace = cover == stego;
-    const bool vec = (P->W % 8) == 0 && ((uintptr_t)cover % 16) == 0 && ((uintptr_t)stego % 16) == 0;
-    const long long items = (long long)(P->H / 2) * (P->W / 8);
+    const PeeWs& L = C.L;
+    hipStream_t st = C.st;
+    const PeeRoute R = pee_route(P, cover, stego, 16);   // 16-B vectors whatever P->bytes: the fused kernels are uint16_t's
+    const bool inplace = R.inplace;
+    const long long items = R.items;
     // fused single launch where the embed is slice-serial anyway (chip-filling batches of
     // <= 64-chunk slices, e.g. C3, or in place) and the counters fit beside the payload in
     // the LDS pad; elsewhere the capacity pass and the per-slice-T embed as two launches
-    const bool fused = P->bytes == 2 && vec && items > 0 && knob("CODEC_PEE_ONEPASS", -1) != 0 &&
+    const bool fused = P->bytes == 2 && R.vec && items > 0 && R.onepass != 0 &&
                        knob("CODEC_PEE_AUTO_FUSED", 1) != 0 && tmax <= SS_AUTO_TMAX &&
                        P->payload_words <= SS_PAY_WORDS && knob("CODEC_PEE_SS_PAYLDS", 1) != 0 &&
                        2LL * P->payload_words <= (long long)SS_AUTO_CNT_BASE(tmax) && pee_use_slice_serial(P, inplace);
@@ -3759,6 +3832,11 @@ int codec_pee_embed_auto(const codec_pee_params* P, const void* cover, void* ste
         if (rc) return rc;
         return codec_pee_embed_ts(P, cover, stego, payload, lengths, t_out, meta, lm, workspace, workspace_bytes, stream);
     }
+    const uint16_t* src = static_cast<const uint16_t*>(cover);
+    uint16_t* dst = static_cast<uint16_t*>(stego);
+    const u64* pay = reinterpret_cast<const u64*>(payload);
+    u64* lmw = reinterpret_cast<u64*>(lm);
+    char* sink = static_cast<char*>(workspace) + L.sink;
     const bool nt = knob("CODEC_NT", 1) != 0;
     // resident variant (out of place, slices of <= 512 x 32 items, e.g. C3 / C4's 512^2): the
     // cover is read once and kept on the CU between the capacity and the embed phase
@@ -3780,39 +3858,46 @@ int codec_pee_embed_auto(const codec_pee_params* P, const void* cover, void* ste
                      knob("CODEC_PEE_RES_LIN", 1) != 0;
     if (!inplace && knob("CODEC_PEE_RES", 1) != 0 && res_fits(nth) && tmax <= SS_AUTO_TMAX) {
         ProfScope prof(st, CODEC_K_PEE_EMBED_RES);
-#define PRES(NI, NTV, NTS, NTH, LN) hipLaunchKernelGGL((k_pee_embed_res<NI, NTV, NTS, NTH, LN>), dim3((unsigned)P->B), dim3(NTH), 0, st, \
-            static_cast<const uint16_t*>(cover), static_cast<uint16_t*>(stego), P->H, P->W, P->maxval, lengths, \
-            reinterpret_cast<const u64*>(payload), P->payload_words, meta, reinterpret_cast<u64*>(lm), P->lm_words, \
-            static_cast<char*>(workspace) + L.sink, (int)tmax, t_out, trace)
         const int trace = (int)knob("CODEC_PEE_RES_TRACE", 0);
         // non-temporal loads, plain stores (nt stores: read phase 29.6 -> 32.5 us at C3);
         // CODEC_PEE_RES_NTS=1 / CODEC_NT=0 for A/B
         const bool nts = knob("CODEC_PEE_RES_NTS", 0) != 0;
-#define PRESN(NI, NTH, LN) do { if (!nt) PRES(NI, false, false, NTH, LN); else if (nts) PRES(NI, true, true, NTH, LN); \
-                                else PRES(NI, true, false, NTH, LN); } while (0)
+        // ni items per lane, nthr threads, ln: the LIN layout; then the cache policy
+        auto res = [&](auto ni, auto nthr, auto ln) {
+            constexpr int NI = ni(), NTH = nthr();
+            constexpr bool LN = ln();
+            auto go = [&](auto kern) {
+                hipLaunchKernelGGL(kern, dim3((unsigned)P->B), dim3(NTH), 0, st, src, dst, P->H, P->W, P->maxval, lengths,
+                                   pay, P->payload_words, meta, lmw, P->lm_words, sink, (int)tmax, t_out, trace);
+            };
+            if (!nt) go(k_pee_embed_res<NI, false, false, NTH, LN>);
+            else if (nts) go(k_pee_embed_res<NI, true, true, NTH, LN>);
+            else go(k_pee_embed_res<NI, true, false, NTH, LN>);
+        };
+        const std::true_type yes;
+        const std::false_type no;
         if (nth == 1024) {
-            if (lin) { if (nres <= 8) PRESN(8, 1024, true); else PRESN(16, 1024, true); }
-            else if (nres <= 8) PRESN(8, 1024, false);
-            else PRESN(16, 1024, false);
+            if (lin) { if (nres <= 8) res(pee_int<8>{}, pee_int<1024>{}, yes); else res(pee_int<16>{}, pee_int<1024>{}, yes); }
+            else if (nres <= 8) res(pee_int<8>{}, pee_int<1024>{}, no);
+            else res(pee_int<16>{}, pee_int<1024>{}, no);
         }
-        else if (nres <= 8) PRESN(8, 512, false);
-        else if (nres <= 16) PRESN(16, 512, false);
-        else PRESN(32, 512, false);
-#undef PRESN
-#undef PRES
+        else if (nres <= 8) res(pee_int<8>{}, pee_int<512>{}, no);
+        else if (nres <= 16) res(pee_int<16>{}, pee_int<512>{}, no);
+        else res(pee_int<32>{}, pee_int<512>{}, no);
         LAUNCH_CHECK("k_pee_embed_res");
         if (P->H & 1) HIP_TRY(pee_copy_last_rows(P, cover, stego, st));
         return 0;
     }
     ProfScope prof(st, CODEC_K_PEE_EMBED_SS_AUTO);
-#define PEA(NTV, IP, DD) hipLaunchKernelGGL((k_pee_embed_ss<uint16_t, NTV, IP, DD, true, true>), dim3((unsigned)P->B), \
-            dim3(SS_THREADS), 0, st, static_cast<const uint16_t*>(cover), static_cast<uint16_t*>(stego), P->H, P->W, \
-            P->T, P->maxval, lengths, nullptr, reinterpret_cast<const u64*>(payload), P->payload_words, meta, \
-            reinterpret_cast<u64*>(lm), P->lm_words, static_cast<char*>(workspace) + L.sink, (int)tmax, t_out)
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)P->B), dim3(SS_THREADS), 0, st, src, dst, P->H, P->W, P->T, P->maxval,
+                           lengths, nullptr, pay, P->payload_words, meta, lmw, P->lm_words, sink, (int)tmax, t_out);
+    };
     // ring depths as in codec_pee_embed_ts (in place 2, out of place 4)
-    if (inplace) { if (nt) PEA(true, true, 2); else PEA(false, true, 2); }
-    else { if (nt) PEA(true, false, 4); else PEA(false, false, 4); }
-#undef PEA
+    pee_flag(nt, [&](auto n) {
+        if (inplace) go(k_pee_embed_ss<uint16_t, n(), true, 2, true, true>);
+        else go(k_pee_embed_ss<uint16_t, n(), false, 4, true, true>);
+    });
     LAUNCH_CHECK("k_pee_embed_ss(auto)");
     if ((P->H & 1) && !inplace) HIP_TRY(pee_copy_last_rows(P, cover, stego, st));
     return 0;
@@ -3820,36 +3905,26 @@ int codec_pee_embed_auto(const codec_pee_params* P, const void* cover, void* ste
 
 }  // extern "C"
 
-// gate: the kernels read each record's gate (reserved[1]; codec_pee_gate_extract) -- the same
-// routes as the ungated call but the slice-serial kernels and the self-cleaning look-back
-static int pee_extract_impl(const codec_pee_params* P, const void* stego, const codec_pee_meta* meta, const uint64_t* lm,
-                            void* cover_out, uint64_t* payload_out, void* workspace, size_t workspace_bytes, void* stream,
-                            bool gate) {
-    int rc = pee_check(P);
-    if (rc) return rc;
-    if (!stego || !meta || !lm || !cover_out || !payload_out || !workspace)
-        return set_err(CODEC_EINVAL, "codec_pee_extract: NULL pointer argument");
-    const PeeWs L = pee_ws(P);
-    if (workspace_bytes < L.total) return set_err(CODEC_EINVAL, "workspace too small");
-    HIP_TRY(pee_ws_enter(workspace, P, L, as_stream(stream)));   // another shape's state: zeroed first
-    hipStream_t st = as_stream(stream);
+// the extract's routes for one pixel type; gate: the kernels read each record's gate
+// (reserved[1]; codec_pee_gate_extract) -- the same routes as the ungated call but the
+// slice-serial kernels and the self-cleaning look-back
+template <typename TT>
+static int pee_extract_t(const codec_pee_params* P, const PeeCall& C, const TT* stego, const codec_pee_meta* meta,
+                         const u64* lm, TT* cover_out, u64* payload_out, void* workspace, bool gate) {
+    constexpr bool U16 = std::is_same_v<TT, uint16_t>;
+    const PeeWs& L = C.L;
+    hipStream_t st = C.st;
     uint32_t* cnt = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + L.cnt);
     uint32_t* off = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + L.off);
+    uint32_t* ctl = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + L.ctl);
     const long long nbytes = (long long)P->H * P->W * P->B * P->bytes;
     const bool nt = knob("CODEC_PEE_X_NT", knob("CODEC_NT", 1)) != 0;   // CODEC_PEE_X_NT: extract only (A/B)
-    const size_t va = P->bytes == 2 ? 16 : 8;
-    const bool vec = (P->W % 8) == 0 && ((uintptr_t)stego % va) == 0 && ((uintptr_t)cover_out % va) == 0;
-    const long long items = (long long)(P->H / 2) * (P->W / 8);
-    const bool inplace = stego == cover_out;
-    const long long onepass = knob("CODEC_PEE_ONEPASS", -1);   // as in codec_pee_embed
-    if (!gate && vec && items > 0 && onepass != 0 && pee_use_slice_serial(P, inplace)) {
+    const PeeRoute R = pee_route(P, stego, cover_out);   // as in codec_pee_embed
+    const bool vec = R.vec, inplace = R.inplace;
+    const long long items = R.items;
+    if (!gate && vec && items > 0 && R.onepass != 0 && pee_use_slice_serial(P, inplace)) {
         // slice-serial: writes every payload word itself (no memset) and never sets the flag
-        uint32_t* ctl = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + L.ctl);
         ProfScope prof(st, CODEC_K_PEE_EXTRACT_SS);
-#define PXSD(TT, NTV, IP, DD) hipLaunchKernelGGL((k_pee_extract_ss<TT, NTV, IP, DD>), dim3((unsigned)P->B), dim3(SS_THREADS), 0, st, \
-            static_cast<const TT*>(stego), static_cast<TT*>(cover_out), P->H, P->W, meta, reinterpret_cast<const u64*>(lm), \
-            P->lm_words, reinterpret_cast<u64*>(payload_out), P->payload_words, ctl + 1, static_cast<char*>(workspace) + L.sink)
-#define PXS(TT, NTV, IP) PXSD(TT, NTV, IP, 4)
         // ring depth (knob: 2, 4, 6).  Out of place (slices of <= 64 chunks, e.g. C3) 2: the
         // ring refills right behind the chunk, 0.0531 -> 0.0517 ms at 256 x 512^2; in place 4
         // (2: 0.0747 -> 0.0761 ms at 256 x 2048^2; 6 is slower everywhere, 0.064 / 0.086)
@@ -3859,125 +3934,81 @@ static int pee_extract_impl(const codec_pee_params* P, const void* stego, const 
         // CODEC_PEE_SSX_EARLY=0 restores the late refill (then CODEC_PEE_SSX_D picks 2 / 4 / 6)
         const bool xe = knob("CODEC_PEE_SSX_EARLY", inplace ? 1 : 0) != 0;
         const long long xde = knob("CODEC_PEE_SSX_D", inplace ? 1 : 2);
-#define PXSE(IP, DD) hipLaunchKernelGGL((k_pee_extract_ss<uint16_t, true, IP, DD, true>), dim3((unsigned)P->B), dim3(SS_THREADS), 0, st, \
-            static_cast<const uint16_t*>(stego), static_cast<uint16_t*>(cover_out), P->H, P->W, meta, reinterpret_cast<const u64*>(lm), \
-            P->lm_words, reinterpret_cast<u64*>(payload_out), P->payload_words, ctl + 1, static_cast<char*>(workspace) + L.sink)
         // in place, early ring of one: cache policies as for the in-place embed (CODEC_PEE_IP_NTL / _NTS)
         const bool xip_ntl = knob("CODEC_PEE_IP_NTL", 1) != 0, xip_nts = knob("CODEC_PEE_IP_NTS", 0) != 0;
-#define PXSP(NTL, NTSV) hipLaunchKernelGGL((k_pee_extract_ss<uint16_t, NTL, true, 1, true, NTSV>), dim3((unsigned)P->B), \
-            dim3(SS_THREADS), 0, st, static_cast<const uint16_t*>(stego), static_cast<uint16_t*>(cover_out), P->H, P->W, meta, \
-            reinterpret_cast<const u64*>(lm), P->lm_words, reinterpret_cast<u64*>(payload_out), P->payload_words, ctl + 1, \
-            static_cast<char*>(workspace) + L.sink)
-        if (P->bytes == 2 && nt && xe) {
-            if (inplace) {
-                if (xde == 1) {
-                    if (xip_ntl && xip_nts) PXSP(true, true);
-                    else if (xip_ntl) PXSP(true, false);
-                    else if (xip_nts) PXSP(false, true);
-                    else PXSP(false, false);
-                }
-                else if (xde == 2) PXSE(true, 2); else PXSE(true, 4);
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3((unsigned)P->B), dim3(SS_THREADS), 0, st, stego, cover_out, P->H, P->W, meta, lm,
+                               P->lm_words, payload_out, P->payload_words, ctl + 1, static_cast<char*>(workspace) + L.sink);
+        };
+        bool ring4 = true;   // the late ring of 4, every pixel type, policy and placement
+        if constexpr (U16) {   // early refill and the other late depths: uint16_t, non-temporal
+            if (nt && xe) {
+                if (inplace && xde == 1)
+                    pee_flag(xip_ntl, xip_nts,
+                             [&](auto ntl, auto nts) { go(k_pee_extract_ss<TT, ntl(), true, 1, true, nts()>); });
+                else if (inplace && xde == 2) go(k_pee_extract_ss<TT, true, true, 2, true>);
+                else if (inplace) go(k_pee_extract_ss<TT, true, true, 4, true>);
+                else if (xde == 1) go(k_pee_extract_ss<TT, true, false, 1, true>);
+                else if (xde == 2) go(k_pee_extract_ss<TT, true, false, 2, true>);
+                else go(k_pee_extract_ss<TT, true, false, 4, true>);
+                ring4 = false;
+            } else if (nt && xd != 4) {
+                pee_flag(inplace, [&](auto ip) {
+                    if (xd == 2) go(k_pee_extract_ss<TT, true, ip(), 2>);
+                    else go(k_pee_extract_ss<TT, true, ip(), 6>);
+                });
+                ring4 = false;
             }
-            else { if (xde == 1) PXSE(false, 1); else if (xde == 2) PXSE(false, 2); else PXSE(false, 4); }
-        } else if (P->bytes == 2 && nt && xd != 4) {
-            if (inplace) { if (xd == 2) PXSD(uint16_t, true, true, 2); else PXSD(uint16_t, true, true, 6); }
-            else { if (xd == 2) PXSD(uint16_t, true, false, 2); else PXSD(uint16_t, true, false, 6); }
-        } else if (P->bytes == 2) {
-            if (inplace) { if (nt) PXS(uint16_t, true, true); else PXS(uint16_t, false, true); }
-            else { if (nt) PXS(uint16_t, true, false); else PXS(uint16_t, false, false); }
-        } else {
-            if (inplace) { if (nt) PXS(uint8_t, true, true); else PXS(uint8_t, false, true); }
-            else { if (nt) PXS(uint8_t, true, false); else PXS(uint8_t, false, false); }
         }
-#undef PXS
-#undef PXSD
-#undef PXSE
-#undef PXSP
+        if (ring4) pee_flag(nt, inplace, [&](auto n, auto ip) { go(k_pee_extract_ss<TT, n(), ip(), 4>); });
         LAUNCH_CHECK("k_pee_extract_ss");
         if ((P->H & 1) && !inplace) HIP_TRY(pee_copy_last_rows(P, stego, cover_out, st));
         return 0;
     }
-    const bool flat = !inplace && P->B < 32 && P->B <= knob("CODEC_PEE_FLAT_MAXB", 7);
-    if (vec && items > 0 && (long long)L.nchunks * P->B < 0x7FFFFFFFLL && onepass != 0) {
-        u64* stw = reinterpret_cast<u64*>(static_cast<char*>(workspace) + L.st);
-        uint32_t* ctl = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + L.ctl);
-        int mode = flat ? PEE_MODE_FLAT | (knob("CODEC_PEE_FLAT_TICKET", 0) ? 0 : PEE_MODE_NOTICKET)
-                        : (knob("CODEC_PEE_X_CHUNK_MAJOR", knob("CODEC_PEE_1P_CHUNK_MAJOR", 1)) ? PEE_MODE_CMAJOR : 0) |
-                              (knob("CODEC_PEE_X_NOTICKET", 1) ? PEE_MODE_NOTICKET : 0) |
-                              ((int)(knob("CODEC_PEE_X_GROUP", 32) / 8) << 8);
-        if (!gate && flat && (mode & PEE_MODE_NOTICKET) && knob("CODEC_PEE_SELFCLEAN", 1) && pee_sc_fits(P, st, workspace)) mode |= PEE_MODE_SC;
-        if (!(mode & PEE_MODE_SC))
-            HIP_TRY(pee_zero(st, payload_out, (size_t)P->B * P->payload_words * 8, stw, L.ctl - L.st + PEE_CTL_WORDS(P->B, L.nchunks) * 4));
-        bool sc_fresh = false;
-        const int sc_epoch = (mode & PEE_MODE_SC) ? pee_ws_epoch(workspace, &sc_fresh) : 0;
-        if (sc_fresh)   // a pointer never seen: start its self-cleaning state clean
-            HIP_TRY(pee_zero(st, stw, L.ctl - L.st + PEE_CTL_WORDS(P->B, L.nchunks) * 4));
+    if (pee_lookback_fits(R, L, P->B)) {
+        PeeLb S;
+        int rc = pee_lookback_setup(&S, P, C, R, gate, workspace, "CODEC_PEE_X_CHUNK_MAJOR", "CODEC_PEE_X_NOTICKET",
+                                    "CODEC_PEE_X_GROUP", payload_out, (size_t)P->B * P->payload_words * 8, nullptr, 0);
+        if (rc) return rc;
         ProfScope prof(st, CODEC_K_PEE_EXTRACT1);
-        const long long total = pee_total_slots(P->B, L.nchunks, pee_group8(P->B, mode, inplace));
-        long long g = knob(inplace ? "CODEC_PEE_IP_WGS" : "CODEC_PEE_1P_WGS", inplace ? 2048 : (1 << 30));
-        if (g > total) g = total;
-        g = (g + 7) / 8 * 8;
-        const uint32_t spin_max = (uint32_t)debug_knob("CODEC_PEE_LB_SPINS", inplace ? (1 << 22) : (1 << 14));
-        const int dbg_skip = (int)debug_knob("CODEC_PEE_DEBUG_SKIP", 0) - 1;
-        const int dbg_stale = (int)debug_knob("CODEC_PEE_DEBUG_STALE", 0) - 1;
-        uint32_t* diag = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + L.diag);
-#define PX1S(TT, NTV, IP, SCV) hipLaunchKernelGGL((k_pee_extract1<TT, NTV, IP, SCV>), dim3((unsigned)g), dim3(256), 0, st, \
-            static_cast<const TT*>(stego), static_cast<TT*>(cover_out), P->H, P->W, meta, reinterpret_cast<const u64*>(lm), \
-            P->lm_words, L.nchunks, P->B, stw, ctl, reinterpret_cast<u64*>(payload_out), P->payload_words, mode, spin_max, \
-            dbg_skip, diag, sc_epoch, dbg_stale)
-#define PX1(TT, NTV, IP) do { if (!(IP) && (mode & PEE_MODE_SC)) PX1S(TT, NTV, false, true); else PX1S(TT, NTV, IP, false); } while (0)
-        // gated: non-temporal accesses only, as the gated embed
-#define PX1G(TT, IP) hipLaunchKernelGGL((k_pee_extract1<TT, true, IP, false, true>), dim3((unsigned)g), dim3(256), 0, st, \
-            static_cast<const TT*>(stego), static_cast<TT*>(cover_out), P->H, P->W, meta, reinterpret_cast<const u64*>(lm), \
-            P->lm_words, L.nchunks, P->B, stw, ctl, reinterpret_cast<u64*>(payload_out), P->payload_words, mode, spin_max, \
-            dbg_skip, diag, sc_epoch, dbg_stale)
-        if (gate) {
-            if (P->bytes == 2) { if (inplace) PX1G(uint16_t, true); else PX1G(uint16_t, false); }
-            else { if (inplace) PX1G(uint8_t, true); else PX1G(uint8_t, false); }
-        } else
-        if (P->bytes == 2) {
-            if (inplace) { if (nt) PX1(uint16_t, true, true); else PX1(uint16_t, false, true); }
-            else { if (nt) PX1(uint16_t, true, false); else PX1(uint16_t, false, false); }
-        } else {
-            if (inplace) { if (nt) PX1(uint8_t, true, true); else PX1(uint8_t, false, true); }
-            else { if (nt) PX1(uint8_t, true, false); else PX1(uint8_t, false, false); }
-        }
-#undef PX1
-#undef PX1S
-#undef PX1G
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3((unsigned)S.g), dim3(256), 0, st, stego, cover_out, P->H, P->W, meta, lm,
+                               P->lm_words, L.nchunks, P->B, S.stw, S.ctl, payload_out, P->payload_words, S.mode,
+                               S.spin_max, S.dbg_skip, S.diag, S.sc_epoch, S.dbg_stale);
+        };
+        // gated: non-temporal accesses only, as the gated embed; self-cleaning: out of place only
+        if (gate) pee_flag(inplace, [&](auto ip) { go(k_pee_extract1<TT, true, ip(), false, true>); });
+        else if (S.sc() && !inplace) pee_flag(nt, [&](auto n) { go(k_pee_extract1<TT, n(), false, true>); });
+        else pee_flag(nt, inplace, [&](auto n, auto ip) { go(k_pee_extract1<TT, n(), ip(), false>); });
         LAUNCH_CHECK("k_pee_extract1");
         if ((P->H & 1) && !inplace) HIP_TRY(pee_copy_last_rows(P, stego, cover_out, st));
         return 0;
     }
     HIP_TRY(hipMemsetAsync(payload_out, 0, (size_t)P->B * P->payload_words * 8, st));
-    {   // the single pass's look-back flag (codec_pee_extract_flag_offset) stays clear here
-        uint32_t* ctl = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + L.ctl);
-        HIP_TRY(hipMemsetAsync(ctl + 1, 0, 4, st));
-    }
+    // the single pass's look-back flag (codec_pee_extract_flag_offset) stays clear here
+    HIP_TRY(hipMemsetAsync(ctl + 1, 0, 4, st));
+    const int g = (int)knob("CODEC_PEE_EMBED_WGS", 64);
+    dim3 grid(g < L.ntiles_max ? g : L.ntiles_max, P->B);
+    // k_pee_dcount_w / k_pee_dcount, then the tile offsets
+    auto dcount = [&](auto kern, dim3 gr) {
+        hipLaunchKernelGGL(kern, gr, dim3(256), 0, st, stego, P->H, P->W, meta, lm, P->lm_words, cnt, L.ntiles_max);
+    };
+    auto offsets = [&]() {
+        hipLaunchKernelGGL(k_pee_offsets, dim3(P->B), dim3(256), 0, st, meta, cnt, off, L.ntiles_max);
+    };
     const bool fused = vec && knob("CODEC_PEE_FUSED", 1) != 0 && (P->W % 8) == 0 && items > 0 && (items % 256) == 0 &&
                        items * P->B < 0xFFFFFFFFLL;
     if (fused) {
-        const int g = (int)knob("CODEC_PEE_EMBED_WGS", 64);
-        dim3 grid(g < L.ntiles_max ? g : L.ntiles_max, P->B);
         {
             ProfScope prof(st, CODEC_K_PEE_DCOUNT);
             if (knob("CODEC_PEE_WAVE_TILES", 1)) {
                 const int gw = (int)knob("CODEC_PEE_DCOUNT_W_WGS", 8);   // 4 waves (tiles) per workgroup
-                dim3 gridw(gw, P->B);
-#define PDCW(TT, GV) hipLaunchKernelGGL((k_pee_dcount_w<TT, GV>), gridw, dim3(256), 0, st, static_cast<const TT*>(stego), P->H, P->W, \
-                               meta, reinterpret_cast<const u64*>(lm), P->lm_words, cnt, L.ntiles_max)
-                if (P->bytes == 2) { if (gate) PDCW(uint16_t, true); else PDCW(uint16_t, false); }
-                else { if (gate) PDCW(uint8_t, true); else PDCW(uint8_t, false); }
-#undef PDCW
+                pee_flag(gate, [&](auto gv) { dcount(k_pee_dcount_w<TT, gv()>, dim3(gw, P->B)); });
             } else {
-#define PDC2(TT, GV) hipLaunchKernelGGL((k_pee_dcount<TT, true, GV>), grid, dim3(256), 0, st, static_cast<const TT*>(stego), P->H, P->W, \
-                               meta, reinterpret_cast<const u64*>(lm), P->lm_words, cnt, L.ntiles_max)
-                if (P->bytes == 2) { if (gate) PDC2(uint16_t, true); else PDC2(uint16_t, false); }
-                else { if (gate) PDC2(uint8_t, true); else PDC2(uint8_t, false); }
-#undef PDC2
+                pee_flag(gate, [&](auto gv) { dcount(k_pee_dcount<TT, true, gv()>, grid); });
             }
             LAUNCH_CHECK("k_pee_dcount");
-            hipLaunchKernelGGL(k_pee_offsets, dim3(P->B), dim3(256), 0, st, meta, cnt, off, L.ntiles_max);
+            offsets();
             LAUNCH_CHECK("k_pee_offsets");
         }
         ProfScope prof(st, CODEC_K_PEE_RECOVER);
@@ -3985,64 +4016,57 @@ static int pee_extract_impl(const codec_pee_params* P, const void* stego, const 
         long long gg = (total + 1023) / 1024;
         const long long cap = knob("CODEC_PEE_RESTORE_WGS", 1 << 30);
         if (gg > cap) gg = cap;
-#define PRG(TT, NTV, GV) hipLaunchKernelGGL((k_pee_restore_gs<TT, NTV, GV>), dim3((unsigned)gg), dim3(256), 0, st, static_cast<const TT*>(stego), \
-                static_cast<TT*>(cover_out), P->H, P->W, (uint32_t)items, total, meta, reinterpret_cast<const u64*>(lm), P->lm_words, \
-                off, L.ntiles_max, reinterpret_cast<u64*>(payload_out), P->payload_words)
-        if (gate) { if (P->bytes == 2) PRG(uint16_t, true, true); else PRG(uint8_t, true, true); }
-        else if (P->bytes == 2) { if (nt) PRG(uint16_t, true, false); else PRG(uint16_t, false, false); }
-        else { if (nt) PRG(uint8_t, true, false); else PRG(uint8_t, false, false); }
-#undef PRG
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3((unsigned)gg), dim3(256), 0, st, stego, cover_out, P->H, P->W, (uint32_t)items,
+                               total, meta, lm, P->lm_words, off, L.ntiles_max, payload_out, P->payload_words);
+        };
+        if (gate) go(k_pee_restore_gs<TT, true, true>);   // gated: non-temporal only
+        else pee_flag(nt, [&](auto n) { go(k_pee_restore_gs<TT, n(), false>); });
         LAUNCH_CHECK("k_pee_restore_gs");
         return 0;
     }
     {
         ProfScope prof(st, CODEC_K_PEE_COPY);
         if (((uintptr_t)stego % 16) == 0 && ((uintptr_t)cover_out % 16) == 0) {
-            const int g = (int)knob("CODEC_PEE_COPY_WGS", 16384);
-            if (P->bytes == 2) {
-                if (nt) hipLaunchKernelGGL((k_pee_copy<uint16_t, true>), dim3(g), dim3(256), 0, st, static_cast<const uint16_t*>(stego), static_cast<uint16_t*>(cover_out), nbytes);
-                else hipLaunchKernelGGL((k_pee_copy<uint16_t, false>), dim3(g), dim3(256), 0, st, static_cast<const uint16_t*>(stego), static_cast<uint16_t*>(cover_out), nbytes);
-            } else {
-                if (nt) hipLaunchKernelGGL((k_pee_copy<uint8_t, true>), dim3(g), dim3(256), 0, st, static_cast<const uint8_t*>(stego), static_cast<uint8_t*>(cover_out), nbytes);
-                else hipLaunchKernelGGL((k_pee_copy<uint8_t, false>), dim3(g), dim3(256), 0, st, static_cast<const uint8_t*>(stego), static_cast<uint8_t*>(cover_out), nbytes);
-            }
+            const int gc = (int)knob("CODEC_PEE_COPY_WGS", 16384);
+            pee_flag(nt, [&](auto n) {
+                hipLaunchKernelGGL((k_pee_copy<TT, n()>), dim3(gc), dim3(256), 0, st, stego, cover_out, nbytes);
+            });
             LAUNCH_CHECK("k_pee_copy");
         } else {
             HIP_TRY(hipMemcpyAsync(cover_out, stego, (size_t)nbytes, hipMemcpyDeviceToDevice, st));
         }
     }
-    const int g = (int)knob("CODEC_PEE_EMBED_WGS", 64);
-    dim3 grid(g < L.ntiles_max ? g : L.ntiles_max, P->B);
     {
         ProfScope prof(st, CODEC_K_PEE_DCOUNT);
-#define PDC(TT, VV, GV) hipLaunchKernelGGL((k_pee_dcount<TT, VV, GV>), grid, dim3(256), 0, st, static_cast<const TT*>(stego), P->H, P->W, \
-                               meta, reinterpret_cast<const u64*>(lm), P->lm_words, cnt, L.ntiles_max)
-        if (gate) {
-            if (P->bytes == 2) { if (vec) PDC(uint16_t, true, true); else PDC(uint16_t, false, true); }
-            else { if (vec) PDC(uint8_t, true, true); else PDC(uint8_t, false, true); }
-        }
-        else if (P->bytes == 2) { if (vec) PDC(uint16_t, true, false); else PDC(uint16_t, false, false); }
-        else { if (vec) PDC(uint8_t, true, false); else PDC(uint8_t, false, false); }
-#undef PDC
+        pee_flag(vec, gate, [&](auto v, auto gv) { dcount(k_pee_dcount<TT, v(), gv()>, grid); });
         LAUNCH_CHECK("k_pee_dcount");
-        hipLaunchKernelGGL(k_pee_offsets, dim3(P->B), dim3(256), 0, st, meta, cnt, off, L.ntiles_max);
+        offsets();
         LAUNCH_CHECK("k_pee_offsets");
     }
     {
         ProfScope prof(st, CODEC_K_PEE_RECOVER);
-#define PREC(TT, VV, GV) hipLaunchKernelGGL((k_pee_recover<TT, VV, GV>), grid, dim3(256), 0, st, static_cast<const TT*>(stego), \
-                               static_cast<TT*>(cover_out), P->H, P->W, meta, reinterpret_cast<const u64*>(lm), \
-                               P->lm_words, off, L.ntiles_max, reinterpret_cast<u64*>(payload_out), P->payload_words)
-        if (gate) {
-            if (P->bytes == 2) { if (vec) PREC(uint16_t, true, true); else PREC(uint16_t, false, true); }
-            else { if (vec) PREC(uint8_t, true, true); else PREC(uint8_t, false, true); }
-        }
-        else if (P->bytes == 2) { if (vec) PREC(uint16_t, true, false); else PREC(uint16_t, false, false); }
-        else { if (vec) PREC(uint8_t, true, false); else PREC(uint8_t, false, false); }
-#undef PREC
+        pee_flag(vec, gate, [&](auto v, auto gv) {
+            hipLaunchKernelGGL((k_pee_recover<TT, v(), gv()>), grid, dim3(256), 0, st, stego, cover_out, P->H, P->W, meta, lm,
+                               P->lm_words, off, L.ntiles_max, payload_out, P->payload_words);
+        });
         LAUNCH_CHECK("k_pee_recover");
     }
     return 0;
+}
+
+static int pee_extract_impl(const codec_pee_params* P, const void* stego, const codec_pee_meta* meta, const uint64_t* lm,
+                            void* cover_out, uint64_t* payload_out, void* workspace, size_t workspace_bytes, void* stream,
+                            bool gate) {
+    PeeCall C;
+    int rc = pee_begin(&C, P, pee_check(P), !stego || !meta || !lm || !cover_out || !payload_out || !workspace,
+                       "codec_pee_extract", pee_no_more, workspace, workspace_bytes, stream, PEE_ENTER);
+    if (rc) return rc;
+    return pee_pixel(P->bytes, [&](auto px) {
+        using TT = decltype(px);
+        return pee_extract_t(P, C, static_cast<const TT*>(stego), meta, reinterpret_cast<const u64*>(lm),
+                             static_cast<TT*>(cover_out), reinterpret_cast<u64*>(payload_out), workspace, gate);
+    });
 }
 
 extern "C" {
@@ -4804,29 +4828,22 @@ __global__ __launch_bounds__(256) void k_pee_pass0_fix(codec_pee_meta* __restric
     M->reserved[0] = 0;
 }
 
-static int pee_multi_check(const codec_pee_params* P, int pass) {
-    int rc = pee_check(P);
-    if (rc) return rc;
-    if (pass < 0 || pass > 3) return set_err(CODEC_EINVAL, "pass must be in 0..3");
-    if ((long long)P->B * P->H * P->W * P->bytes > (1LL << 40)) return set_err(CODEC_EINVAL, "batch too large");
-    return 0;
-}
-
 extern "C" {
 
 int codec_pee_multi_embed_pass(const codec_pee_params* P, int32_t pass, const void* cover, void* stego,
                                const uint64_t* payload, const int32_t* lengths, codec_pee_meta* metas, uint64_t* lm,
                                void* workspace, size_t workspace_bytes, void* stream) {
-    int rc = pee_multi_check(P, pass);
+    // lattice 0 is scheme 1's: its embed paths (copy fused, 16-B items, look-back or
+    // slice-serial) take the pass, and the records are made scheme 2's
+    const bool p0s1 = pass == 0 && knob("CODEC_PEE_MULTI_P0", 1) != 0;
+    PeeCall C;
+    int rc = pee_begin(&C, P, pee_multi_check(P, pass), !cover || !stego || !payload || !lengths || !metas || !lm || !workspace,
+                       "codec_pee_multi_embed_pass", pee_no_more, workspace, workspace_bytes, stream,
+                       p0s1 ? PEE_NO_ENTER : PEE_ENTER);
     if (rc) return rc;
-    if (!cover || !stego || !payload || !lengths || !metas || !lm || !workspace)
-        return set_err(CODEC_EINVAL, "codec_pee_multi_embed_pass: NULL pointer argument");
-    const PeeWs L = pee_ws(P);
-    if (workspace_bytes < L.total) return set_err(CODEC_EINVAL, "workspace too small");
-    hipStream_t st = as_stream(stream);
-    if (pass == 0 && knob("CODEC_PEE_MULTI_P0", 1) != 0) {
-        // lattice 0 is scheme 1's: its embed paths (copy fused, 16-B items, look-back or
-        // slice-serial) take the pass, and the records are made scheme 2's
+    const PeeWs& L = C.L;
+    hipStream_t st = C.st;
+    if (p0s1) {   // (the callee enters the workspace registry)
         rc = codec_pee_embed_ts(P, cover, stego, payload, lengths, nullptr, metas, lm, workspace, workspace_bytes,
                                 stream);
         if (rc) return rc;
@@ -4834,7 +4851,6 @@ int codec_pee_multi_embed_pass(const codec_pee_params* P, int32_t pass, const vo
         LAUNCH_CHECK("k_pee_pass0_fix");
         return 0;
     }
-    HIP_TRY(pee_ws_enter(workspace, P, L, st));
     uint32_t* cnt = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + L.cnt);
     uint32_t* off = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + L.off);
     if (cover != stego)   // the pass runs in place on the stego
@@ -4845,23 +4861,26 @@ int codec_pee_multi_embed_pass(const codec_pee_params* P, int32_t pass, const vo
     dim3 grid(gx, P->B);
     {
         ProfScope prof(st, CODEC_K_PEE_LAT_COUNT);
-#define PLC(TT) hipLaunchKernelGGL(k_pee_lat_count<TT>, grid, dim3(256), 0, st, static_cast<const TT*>(stego), P->H, P->W, \
-                                   (int)pass, P->T, P->maxval, lengths, metas, (int)pass, P->B, cnt, L.ntiles_max)
-        if (P->bytes == 2) PLC(uint16_t); else PLC(uint8_t);
-#undef PLC
+        pee_pixel(P->bytes, [&](auto px) {
+            using TT = decltype(px);
+            hipLaunchKernelGGL(k_pee_lat_count<TT>, grid, dim3(256), 0, st, static_cast<const TT*>(stego), P->H, P->W,
+                               (int)pass, P->T, P->maxval, lengths, metas, (int)pass, P->B, cnt, L.ntiles_max);
+        });
         LAUNCH_CHECK("k_pee_lat_count");
-#define PLL(TT) hipLaunchKernelGGL(k_pee_lat_locate<TT>, dim3(P->B), dim3(256), 0, st, static_cast<const TT*>(stego), P->H, \
-                                   P->W, (int)pass, P->T, P->maxval, lengths, metas, (int)pass, P->B, cnt, off, L.ntiles_max)
-        if (P->bytes == 2) PLL(uint16_t); else PLL(uint8_t);
-#undef PLL
+        pee_pixel(P->bytes, [&](auto px) {
+            using TT = decltype(px);
+            hipLaunchKernelGGL(k_pee_lat_locate<TT>, dim3(P->B), dim3(256), 0, st, static_cast<const TT*>(stego), P->H,
+                               P->W, (int)pass, P->T, P->maxval, lengths, metas, (int)pass, P->B, cnt, off, L.ntiles_max);
+        });
         LAUNCH_CHECK("k_pee_lat_locate");
     }
     ProfScope prof(st, CODEC_K_PEE_LAT_EMBED);
-#define PLE(TT) hipLaunchKernelGGL(k_pee_lat_embed<TT>, grid, dim3(256), 0, st, static_cast<TT*>(stego), P->H, P->W, \
-                                   (int)pass, reinterpret_cast<const u64*>(payload), P->payload_words, off, L.ntiles_max, \
-                                   metas, (int)pass, P->B, reinterpret_cast<u64*>(lm), P->lm_words)
-    if (P->bytes == 2) PLE(uint16_t); else PLE(uint8_t);
-#undef PLE
+    pee_pixel(P->bytes, [&](auto px) {
+        using TT = decltype(px);
+        hipLaunchKernelGGL(k_pee_lat_embed<TT>, grid, dim3(256), 0, st, static_cast<TT*>(stego), P->H, P->W, (int)pass,
+                           reinterpret_cast<const u64*>(payload), P->payload_words, off, L.ntiles_max, metas, (int)pass,
+                           P->B, reinterpret_cast<u64*>(lm), P->lm_words);
+    });
     LAUNCH_CHECK("k_pee_lat_embed");
     return 0;
 }
@@ -4869,14 +4888,12 @@ int codec_pee_multi_embed_pass(const codec_pee_params* P, int32_t pass, const vo
 int codec_pee_multi_extract_pass(const codec_pee_params* P, int32_t pass, const void* stego,
                                  const codec_pee_meta* metas, const uint64_t* lm, void* cover_out,
                                  uint64_t* payload_out, void* workspace, size_t workspace_bytes, void* stream) {
-    int rc = pee_multi_check(P, pass);
+    PeeCall C;
+    int rc = pee_begin(&C, P, pee_multi_check(P, pass), !stego || !metas || !lm || !cover_out || !payload_out || !workspace,
+                       "codec_pee_multi_extract_pass", pee_no_more, workspace, workspace_bytes, stream, PEE_ENTER);
     if (rc) return rc;
-    if (!stego || !metas || !lm || !cover_out || !payload_out || !workspace)
-        return set_err(CODEC_EINVAL, "codec_pee_multi_extract_pass: NULL pointer argument");
-    const PeeWs L = pee_ws(P);
-    if (workspace_bytes < L.total) return set_err(CODEC_EINVAL, "workspace too small");
-    hipStream_t st = as_stream(stream);
-    HIP_TRY(pee_ws_enter(workspace, P, L, st));
+    const PeeWs& L = C.L;
+    hipStream_t st = C.st;
     uint32_t* cnt = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + L.cnt);
     uint32_t* off = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + L.off);
     if (cover_out != stego)   // the pass runs in place on cover_out
@@ -4887,21 +4904,23 @@ int codec_pee_multi_extract_pass(const codec_pee_params* P, int32_t pass, const 
     dim3 grid(gx, P->B);
     {
         ProfScope prof(st, CODEC_K_PEE_LAT_DCOUNT);
-#define PLD(TT) hipLaunchKernelGGL(k_pee_lat_dcount<TT>, grid, dim3(256), 0, st, static_cast<const TT*>(cover_out), P->H, \
-                                   P->W, (int)pass, metas, (int)pass, P->B, reinterpret_cast<const u64*>(lm), P->lm_words, \
-                                   cnt, L.ntiles_max)
-        if (P->bytes == 2) PLD(uint16_t); else PLD(uint8_t);
-#undef PLD
+        pee_pixel(P->bytes, [&](auto px) {
+            using TT = decltype(px);
+            hipLaunchKernelGGL(k_pee_lat_dcount<TT>, grid, dim3(256), 0, st, static_cast<const TT*>(cover_out), P->H,
+                               P->W, (int)pass, metas, (int)pass, P->B, reinterpret_cast<const u64*>(lm), P->lm_words,
+                               cnt, L.ntiles_max);
+        });
         LAUNCH_CHECK("k_pee_lat_dcount");
         hipLaunchKernelGGL(k_pee_offsets, dim3(P->B), dim3(256), 0, st, metas + (size_t)pass * P->B, cnt, off, L.ntiles_max);
         LAUNCH_CHECK("k_pee_offsets");
     }
     ProfScope prof(st, CODEC_K_PEE_LAT_RECOVER);
-#define PLR(TT) hipLaunchKernelGGL(k_pee_lat_recover<TT>, grid, dim3(256), 0, st, static_cast<TT*>(cover_out), P->H, P->W, \
-                                   (int)pass, metas, (int)pass, P->B, reinterpret_cast<const u64*>(lm), P->lm_words, off, \
-                                   L.ntiles_max, reinterpret_cast<u64*>(payload_out), P->payload_words)
-    if (P->bytes == 2) PLR(uint16_t); else PLR(uint8_t);
-#undef PLR
+    pee_pixel(P->bytes, [&](auto px) {
+        using TT = decltype(px);
+        hipLaunchKernelGGL(k_pee_lat_recover<TT>, grid, dim3(256), 0, st, static_cast<TT*>(cover_out), P->H, P->W,
+                           (int)pass, metas, (int)pass, P->B, reinterpret_cast<const u64*>(lm), P->lm_words, off,
+                           L.ntiles_max, reinterpret_cast<u64*>(payload_out), P->payload_words);
+    });
     LAUNCH_CHECK("k_pee_lat_recover");
     return 0;
 }
@@ -4915,10 +4934,7 @@ static bool pee_multi_use_ss(const codec_pee_params* P) {
     const long long k = knob("CODEC_PEE_LAT_SS", -1);
     if (k == 0) return false;
     if (k == 1) return true;
-    const long long ncu = device_cu_count();
-    if (P->B < ncu) return false;
-    const long long rounds = (P->B + ncu - 1) / ncu;
-    if ((double)P->B / (double)(rounds * ncu) < 0.85) return false;
+    if (!pee_fills_chip(P->B)) return false;
     return (long long)P->H * P->W <= knob("CODEC_PEE_LAT_SS_MAXPX", 1LL << 20);
 }
 // 0: in place (no copy); 1: 16-B vector copy; 2: element copy (unaligned or ragged slices)
@@ -4927,17 +4943,37 @@ static int pee_lss_copy_mode(const codec_pee_params* P, const void* s, const voi
     const size_t sb = (size_t)P->H * P->W * P->bytes;
     return (sb % 16 == 0 && (uintptr_t)s % 16 == 0 && (uintptr_t)d % 16 == 0) ? 1 : 2;
 }
+// k_pee_lat_ss<TT, EXTRACT, payload in LDS, prefetch>, one launch for the embed and the extract
+// (the extract's payload and map are written / read through the same parameters).  The
+// no-prefetch A/B instantiation (CODEC_PEE_LAT_SS_PF=0) exists for uint16_t with the payload
+// staged in LDS only: elsewhere the knob is ignored
+template <bool EXTRACT>
+static void pee_lss_launch(const codec_pee_params* P, hipStream_t st, const void* src, void* dst, int cm, int p0_done,
+                           u64* payload, const int32_t* lengths, codec_pee_meta* metas, u64* lm, char* sink) {
+    const bool pl = P->payload_words <= LSS_PAY_MAXW && knob("CODEC_PEE_LAT_SS_PL", 1) != 0;
+    const bool pf = knob("CODEC_PEE_LAT_SS_PF", 1) != 0 || !pl;
+    pee_pixel(P->bytes, [&](auto px) {
+        using TT = decltype(px);
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3((unsigned)P->B), dim3(LSS_THREADS), 0, st, static_cast<const TT*>(src),
+                               static_cast<TT*>(dst), P->H, P->W, P->T, P->maxval, cm, p0_done, payload, P->payload_words,
+                               lengths, metas, P->B, lm, P->lm_words, sink);
+        };
+        if constexpr (std::is_same_v<TT, uint16_t>)
+            if (!pf) return go(k_pee_lat_ss<TT, EXTRACT, true, false>);
+        pee_flag(pl, [&](auto plv) { go(k_pee_lat_ss<TT, EXTRACT, plv(), true>); });
+    });
+}
 
 extern "C" {
 
 int codec_pee_multi_embed(const codec_pee_params* P, const void* cover, void* stego, const uint64_t* payload,
                           const int32_t* lengths, codec_pee_meta* metas, uint64_t* lm, void* workspace,
                           size_t workspace_bytes, void* stream) {
-    int rc = pee_multi_check(P, 0);
+    PeeCall C;   // the callees (pass calls, scheme 1's embed) enter the workspace registry
+    int rc = pee_begin(&C, P, pee_multi_check(P, 0), !cover || !stego || !payload || !lengths || !metas || !lm || !workspace,
+                       "codec_pee_multi_embed", pee_no_more, workspace, workspace_bytes, stream, PEE_NO_ENTER);
     if (rc) return rc;
-    if (!cover || !stego || !payload || !lengths || !metas || !lm || !workspace)
-        return set_err(CODEC_EINVAL, "codec_pee_multi_embed: NULL pointer argument");
-    if (workspace_bytes < pee_ws(P).total) return set_err(CODEC_EINVAL, "workspace too small");
     const size_t lmp = (size_t)P->B * P->lm_words;   // one pass's map
     if (!pee_multi_use_ss(P)) {
         for (int p = 0; p < 4; ++p) {
@@ -4947,7 +4983,6 @@ int codec_pee_multi_embed(const codec_pee_params* P, const void* cover, void* st
         }
         return 0;
     }
-    hipStream_t st = as_stream(stream);
     // pass 0 through scheme 1's kernels (copy fused) unless CODEC_PEE_LAT_SS_P0=0, which runs the
     // copy and all four passes in the one slice-serial launch
     const bool p0s1 = knob("CODEC_PEE_LAT_SS_P0", 1) != 0 && knob("CODEC_PEE_MULTI_P0", 1) != 0;
@@ -4957,25 +4992,9 @@ int codec_pee_multi_embed(const codec_pee_params* P, const void* cover, void* st
         if (rc) return rc;
     }
     const int cm = p0s1 ? 0 : pee_lss_copy_mode(P, cover, stego);
-    ProfScope prof(st, CODEC_K_PEE_LAT_SS_EMBED);
-    char* sink = static_cast<char*>(workspace) + pee_ws(P).sink;
-    const bool pl = P->payload_words <= LSS_PAY_MAXW && knob("CODEC_PEE_LAT_SS_PL", 1) != 0;
-#define PLSE(TT, PLV) hipLaunchKernelGGL((k_pee_lat_ss<TT, false, PLV, true>), dim3((unsigned)P->B), dim3(LSS_THREADS), 0, st, \
-                                    static_cast<const TT*>(cover), static_cast<TT*>(stego), P->H, P->W, P->T, P->maxval, cm, \
-                                    p0s1 ? 1 : 0, const_cast<u64*>(reinterpret_cast<const u64*>(payload)), P->payload_words, \
-                                    lengths, metas, P->B, reinterpret_cast<u64*>(lm), P->lm_words, sink)
-    // the no-prefetch A/B instantiation stages the payload in LDS: only where it fits (pl)
-    const bool pf = knob("CODEC_PEE_LAT_SS_PF", 1) != 0 || !pl;
-    if (P->bytes == 2) {
-        if (!pf) hipLaunchKernelGGL((k_pee_lat_ss<uint16_t, false, true, false>), dim3((unsigned)P->B), dim3(LSS_THREADS), 0,
-                                    st, static_cast<const uint16_t*>(cover), static_cast<uint16_t*>(stego), P->H, P->W, P->T,
-                                    P->maxval, cm, p0s1 ? 1 : 0, const_cast<u64*>(reinterpret_cast<const u64*>(payload)),
-                                    P->payload_words, lengths, metas, P->B, reinterpret_cast<u64*>(lm), P->lm_words, sink);
-        else if (pl) PLSE(uint16_t, true);
-        else PLSE(uint16_t, false);
-    }
-    else { if (pl) PLSE(uint8_t, true); else PLSE(uint8_t, false); }
-#undef PLSE
+    ProfScope prof(C.st, CODEC_K_PEE_LAT_SS_EMBED);
+    pee_lss_launch<false>(P, C.st, cover, stego, cm, p0s1 ? 1 : 0, const_cast<u64*>(reinterpret_cast<const u64*>(payload)),
+                          lengths, metas, reinterpret_cast<u64*>(lm), static_cast<char*>(workspace) + C.L.sink);
     LAUNCH_CHECK("k_pee_lat_ss<embed>");
     return 0;
 }
@@ -4983,12 +5002,11 @@ int codec_pee_multi_embed(const codec_pee_params* P, const void* cover, void* st
 int codec_pee_multi_extract(const codec_pee_params* P, const void* stego, const codec_pee_meta* metas,
                             const uint64_t* lm, void* cover_out, uint64_t* payload_out, void* workspace,
                             size_t workspace_bytes, void* stream) {
-    int rc = pee_multi_check(P, 0);
+    PeeCall C;   // the pass calls enter the workspace registry; the slice-serial launch keeps no state
+    int rc = pee_begin(&C, P, pee_multi_check(P, 0), !stego || !metas || !lm || !cover_out || !payload_out || !workspace,
+                       "codec_pee_multi_extract", pee_no_more, workspace, workspace_bytes, stream, PEE_NO_ENTER);
     if (rc) return rc;
-    if (!stego || !metas || !lm || !cover_out || !payload_out || !workspace)
-        return set_err(CODEC_EINVAL, "codec_pee_multi_extract: NULL pointer argument");
-    if (workspace_bytes < pee_ws(P).total) return set_err(CODEC_EINVAL, "workspace too small");
-    hipStream_t st = as_stream(stream);
+    hipStream_t st = C.st;
     const size_t lmp = (size_t)P->B * P->lm_words;
     if (!pee_multi_use_ss(P)) {
         HIP_TRY(hipMemsetAsync(payload_out, 0, (size_t)P->B * P->payload_words * 8, st));
@@ -5001,22 +5019,9 @@ int codec_pee_multi_extract(const codec_pee_params* P, const void* stego, const 
     }
     const int cm = pee_lss_copy_mode(P, stego, cover_out);
     ProfScope prof(st, CODEC_K_PEE_LAT_SS_EXTRACT);
-    char* sink = static_cast<char*>(workspace) + pee_ws(P).sink;
-    const bool pl = P->payload_words <= LSS_PAY_MAXW && knob("CODEC_PEE_LAT_SS_PL", 1) != 0;
-#define PLSX(TT, PLV, PFV) hipLaunchKernelGGL((k_pee_lat_ss<TT, true, PLV, PFV>), dim3((unsigned)P->B), dim3(LSS_THREADS), 0, st, \
-                                    static_cast<const TT*>(stego), static_cast<TT*>(cover_out), P->H, P->W, P->T, P->maxval, cm, \
-                                    0, reinterpret_cast<u64*>(payload_out), P->payload_words, nullptr, \
-                                    const_cast<codec_pee_meta*>(metas), P->B, const_cast<u64*>(reinterpret_cast<const u64*>(lm)), \
-                                    P->lm_words, sink)
-    const bool pf = knob("CODEC_PEE_LAT_SS_PF", 1) != 0 || !pl;   // as codec_pee_multi_embed
-    if (P->bytes == 2) {
-        if (!pf) PLSX(uint16_t, true, false);
-        else if (pl) PLSX(uint16_t, true, true);
-        else PLSX(uint16_t, false, true);
-    } else {
-        if (pl) PLSX(uint8_t, true, true); else PLSX(uint8_t, false, true);
-    }
-#undef PLSX
+    pee_lss_launch<true>(P, st, stego, cover_out, cm, 0, reinterpret_cast<u64*>(payload_out), nullptr,
+                         const_cast<codec_pee_meta*>(metas), const_cast<u64*>(reinterpret_cast<const u64*>(lm)),
+                         static_cast<char*>(workspace) + C.L.sink);
     LAUNCH_CHECK("k_pee_lat_ss<extract>");
     return 0;
 }
@@ -5030,26 +5035,28 @@ int codec_pee_multi_embed_auto(const codec_pee_params* P, const void* cover, voi
         return set_err(CODEC_EINVAL, "codec_pee_multi_embed_auto: need 1 <= tmin <= tmax <= 64");
     codec_pee_params Q = *P;   // P->T is ignored: the kernel scans tmin..tmax
     Q.T = tmin;
-    int rc = pee_multi_check(&Q, 0);
+    PeeCall C;   // the kernel keeps no state in the workspace: the registry is not entered
+    int rc = pee_begin(&C, &Q, pee_multi_check(&Q, 0),
+                       !cover || !stego || !payload || !lengths || !t_out || !metas || !lm || !workspace,
+                       "codec_pee_multi_embed_auto", [&] {
+        return cover == stego ? set_err(CODEC_EINVAL, "codec_pee_multi_embed_auto: out of place only (a failed trial "
+                                                      "is undone from the cover)") : 0;
+    }, workspace, workspace_bytes, stream, PEE_NO_ENTER);
     if (rc) return rc;
-    if (!cover || !stego || !payload || !lengths || !t_out || !metas || !lm || !workspace)
-        return set_err(CODEC_EINVAL, "codec_pee_multi_embed_auto: NULL pointer argument");
-    if (cover == stego)
-        return set_err(CODEC_EINVAL, "codec_pee_multi_embed_auto: out of place only (a failed trial is undone from the cover)");
-    const PeeWs L = pee_ws(&Q);
-    if (workspace_bytes < L.total) return set_err(CODEC_EINVAL, "workspace too small");
-    hipStream_t st = as_stream(stream);
+    hipStream_t st = C.st;
     const int cm = pee_lss_copy_mode(&Q, cover, stego);
-    char* sink = static_cast<char*>(workspace) + L.sink;
+    char* sink = static_cast<char*>(workspace) + C.L.sink;
     const bool pl = Q.payload_words <= LSS_PAY_MAXW;
     ProfScope prof(st, CODEC_K_PEE_LAT_AUTO);
-#define PLA(TT, PLV) hipLaunchKernelGGL((k_pee_lat_auto<TT, PLV>), dim3((unsigned)Q.B), dim3(LSS_THREADS), 0, st, \
-                                   static_cast<const TT*>(cover), static_cast<TT*>(stego), Q.H, Q.W, (int)tmin, (int)tmax, \
-                                   Q.maxval, cm, reinterpret_cast<const u64*>(payload), Q.payload_words, lengths, metas, \
-                                   Q.B, reinterpret_cast<u64*>(lm), Q.lm_words, t_out, sink)
-    if (Q.bytes == 2) { if (pl) PLA(uint16_t, true); else PLA(uint16_t, false); }
-    else { if (pl) PLA(uint8_t, true); else PLA(uint8_t, false); }
-#undef PLA
+    pee_pixel(Q.bytes, [&](auto px) {
+        using TT = decltype(px);
+        pee_flag(pl, [&](auto plv) {
+            hipLaunchKernelGGL((k_pee_lat_auto<TT, plv()>), dim3((unsigned)Q.B), dim3(LSS_THREADS), 0, st,
+                               static_cast<const TT*>(cover), static_cast<TT*>(stego), Q.H, Q.W, (int)tmin, (int)tmax,
+                               Q.maxval, cm, reinterpret_cast<const u64*>(payload), Q.payload_words, lengths, metas, Q.B,
+                               reinterpret_cast<u64*>(lm), Q.lm_words, t_out, sink);
+        });
+    });
     LAUNCH_CHECK("k_pee_lat_auto");
     return 0;
 }
