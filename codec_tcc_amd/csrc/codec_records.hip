@@ -24,13 +24,16 @@ constexpr int REC_HDR = CODEC_PEE_RECORD_HDR_WORDS;   // codec_pee_meta, in uint
 static_assert(sizeof(codec_pee_meta) == REC_HDR * 8, "codec_pee_meta must be 8 words");
 
 __device__ __forceinline__ int dense_words_of(int end, int lm_words) {
-    const int dw = (end + 64) >> 6;   // ceil((end + 1) / 64); end >= -1
-    return dw < 0 ? 0 : (dw > lm_words ? lm_words : dw);
+    if (end < 0) return 0;                // end < -1 counts as -1
+    const int dw = (end >> 6) + 1;        // ceil((end + 1) / 64), no overflow at end = INT_MAX
+    return dw > lm_words ? lm_words : dw;
 }
 
-__device__ __forceinline__ u64 end_mask(int end) {   // bits 0 .. end % 64 of end's word
+// The mask of the prefix's last word, dense_words_of(end, lm_words) - 1: bits 0 .. end % 64 when
+// that is end's own word, every bit when `end` lies past the map (no bit of the map is past it).
+__device__ __forceinline__ u64 end_mask(int end, int lm_words) {
     const int r = end & 63;
-    return r == 63 ? ~0ull : ((1ull << (r + 1)) - 1ull);
+    return (r == 63 || (end >> 6) >= lm_words) ? ~0ull : ((1ull << (r + 1)) - 1ull);
 }
 
 __global__ __launch_bounds__(REC_NT) void k_pee_pack_records(const codec_pee_meta* __restrict__ meta,
@@ -43,7 +46,7 @@ __global__ __launch_bounds__(REC_NT) void k_pee_pack_records(const codec_pee_met
     if (tid < REC_HDR) r[tid] = m[tid];
     const int end = meta[b].end, cnt = meta[b].lm_count;
     const int dw = dense_words_of(end, lm_words);
-    const u64 last = end_mask(end);
+    const u64 last = end_mask(end, lm_words);
     const u64* row = lm + (size_t)b * lm_words;
     u64* pay = r + REC_HDR;
     if (cnt >= 0 && cnt <= 2 * width) {

@@ -411,6 +411,7 @@ int codec_pee_multi_extract(const codec_pee_params* P, const void* stego, const 
  *          ascending, as uint32 (two per word), unused slots zero;
  *   dense  (otherwise): map words 0 .. width-1 with every bit past `end` zero.
  * Slice b's map travels exactly when width >= min(ceil(lm_count / 2), ceil((end + 1) / 64)).
+ * An `end` past the map (end >= 64 * lm_words) clears nothing, and end < -1 counts as -1.
  * meta/lm: codec_pee_embed outputs ([B], [B][lm_words]); records: [B][HDR + width]. */
 #define CODEC_PEE_RECORD_HDR_WORDS 8
 /* set in a packed record's meta.flags when the map held fewer set bits in [0, end] than
