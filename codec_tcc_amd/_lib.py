@@ -1,5 +1,5 @@
 """ctypes binding of libcodec_hip.so (include/codec_tcc.h, include/codec_tcc_ext.h,
-include/codec_tcc_crc.h, include/codec_tcc_vol.h).
+include/codec_tcc_crc.h, include/codec_tcc_vol.h, include/codec_tcc_gate.h, include/codec_tcc_gvol.h).
 
 The library is built in-tree (codec_tcc_amd/libcodec_hip.so, see build.py).  There is no
 CPU fallback: if the library cannot be loaded, every entry point raises RuntimeError.
@@ -138,7 +138,7 @@ KERNEL_TAGS = {1: "k_scan_fast", 2: "k_scan_generic", 3: "k_block_exact", 4: "k_
                29: "k_pee_lat_count", 30: "k_pee_lat_embed", 31: "k_pee_lat_dcount", 32: "k_pee_lat_recover",
                33: "k_pee_lat_ss_embed", 34: "k_pee_lat_ss_extract", 35: "k_pee_lat_auto",
                36: "k_crc32", 37: "k_crc32_combine", 38: "k_vol_plan", 39: "k_vol_scatter", 40: "k_vol_gather",
-               41: "k_pee_gate_table"}
+               41: "k_pee_gate_table", 42: "k_gvol_plan"}
 EXPORTS = tuple(_SIGS)
 # include/codec_tcc_ext.h: entries added after codec_tcc.h's list (EXPORTS) was fixed
 _SIGS_EXT = {
@@ -192,6 +192,27 @@ _SIGS_GATE = {
 }
 EXPORTS_GATE = tuple(_SIGS_GATE)
 
+
+class PeeGvolInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("T", C.c_int32), ("total", C.c_int32), ("requested", C.c_int32),
+                ("capacity", C.c_int32), ("policy", C.c_int32), ("B", C.c_int32), ("tmax", C.c_int32),
+                ("gate", C.c_int32), ("reserved", C.c_int32)]
+
+
+PEE_GVOL_INFO_BYTES = C.sizeof(PeeGvolInfo)
+# include/codec_tcc_gvol.h: gated volume payloads (pee.py embed_volume(gate=...))
+_SIGS_GVOL = {
+    "codec_pee_gvol_workspace_bytes": (C.c_size_t, [C.POINTER(PeeParams), C.c_int32]),
+    "codec_pee_gvol_plan": (C.c_int, [C.POINTER(PeeParams), _VP, _VP, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _VP,
+                                      _VP, _VP, _VP, _VP, _VP]),
+    "codec_pee_gvol_embed": (C.c_int, [C.POINTER(PeeParams), _VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                       _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP, C.c_size_t, _VP,
+                                       C.c_size_t, _VP]),
+    "codec_pee_gvol_extract": (C.c_int, [C.POINTER(PeeParams), _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP, _VP, C.c_size_t,
+                                         _VP, C.c_size_t, _VP]),
+}
+EXPORTS_GVOL = tuple(_SIGS_GVOL)
+
 _lib = None
 _load_error = None
 # -D flags of diagnostic builds (tools/): never the product library
@@ -219,7 +240,7 @@ def load(path: str = LIB_PATH):
     except OSError as e:  # pragma: no cover - environment specific
         _load_error = e
         raise RuntimeError(f"cannot load {path}: {e}") from e
-    for name, (res, args) in {**_SIGS, **_SIGS_EXT, **_SIGS_CRC, **_SIGS_VOL, **_SIGS_GATE}.items():
+    for name, (res, args) in {**_SIGS, **_SIGS_EXT, **_SIGS_CRC, **_SIGS_VOL, **_SIGS_GATE, **_SIGS_GVOL}.items():
         fn = getattr(lib, name, None)
         if fn is None:
             if name == "codec_build_digest" and not in_tree:   # a diagnostic build (tools/)

@@ -17,7 +17,9 @@ Volume payloads (scheme 1; include/codec_tcc_vol.h): one bitstream across the wh
     vol = codec.embed_volume(covers, payload, policy="even")   # device plan + cut + embed
     bits, covers = codec.decode_volume(vol)
 
-with the per-slice bit counts and T chosen on the device from the capacity curves.
+with the per-slice bit counts and T chosen on the device from the capacity curves.  With
+embed_volume(..., gate="auto") (or an integer gate; include/codec_tcc_gvol.h) the plan is over
+(T, G): the smoothness gate of PeeCodec(gate=...) chosen for the volume and again per slice.
 """
 from __future__ import annotations
 
@@ -237,6 +239,20 @@ def check_gate_args(gate, T, tmax: int, nc: int, scheme: int = 1) -> None:
         raise ValueError(f"{int(nc)} candidates per slice exceed the gated selection's 2^26")
 
 
+def check_gvol_args(codec_gate, gate, tmax: int, nc: int, scheme: int = 1) -> None:
+    """The argument rules of embed_volume's gate= keyword (include/codec_tcc_gvol.h), as
+    ValueError before any launch.  Pure host code: no GPU, no library load.  codec_gate: the
+    gate the codec itself was built with (must be None: a volume takes its gate per call)."""
+    if codec_gate is not None:
+        raise ValueError("volume payloads take an ungated codec: a codec built with gate= plans per slice "
+                         "(DESIGN §3f); build the codec without gate= and pass embed_volume(..., gate=) to plan "
+                         "a gated volume over (T, G) (DESIGN §3g)")
+    if gate is not None and int(scheme) != 1:
+        raise ValueError("volume payloads are scheme 1's: scheme 2 has no cover-side capacity to plan with "
+                         "(DESIGN §3b-2)")
+    check_gate_args(gate, "auto", tmax, nc, scheme)
+
+
 @dataclass
 class PeeVolume:
     """One bitstream embedded across a slice stack (PeeCodec.embed_volume).  enc is an ordinary
@@ -246,24 +262,31 @@ class PeeVolume:
     enc: PeeEncoded
     total_bits: int                   # the stream's bits (what was asked for)
     policy: str
-    plan: object                      # torch.int32 [3 B + 1] (device): n[B], T[B], off[B + 1]
-    info: object                      # torch.int32 [8] (device): codec_pee_volume_info
+    plan: object                      # torch.int32 [3 B + 1] (device): n[B], T[B], off[B + 1]; gated: + g[B]
+    info: object                      # torch.int32 [8] (device): codec_pee_volume_info; gated: [10], codec_pee_gvol_info
     payload_crc: Optional[int] = None   # CRC-32 of the whole stream (checksum.payload_crc32)
     embedded_bits: Optional[int] = None  # info.total, once read back (check=True): < total_bits when truncated
+    gate: object = None               # embed_volume's gate= (None: an ungated volume)
 
     def plan_host(self) -> dict:
-        """n, t, off (numpy) and the info record's fields: one read-back."""
+        """n, t, off (numpy) and the info record's fields: one read-back.  A gated volume adds
+        g (the slices' gate values) and gate (the volume's G*, or the fixed gate)."""
         torch = _torch()
         B = len(self.enc.lengths)
         both = torch.cat([self.plan.reshape(-1), self.info.reshape(-1)]).cpu().numpy()
-        return _plan_dict(both[:3 * B + 1], both[3 * B + 1:], B)
+        np_ = self.plan.numel()
+        return _plan_dict(both[:np_], both[np_:], B, gated=self.gate is not None)
 
 
-def _plan_dict(plan, info, B: int) -> dict:
-    i = _lib.PeeVolumeInfo.from_buffer_copy(np.ascontiguousarray(info, dtype=np.int32).tobytes())
-    return {"n": plan[:B].copy(), "t": plan[B:2 * B].copy(), "off": plan[2 * B:3 * B + 1].copy(),
-            "status": int(i.status), "T": int(i.T), "total": int(i.total), "requested": int(i.requested),
-            "capacity": int(i.capacity), "policy": {v: k for k, v in _lib.VOL_POLICIES.items()}[int(i.policy)]}
+def _plan_dict(plan, info, B: int, gated: bool = False) -> dict:
+    rec = _lib.PeeGvolInfo if gated else _lib.PeeVolumeInfo
+    i = rec.from_buffer_copy(np.ascontiguousarray(info, dtype=np.int32).tobytes())
+    d = {"n": plan[:B].copy(), "t": plan[B:2 * B].copy(), "off": plan[2 * B:3 * B + 1].copy(),
+         "status": int(i.status), "T": int(i.T), "total": int(i.total), "requested": int(i.requested),
+         "capacity": int(i.capacity), "policy": {v: k for k, v in _lib.VOL_POLICIES.items()}[int(i.policy)]}
+    if gated:
+        d["g"], d["gate"] = plan[3 * B + 1:4 * B + 1].copy(), int(i.gate)
+    return d
 
 
 class PeeCodec:
@@ -678,12 +701,36 @@ class PeeCodec:
         cache.move_to_end(key)
         return cache[key]
 
-    def volume_buffers(self):
+    def _gvol_workspace(self, payload_words: int, tmax: int):
+        """The gated volume workspace for this row pitch (offsets, payload rows, the slices'
+        tables), kept like _volume_workspace's."""
+        torch = _torch()
+        key = (int(payload_words), int(tmax))
+        cache = self.__dict__.setdefault("_gvol_ws", OrderedDict())
+        if key not in cache:
+            n = int(_lib.load().codec_pee_gvol_workspace_bytes(C.byref(self._params(payload_words)), tmax))
+            if n == 0:
+                _lib.check(-1, "codec_pee_gvol_workspace_bytes")
+            cache[key] = torch.empty(n, dtype=torch.uint8, device=self.device)
+            while len(cache) > 4:
+                cache.popitem(last=False)
+        cache.move_to_end(key)
+        return cache[key]
+
+    def _side_words(self, gated: bool):
+        """int32 words of the plan and of the info record in a volume's side buffer."""
+        if gated:
+            return 4 * self.B + 1, _lib.PEE_GVOL_INFO_BYTES // 4
+        return 3 * self.B + 1, _lib.PEE_VOLUME_INFO_BYTES // 4
+
+    def volume_buffers(self, gate: bool = False):
         """(lm, side) for embed_volume(..., buffers=): the location map and the one int32 buffer
-        that holds records, plan and info, so that a caller (a captured graph) can preallocate."""
+        that holds records, plan and info, so that a caller (a captured graph) can preallocate.
+        gate=True: the larger side buffer of a gated volume (the plan gains g[B], the info
+        record is codec_pee_gvol_info)."""
         torch = _torch()
         lm = torch.empty((self.B, self.lm_words), dtype=torch.int64, device=self.device)
-        side = torch.empty(self.B * _lib.PEE_META_BYTES // 4 + 3 * self.B + 1 + _lib.PEE_VOLUME_INFO_BYTES // 4,
+        side = torch.empty(self.B * _lib.PEE_META_BYTES // 4 + sum(self._side_words(bool(gate))),
                            dtype=torch.int32, device=self.device)
         return lm, side
 
@@ -695,7 +742,7 @@ class PeeCodec:
         return _torch().from_numpy(framing.pack_bits([bits])[0].reshape(-1)).to(self.device), int(bits.size)
 
     def embed_volume(self, covers, payload, *, policy: str = "even", stego=None, check: bool = True,
-                     checksum: bool = False, buffers=None, packed=None) -> "PeeVolume":
+                     checksum: bool = False, buffers=None, packed=None, gate=None) -> "PeeVolume":
         """One payload (str / bytes / 0-1 vector, framing.to_bits) embedded across the whole
         stack: the device plans how many bits each slice takes and at which T (the rule of
         include/codec_tcc_vol.h: policy "even" spreads the bits in proportion to the slices'
@@ -704,6 +751,13 @@ class PeeCodec:
         and embeds them -- capacity pass, plan, cut and embed are queued on the current stream,
         no host round trip.  tmax is the codec's; the T given at construction is
         ignored here.  Scheme 1 only.
+        gate: None (ungated, as ever), a smoothness gate 0..65535 or "auto" -- a gated volume
+        (include/codec_tcc_gvol.h; the codec itself is built without gate=).  "auto": the device
+        sums the slices' gated capacity tables, picks the volume's (T*, G*) by the per-slice
+        selection rule, shares the bits by the capacities at that pair and lets every slice
+        re-choose its own (T_b, G_b) for its share; an integer gate plans T alone under that
+        gate.  The records carry the gates, so every slice still decodes on its own.  Needs
+        tmax <= 16 and at most 2^26 candidates per slice; buffers: volume_buffers(gate=True).
         check=True (default): one read-back of records, plan and info fills enc.lengths and
         embedded_bits, raises RuntimeError if an in-place look-back gave up (the workspace is
         reset, as embed does); a payload beyond the volume's capacity at tmax is truncated to
@@ -715,9 +769,8 @@ class PeeCodec:
         packed: pack_volume()'s result instead of `payload` (no upload in the call; the payload
         CRC is then absent, as with embed's packed=)."""
         torch = _torch()
-        if self.gate is not None:
-            raise ValueError("volume payloads are ungated: planning a gated volume needs a plan over (T, G) "
-                             "(DESIGN §3f); use a codec without gate=")
+        check_gvol_args(self.gate, gate, self.tmax, self.nc, self.scheme)
+        gated = gate is not None
         if tuple(covers.shape) != (self.B, self.H, self.W) or _elem_bytes(covers) != self.bytes:
             raise ValueError("covers do not match the codec's shape/dtype")
         bits = framing.to_bits(payload) if packed is None else None
@@ -731,25 +784,38 @@ class PeeCodec:
         cover_crc = _ck.crc32_slices(covers) if checksum else None   # before an in-place embed
         if stego is None:
             stego = torch.empty_like(covers)
-        lm, side = buffers if buffers is not None else self.volume_buffers()
+        lm, side = buffers if buffers is not None else self.volume_buffers(gated)
         nm = self.B * _lib.PEE_META_BYTES // 4
+        npl, _ninfo = self._side_words(gated)
         if tuple(lm.shape) != (self.B, self.lm_words) or lm.element_size() != 8 or not lm.is_contiguous() or \
-                side.dim() != 1 or side.numel() != nm + 3 * self.B + 1 + _lib.PEE_VOLUME_INFO_BYTES // 4 or \
+                side.dim() != 1 or side.numel() != nm + npl + _ninfo or \
                 side.element_size() != 4 or not side.is_contiguous():
-            raise ValueError("buffers must be what volume_buffers() returns")
+            raise ValueError("buffers must be what volume_buffers() returns" + (" with gate=True" if gated else ""))
         meta = side[:nm].view(torch.uint8).view(self.B, _lib.PEE_META_BYTES)
-        plan, info = side[nm:nm + 3 * self.B + 1], side[nm + 3 * self.B + 1:]
-        vws = self._volume_workspace(pw, self.tmax)
+        plan, info = side[nm:nm + npl], side[nm + npl:]
         P = self._params(pw)
         n_ptr = plan.data_ptr()
-        self._guarded(lambda: _lib.check(_lib.load().codec_pee_volume_embed(
-            C.byref(P), covers.data_ptr(), stego.data_ptr(), words.data_ptr(), N, _lib.VOL_POLICIES[policy], self.tmax,
-            n_ptr, n_ptr + 4 * self.B, n_ptr + 8 * self.B, info.data_ptr(), meta.data_ptr(), lm.data_ptr(),
-            self.workspace.data_ptr(), self.workspace.numel(), vws.data_ptr(), vws.numel(), _stream()),
-            "codec_pee_volume_embed"))
+        if gated:   # table, plan over (T, G), cut and gated embed, queued on this stream
+            gws, tws = self._gvol_workspace(pw, self.tmax), self._table_workspace(self.tmax)
+            self._guarded(lambda: _lib.check(_lib.load().codec_pee_gvol_embed(
+                C.byref(P), covers.data_ptr(), stego.data_ptr(), words.data_ptr(), N, _lib.VOL_POLICIES[policy],
+                self.tmax, -1 if gate == "auto" else int(gate), n_ptr, n_ptr + 4 * self.B, n_ptr + 4 * (3 * self.B + 1),
+                n_ptr + 8 * self.B, info.data_ptr(), meta.data_ptr(), lm.data_ptr(), self.workspace.data_ptr(),
+                self.workspace.numel(), tws.data_ptr(), tws.numel(), gws.data_ptr(), gws.numel(), _stream()),
+                "codec_pee_gvol_embed"))
+        else:
+            vws = self._volume_workspace(pw, self.tmax)
+            self._guarded(lambda: _lib.check(_lib.load().codec_pee_volume_embed(
+                C.byref(P), covers.data_ptr(), stego.data_ptr(), words.data_ptr(), N, _lib.VOL_POLICIES[policy], self.tmax,
+                n_ptr, n_ptr + 4 * self.B, n_ptr + 8 * self.B, info.data_ptr(), meta.data_ptr(), lm.data_ptr(),
+                self.workspace.data_ptr(), self.workspace.numel(), vws.data_ptr(), vws.numel(), _stream()),
+                "codec_pee_volume_embed"))
+        config = dict(self.config, T="auto")
+        if gated:
+            config["gate"] = gate if isinstance(gate, str) else int(gate)
         enc = PeeEncoded(stego=stego, lm=lm, meta=meta, lengths=[0] * self.B, payload_words=pw,
-                         config=dict(self.config, T="auto"), cover_crc=cover_crc)
-        vol = PeeVolume(enc=enc, total_bits=N, policy=policy, plan=plan, info=info,
+                         config=config, cover_crc=cover_crc)
+        vol = PeeVolume(enc=enc, total_bits=N, policy=policy, plan=plan, info=info, gate=config.get("gate"),
                         payload_crc=_ck.payload_crc32(bits) if checksum and bits is not None else None)
         if check:
             host = side.cpu().numpy()   # records, plan and info: one read-back
@@ -758,7 +824,7 @@ class PeeCodec:
             if any(r.status not in (0, 1) for r in recs):
                 self.reset()
             _raise_lookback(recs)
-            p = _plan_dict(host[nm:nm + 3 * self.B + 1], host[nm + 3 * self.B + 1:], self.B)
+            p = _plan_dict(host[nm:nm + npl], host[nm + npl:], self.B, gated)
             enc.lengths = [int(v) for v in p["n"]]
             vol.embedded_bits = p["total"]
             if checksum and bits is not None and p["total"] < N:
@@ -789,12 +855,18 @@ class PeeCodec:
         sw = max(1, (int(vol.total_bits) + 63) // 64)
         out = torch.empty(sw + 1, dtype=torch.int64, device=self.device)   # the stream, then the total
         cover = torch.empty_like(enc.stego)
-        vws = self._volume_workspace(enc.payload_words, 1)
         P = self._params(enc.payload_words)
-        self._guarded(lambda: _lib.check(_lib.load().codec_pee_volume_extract(
+        # the gate is the records': a gated volume decodes on any scheme-1 codec of the shape
+        if any(int(r.reserved[1]) != 0 for r in recs):
+            fn, what = _lib.load().codec_pee_gvol_extract, "codec_pee_gvol_extract"
+            vws = self._gvol_workspace(enc.payload_words, 1)
+        else:
+            fn, what = _lib.load().codec_pee_volume_extract, "codec_pee_volume_extract"
+            vws = self._volume_workspace(enc.payload_words, 1)
+        self._guarded(lambda: _lib.check(fn(
             C.byref(P), enc.stego.data_ptr(), enc.meta.data_ptr(), enc.lm.data_ptr(), cover.data_ptr(), out.data_ptr(),
             sw, out.data_ptr() + 8 * sw, self.workspace.data_ptr(), self.workspace.numel(), vws.data_ptr(),
-            vws.numel(), _stream()), "codec_pee_volume_extract"))
+            vws.numel(), _stream()), what))
         self._cover_crc = _ck.crc32_slices(cover) if (mode is not None and have_c) else None
         host = out.cpu().numpy()
         if self.lookback_failed(enc.payload_words):
@@ -958,10 +1030,12 @@ def decode(enc: PeeEncoded, verify=True, *, restore: bool = True):
 
 
 def encode_volume(covers, payload, *, policy: str = "even", tmax: int = 16, maxval: Optional[int] = None,
-                  checksum: bool = False, scheme: int = 1) -> PeeVolume:
+                  checksum: bool = False, scheme: int = 1, gate=None) -> PeeVolume:
     """MED-PEE embed of ONE payload across a [B,H,W] stack (PeeCodec.embed_volume): the bits are
     spread over the slices on the device (policy "even": in proportion to capacity; "fill": in
-    slice order), each slice at the smallest T <= tmax that holds its share.  Raises ValueError
+    slice order), each slice at the smallest T <= tmax that holds its share.  gate: a smoothness
+    gate 0..65535 or "auto" -- a gated volume, planned over (T, G) (PeeCodec.embed_volume);
+    decode_volume() reads the gates from the records.  Raises ValueError
     when the volume cannot hold the payload at tmax, as encode() does per slice; argument errors
     (policy, scheme 2, more than 2^31 - 1 bits or candidates, a shape that is no stack) are
     ValueError before the GPU is touched."""
@@ -969,11 +1043,12 @@ def encode_volume(covers, payload, *, policy: str = "even", tmax: int = 16, maxv
     shape = tuple(covers.shape)
     bits = framing.to_bits(payload)
     check_volume_args(shape if len(shape) != 2 else (1,) + shape, bits.size, policy, scheme)
+    check_gvol_args(None, gate, tmax, (int(shape[-2]) // 2) * (int(shape[-1]) // 2), scheme)
     _require_gpu()
     covers = _as_batch(covers)
     dt = "uint16" if _elem_bytes(covers) == 2 else "uint8"
     codec = _codec_for(tuple(covers.shape), dt, T="auto", tmax=tmax, maxval=maxval)
-    vol = codec.embed_volume(covers, bits, policy=policy, checksum=checksum)
+    vol = codec.embed_volume(covers, bits, policy=policy, checksum=checksum, gate=gate)
     if vol.embedded_bits < vol.total_bits:
         raise ValueError(f"payload of {vol.total_bits} bits exceeds the volume's PEE capacity "
                          f"{vol.embedded_bits} (tmax={tmax})")
