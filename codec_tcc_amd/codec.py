@@ -232,16 +232,31 @@ class Codec:
             setattr(P, k, v)
         return P
 
-    def _check_pixels(self, t, nbytes):
+    def _check_device(self, t, name):
         torch = _torch()
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise TypeError("pixels must be a CUDA/ROCm torch tensor")
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a CUDA/ROCm torch tensor on {self.device}, got {type(t).__name__}")
+        if t.device != self.device and not (self.device.index is None and t.device.type == self.device.type):
+            raise TypeError(f"{name} is on {t.device}, the codec is on {self.device}")
+
+    def _check_pixels(self, t, nbytes, name="pixels"):
+        """The library sees a pointer and (B, H, W, bytes): a dense block on the codec's device
+        (at any storage offset) or an error before the launch."""
+        self._check_device(t, name)
         if tuple(t.shape) != (self.B, self.H, self.W):
-            raise ValueError(f"expected shape {(self.B, self.H, self.W)}, got {tuple(t.shape)}")
+            raise ValueError(f"{name}: expected shape {(self.B, self.H, self.W)}, got {tuple(t.shape)}")
         if _elem_bytes(t) != nbytes:
-            raise TypeError(f"expected {nbytes}-byte pixels, got {t.dtype}")
+            raise TypeError(f"{name}: expected {nbytes}-byte pixels, got {t.dtype}")
         if not t.is_contiguous():
-            raise ValueError("pixel tensor must be contiguous")
+            raise ValueError(f"{name}: the pixel tensor must be contiguous, got strides {tuple(t.stride())}")
+
+    def _check_rows(self, t, name, esize, words):
+        """A side buffer the library indexes as B rows of `words` elements of `esize` bytes."""
+        self._check_device(t, name)
+        pitch_ok = self.B == 1 or t.dim() != 2 or t.shape[1] == int(words)   # rows are `words` apart
+        if t.element_size() != esize or not t.is_contiguous() or t.numel() < self.B * int(words) or not pitch_ok:
+            raise ValueError(f"{name} must be contiguous and hold [B, {int(words)}] = [{self.B}, {int(words)}] "
+                             f"{esize}-byte elements, got shape {tuple(t.shape)}, strides {tuple(t.stride())}, {t.dtype}")
 
     # -- encode: codec_encode (= codec_plan + codec_embed, fused when the dtypes allow)
     def encode(self, covers, payloads, *, stego=None, maps=None, meta=None, check: bool = True) -> Encoded:
@@ -249,7 +264,11 @@ class Codec:
         slice's decision is not the reference's (check_status); check=False keeps the call
         asynchronous (benchmarks, graph capture) -- inspect enc.records() afterwards."""
         torch = _torch()
-        self._check_pixels(covers, self.in_bytes)
+        self._check_pixels(covers, self.in_bytes, "covers")
+        if stego is not None:
+            self._check_pixels(stego, self.out_bytes, "stego")
+        if meta is not None:
+            self._check_rows(meta, "meta", 1, _lib.META_BYTES)
         pl = payloads if isinstance(payloads, Payloads) else make_payloads(payloads, self.device)
         if len(pl.lengths) != self.B:
             raise ValueError("one payload per slice is required")
@@ -258,6 +277,8 @@ class Codec:
             stego = _padded_empty((self.B, self.H, self.W), _pix_dtype(self.out_bytes), self.device)
         if maps is None:
             maps = torch.empty((self.B, pl.map_words), dtype=torch.int64, device=self.device)
+        else:
+            self._check_rows(maps, "maps", 8, pl.map_words)
         if meta is None:
             meta = torch.empty((self.B, _lib.META_BYTES), dtype=torch.uint8, device=self.device)
         lib = _lib.load()
@@ -291,12 +312,18 @@ class Codec:
     def decode(self, stego, maps, meta, *, payload_words: int, map_words: int, restore: bool = True,
                cover=None, payload=None):
         torch = _torch()
-        self._check_pixels(stego, self.out_bytes)
+        self._check_pixels(stego, self.out_bytes, "stego")
+        self._check_rows(maps, "maps", 8, map_words)
+        self._check_rows(meta, "meta", 1, _lib.META_BYTES)
         P = self._params(None, payload_words=int(payload_words), map_words=int(map_words))
         if restore and cover is None:
             cover = torch.empty((self.B, self.H, self.W), dtype=_pix_dtype(self.out_bytes), device=self.device)
+        elif restore:
+            self._check_pixels(cover, self.out_bytes, "cover")
         if payload is None:
             payload = torch.empty((self.B, int(payload_words)), dtype=torch.int64, device=self.device)
+        else:
+            self._check_rows(payload, "payload", 8, payload_words)
         lib = _lib.load()
         _lib.check(lib.codec_extract(C.byref(P), stego.data_ptr(), maps.data_ptr(), meta.data_ptr(),
                                      cover.data_ptr() if restore else None, payload.data_ptr(), _stream()),

@@ -320,6 +320,8 @@ class PeeCodec:
         _require_gpu()
         torch = _torch()
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if self.device.type == "cuda" and self.device.index is None:   # "cuda": the current card, as tensors name it
+            self.device = torch.device("cuda", torch.cuda.current_device())
         nbytes = 2 if "16" in str(dtype) else 1
         if str(dtype) not in ("uint16", "torch.uint16", "uint8", "torch.uint8"):
             raise ValueError("A imagem deve ser uint8 ou uint16.")
@@ -386,6 +388,11 @@ class PeeCodec:
                 pass
             raise
 
+    def _check_buffers(self, **tensors):
+        """check_buffers() with this codec's device, shape and scheme."""
+        check_buffers(self.device, self.B, self.H, self.W, self.bytes, lm_words=self.lm_words, scheme=self.scheme,
+                      **tensors)
+
     def _params(self, payload_words: int) -> _lib.PeeParams:
         return _lib.PeeParams(B=self.B, H=self.H, W=self.W, bytes=self.bytes, T=self.T, maxval=self.maxval,
                               payload_words=int(payload_words), lm_words=self.lm_words)
@@ -424,8 +431,7 @@ class PeeCodec:
             raise ValueError("the smoothness gate is scheme 1's")
         tmax = self.tmax if tmax is None else int(tmax)
         check_gate_args(0 if gate is None else gate, 1, tmax, self.nc)
-        if tuple(covers.shape) != (self.B, self.H, self.W) or _elem_bytes(covers) != self.bytes:
-            raise ValueError("covers do not match the codec's shape/dtype")
+        self._check_buffers(covers=covers)
         n = torch.empty((self.B, 16), dtype=torch.int32, device=self.device)
         hs = torch.empty((self.B, tmax, 16), dtype=torch.int32, device=self.device)
         ws = self._table_workspace(tmax)
@@ -444,6 +450,7 @@ class PeeCodec:
         if gate is not None:
             _n, hs = self.gate_table(covers, tmax, gate)
             return hs[:, :, 0].cumsum(1).to(torch.int32)
+        self._check_buffers(covers=covers)
         caps = torch.empty((self.B, tmax), dtype=torch.int32, device=self.device)
         self._guarded(lambda: _lib.check(_lib.load().codec_pee_capacity(
             C.byref(self._params(1)), covers.data_ptr(), tmax, None, caps.data_ptr(), None, self.workspace.data_ptr(),
@@ -461,8 +468,12 @@ class PeeCodec:
         enc.payload_crc from the bits on the host (None with caller-packed `packed=` payloads:
         the bits are not here); decode(enc) then verifies both."""
         torch = _torch()
-        if tuple(covers.shape) != (self.B, self.H, self.W) or _elem_bytes(covers) != self.bytes:
-            raise ValueError("covers do not match the codec's shape/dtype")
+        # every buffer of the call, before anything is queued (the checksum launch included)
+        check_buffers(self.device, self.B, self.H, self.W, self.bytes, lm_words=self.lm_words, scheme=self.scheme,
+                      covers=covers, stego=stego, lm=lm, meta=meta, packed=packed)
+        if self.scheme == 2 and self.auto and stego is not None and _same_storage(covers, stego):
+            raise ValueError("scheme 2 with T='auto' embeds out of place only (a failed trial is undone from "
+                             "the cover): pass a stego buffer other than the covers")
         cover_crc = payload_crc = None
         if checksum:
             cover_crc = _ck.crc32_slices(covers)   # queued first: the host work below runs beside it
@@ -533,9 +544,6 @@ class PeeCodec:
         otherwise); pass 0 copies cover -> stego, the others run in place.  T="auto":
         codec_pee_multi_embed_auto, one launch that scans T per slice (out of place only)."""
         torch = _torch()
-        if self.auto and _same_storage(covers, stego):
-            raise ValueError("scheme 2 with T='auto' embeds out of place only (a failed trial is undone from "
-                             "the cover): pass a stego buffer other than the covers")
         if lm is None:
             lm = torch.empty((4, self.B, self.lm_words), dtype=torch.int64, device=self.device)
         if meta is None:
@@ -566,6 +574,8 @@ class PeeCodec:
         (reserved[1]; it reads ungated records too).  None: this codec's own setting; decode()
         passes what the records say."""
         torch = _torch()
+        check_buffers(self.device, self.B, self.H, self.W, self.bytes, lm_words=self.lm_words, scheme=self.scheme,
+                      stego=stego, cover=cover, lm=lm, meta=meta, payload=payload, payload_words=payload_words)
         if cover is None:
             cover = torch.empty_like(stego)
         if payload is None:
@@ -658,6 +668,7 @@ class PeeCodec:
         extract, before the payload read-back (self._cover_crc)."""
         if enc.scheme != self.scheme:
             raise ValueError(f"a scheme-{enc.scheme} embedding given to a scheme-{self.scheme} codec")
+        self._check_buffers(stego=enc.stego, lm=enc.lm, meta=enc.meta)   # before the records' read-back
         if self.scheme == 2:
             prs = enc.pass_records()   # one read-back serves the capacity test and the record check
             got = [sum(int(pr[b].L) for pr in prs) for b in range(len(enc.lengths))]
@@ -771,26 +782,31 @@ class PeeCodec:
         torch = _torch()
         check_gvol_args(self.gate, gate, self.tmax, self.nc, self.scheme)
         gated = gate is not None
-        if tuple(covers.shape) != (self.B, self.H, self.W) or _elem_bytes(covers) != self.bytes:
-            raise ValueError("covers do not match the codec's shape/dtype")
+        self._check_buffers(covers=covers, stego=stego)
         bits = framing.to_bits(payload) if packed is None else None
         N = int(bits.size) if packed is None else int(packed[1])
         check_volume_args((self.B, self.H, self.W), N, policy, self.scheme)
         pw = max(1, min((N + 63) // 64, self.lm_words))
+        nm = self.B * _lib.PEE_META_BYTES // 4
+        npl, _ninfo = self._side_words(gated)
+        # the caller's other buffers, judged like the pixels' before the upload and the checksum launch
+        if packed is not None:
+            if not _on_device(packed[0], self.device):
+                _bad_device("packed[0]", packed[0], self.device)
+            if packed[0].element_size() != 8 or packed[0].numel() < max(1, (N + 63) // 64) or not packed[0].is_contiguous():
+                raise ValueError("the packed stream (packed[0]) must hold ceil(bits / 64) contiguous 64-bit words")
+        if buffers is not None:
+            lm, side = buffers
+            if not _dense(lm, self.device, (self.B, self.lm_words), 8) or \
+                    not _dense(side, self.device, (nm + npl + _ninfo,), 4):
+                raise ValueError("buffers must be what volume_buffers() returns" + (" with gate=True" if gated else ""))
         words = packed[0] if packed is not None else \
             torch.from_numpy(framing.pack_bits([bits])[0].reshape(-1)).to(self.device)
-        if words.element_size() != 8 or words.numel() < max(1, (N + 63) // 64) or not words.is_contiguous():
-            raise ValueError("the packed stream must hold ceil(bits / 64) contiguous 64-bit words")
         cover_crc = _ck.crc32_slices(covers) if checksum else None   # before an in-place embed
         if stego is None:
             stego = torch.empty_like(covers)
-        lm, side = buffers if buffers is not None else self.volume_buffers(gated)
-        nm = self.B * _lib.PEE_META_BYTES // 4
-        npl, _ninfo = self._side_words(gated)
-        if tuple(lm.shape) != (self.B, self.lm_words) or lm.element_size() != 8 or not lm.is_contiguous() or \
-                side.dim() != 1 or side.numel() != nm + npl + _ninfo or \
-                side.element_size() != 4 or not side.is_contiguous():
-            raise ValueError("buffers must be what volume_buffers() returns" + (" with gate=True" if gated else ""))
+        if buffers is None:
+            lm, side = self.volume_buffers(gated)
         meta = side[:nm].view(torch.uint8).view(self.B, _lib.PEE_META_BYTES)
         plan, info = side[nm:nm + npl], side[nm + npl:]
         P = self._params(pw)
@@ -847,6 +863,7 @@ class PeeCodec:
             missing = [n for n, h in (("cover", have_c), ("payload", have_p)) if not h]
             raise _ck.IntegrityError(f"MED-PEE decode: verify='require' and the volume carries no "
                                      f"{' / '.join(missing)} checksum")
+        self._check_buffers(stego=enc.stego, lm=enc.lm, meta=enc.meta)   # before the records' read-back
         recs = enc.records()
         _raise_lookback(recs)
         _raise_status(recs, "volume, " + self._t_text())
@@ -920,6 +937,150 @@ def _same_storage(a, b) -> bool:
     return a is b or a.data_ptr() == b.data_ptr()
 
 
+_PIX_DTYPES = {}
+_INT32 = []
+
+
+def _pix_dtypes(nbytes: int):
+    if not _PIX_DTYPES:
+        torch = _torch()
+        _INT32.append(torch.int32)
+        _PIX_DTYPES.update({1: (torch.uint8,), 2: (torch.uint16, torch.int16)})
+    return _PIX_DTYPES[nbytes]
+
+
+def _on_device(t, device) -> bool:
+    """t is a torch tensor on `device` (a device given without an index names every card of its type)."""
+    if not isinstance(t, _torch().Tensor):
+        return False
+    d = t.device
+    return d == device or (device.index is None and d.type == device.type)
+
+
+def _dense(t, device, shape, esize: int) -> bool:
+    return _on_device(t, device) and t.shape == shape and t.element_size() == esize and t.is_contiguous()
+
+
+def _bad_device(name: str, t, device):
+    if not isinstance(t, _torch().Tensor):
+        raise TypeError(f"{name} must be a torch tensor on {device}, got {type(t).__name__}")
+    raise TypeError(f"{name} is on {t.device}, the codec is on {device}")
+
+
+# What check_buffers calls once an argument failed its one-expression test: the rules again, one by
+# one, with the message.  They return when nothing is wrong after all -- the quick test compares
+# devices exactly, and a codec device given without an index names every card of its type.
+def _bad_pixels(name: str, t, device, shape, nbytes: int):
+    if not _on_device(t, device):
+        _bad_device(name, t, device)
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{name} must have the codec's shape {shape}, got {tuple(t.shape)}")
+    if t.dtype not in _pix_dtypes(nbytes):
+        raise ValueError(f"{name} must hold {nbytes}-byte pixels (uint{8 * nbytes}), got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous (a dense [B, H, W] block at any storage offset), got strides "
+                         f"{tuple(t.stride())}: the library sees a pointer and (B, H, W) alone")
+
+
+def _bad_side(name: str, t, device, rest, what: str):
+    """rest(): every rule of the argument but the device's."""
+    if not _on_device(t, device):
+        _bad_device(name, t, device)
+    if not rest():
+        raise ValueError(f"{name} must be {what}, got shape {tuple(t.shape)}, strides {tuple(t.stride())}, {t.dtype}")
+
+
+def _bad_overlap(src_name: str, dst_name: str, apart: int, nbytes: int):
+    raise ValueError(f"{dst_name} overlaps {src_name} without being the same buffer ({apart} bytes apart, {nbytes} "
+                     f"bytes each): pass the same tensor (in place) or disjoint buffers")
+
+
+def check_buffers(device, B: int, H: int, W: int, bytes: int, *, lm_words: Optional[int] = None, scheme: int = 1,
+                  covers=None, stego=None, cover=None, lm=None, meta=None, payload=None,
+                  payload_words: Optional[int] = None, packed=None) -> None:
+    """The buffer contract of every PeeCodec entry that hands a pointer to the library, which
+    sees that pointer and (B, H, W, bytes) alone and assumes a dense block on the current
+    device: TypeError / ValueError naming the argument, before anything is queued.  Shapes,
+    strides, devices and pointers only -- it runs on tensors of any device without a GPU, and
+    makes no launch, sync, allocation or read-back.  Arguments left None are not looked at.
+
+    covers, stego, cover (the pixel tensors): torch tensors on `device` (TypeError naming both
+      devices otherwise), of shape (B, H, W), `bytes`-byte pixels, contiguous -- at any storage
+      offset: big[lo:hi] or flat[k:k + n].view(B, H, W) are dense blocks; a crop, a strided or
+      a transposed view is not;
+    the call's source and destination (covers -> stego, stego -> cover) are the same pointer
+      (in place) or disjoint byte ranges: the out-of-place kernels look back at neighbours
+      through __restrict__ pointers;
+    lm: [B, lm_words] 64-bit words, contiguous; meta: [B, PEE_META_BYTES] bytes, contiguous
+      (scheme 2: [4, B, ...] each, as _check_multi_args has them);
+    payload: at least [B, payload_words] 64-bit words whose rows are payload_words apart;
+    packed = (words, lengths, lens_t): words [B, pw >= 1] 64-bit, contiguous; one length per
+      slice; lens_t int32 [B], contiguous.
+
+    This runs on every embed and extract, launch-bound ones included: each argument is one
+    expression of attribute reads, and nothing else happens (no call, no string) unless it fails."""
+    try:
+        shape = (B, H, W)
+        dts = _PIX_DTYPES[bytes] if _PIX_DTYPES else _pix_dtypes(bytes)
+        if covers is not None and not (covers.device == device and covers.shape == shape and covers.dtype in dts
+                                       and covers.is_contiguous()):
+            _bad_pixels("covers", covers, device, shape, bytes)
+        if stego is not None:
+            if not (stego.device == device and stego.shape == shape and stego.dtype in dts and stego.is_contiguous()):
+                _bad_pixels("stego", stego, device, shape, bytes)
+            if covers is not None and covers is not stego:
+                apart = covers.data_ptr() - stego.data_ptr()
+                if apart and -B * H * W * bytes < apart < B * H * W * bytes:
+                    _bad_overlap("covers", "stego", abs(apart), B * H * W * bytes)
+        if cover is not None:
+            if not (cover.device == device and cover.shape == shape and cover.dtype in dts and cover.is_contiguous()):
+                _bad_pixels("cover", cover, device, shape, bytes)
+            if stego is not None and stego is not cover:
+                apart = stego.data_ptr() - cover.data_ptr()
+                if apart and -B * H * W * bytes < apart < B * H * W * bytes:
+                    _bad_overlap("stego", "cover", abs(apart), B * H * W * bytes)
+        if lm is not None:   # scheme 2: one map and one record per pass, pass-major
+            want = (4, B, lm_words) if scheme == 2 else (B, lm_words)
+            if not (lm.device == device and lm.shape == want and lm.element_size() == 8 and lm.is_contiguous()):
+                _bad_side("lm", lm, device, lambda: _dense(lm, lm.device, want, 8),
+                          f"{list(want)} ([B, lm_words]; scheme 2: [4, B, lm_words]) contiguous 64-bit words")
+        if meta is not None:
+            want = (4, B, _lib.PEE_META_BYTES) if scheme == 2 else (B, _lib.PEE_META_BYTES)
+            if not (meta.device == device and meta.shape == want and meta.element_size() == 1 and meta.is_contiguous()):
+                _bad_side("meta", meta, device, lambda: _dense(meta, meta.device, want, 1),
+                          f"{list(want)} ([B, PEE_META_BYTES]; scheme 2: [4, B, PEE_META_BYTES]) contiguous bytes")
+        if payload is not None:
+            pw = int(payload_words)
+            sh = payload.shape
+            if not (payload.device == device and pw >= 1 and len(sh) == 2 and sh[0] == B and sh[1] >= pw
+                    and payload.element_size() == 8 and payload.stride() == (pw, 1)):   # B = 1: any row pitch, below
+                _bad_side("payload", payload, device, lambda: pw >= 1 and len(sh) == 2 and sh[0] == B and sh[1] >= pw
+                          and payload.element_size() == 8, f"at least [B, payload_words] = [{B}, {pw}] 64-bit words")
+                _bad_side("payload", payload, device, lambda: payload.stride(1) == 1 and (B == 1 or payload.stride(0) == pw),
+                          f"rows of 64-bit words payload_words = {pw} apart (the library's row pitch)")
+        if packed is not None:
+            words, lengths, lens_t = packed
+            sh = words.shape
+            if not (words.device == device and len(sh) == 2 and sh[0] == B and sh[1] >= 1 and words.element_size() == 8
+                    and words.is_contiguous()):
+                _bad_side("packed[0]", words, device, lambda: len(sh) == 2 and sh[0] == B and sh[1] >= 1
+                          and words.element_size() == 8 and words.is_contiguous(),
+                          f"[B, payload_words >= 1] = [{B}, >= 1] contiguous 64-bit words")
+            if len(lengths) != B:
+                raise ValueError(f"packed[1] holds {len(lengths)} lengths for {B} slices")
+            if not (lens_t.device == device and lens_t.shape == (B,) and lens_t.dtype == _INT32[0]
+                    and lens_t.is_contiguous()):
+                _bad_side("packed[2]", lens_t, device, lambda: _dense(lens_t, lens_t.device, (B,), 4)
+                          and lens_t.dtype == _torch().int32, f"[B] = [{B}] contiguous int32 lengths")
+    except AttributeError:   # something that is no tensor at all
+        named = (("covers", covers), ("stego", stego), ("cover", cover), ("lm", lm), ("meta", meta), ("payload", payload))
+        named += (("packed[0]", packed[0]), ("packed[2]", packed[2])) if packed is not None and len(packed) == 3 else ()
+        for name, t in named:
+            if t is not None and not isinstance(t, _torch().Tensor):
+                _bad_device(name, t, device)
+        raise
+
+
 # one PeeCodec (and its zeroed workspace) per (shape, dtype, T, tmin, tmax, maxval, device); the
 # least recently used one is dropped past _CODECS_MAX entries, so varied shapes do not keep
 # GPU memory alive indefinitely (clear_codec_cache() drops them all)
@@ -947,6 +1108,19 @@ def _codec_for(shape, dtype: str, *, T, tmax: int, maxval: Optional[int], scheme
     else:
         _CODECS.move_to_end(key)
     return c
+
+
+def _as_gpu_batch(covers):
+    """codec._as_batch for encode() / encode_volume(): a numpy array is uploaded; a torch tensor
+    must already be on the current GPU, where the cached codec lives (TypeError before any codec
+    is built or launch made -- the kernels would take a host pointer as it comes)."""
+    from .codec import _as_batch
+    torch = _torch()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if isinstance(covers, torch.Tensor) and covers.device != dev:
+        raise TypeError(f"covers is on {covers.device}, the codec is on {dev}: move the tensor there (numpy arrays "
+                        f"are uploaded by the call)")
+    return _as_batch(covers)
 
 
 _STATUS_TEXT = {1: "payload exceeds PEE capacity", _lib.CODEC_PEE_ELOOKBACK: "in-place cursor look-back timed out"}
@@ -996,11 +1170,10 @@ def encode(covers, payloads: Sequence, *, T=2, tmax: int = 16, maxval: Optional[
     checksum=True: the encoding carries the covers' and payloads' CRC-32 and decode() verifies them.
     gate (scheme 1): a smoothness gate 0..65535 or "auto" (PeeCodec); decode() reads it from the records.
     Raises ValueError when a payload exceeds its slice's capacity."""
-    from .codec import _as_batch
     shape = tuple(covers.shape)
     check_gate_args(gate, T, tmax, (int(shape[-2]) // 2) * (int(shape[-1]) // 2) if len(shape) >= 2 else 0, scheme)
     _require_gpu()
-    covers = _as_batch(covers)
+    covers = _as_gpu_batch(covers)
     if isinstance(payloads, (str, bytes, bytearray)):
         payloads = [payloads]
     dt = "uint16" if _elem_bytes(covers) == 2 else "uint8"
@@ -1039,13 +1212,12 @@ def encode_volume(covers, payload, *, policy: str = "even", tmax: int = 16, maxv
     when the volume cannot hold the payload at tmax, as encode() does per slice; argument errors
     (policy, scheme 2, more than 2^31 - 1 bits or candidates, a shape that is no stack) are
     ValueError before the GPU is touched."""
-    from .codec import _as_batch
     shape = tuple(covers.shape)
     bits = framing.to_bits(payload)
     check_volume_args(shape if len(shape) != 2 else (1,) + shape, bits.size, policy, scheme)
     check_gvol_args(None, gate, tmax, (int(shape[-2]) // 2) * (int(shape[-1]) // 2), scheme)
     _require_gpu()
-    covers = _as_batch(covers)
+    covers = _as_gpu_batch(covers)
     dt = "uint16" if _elem_bytes(covers) == 2 else "uint8"
     codec = _codec_for(tuple(covers.shape), dt, T="auto", tmax=tmax, maxval=maxval)
     vol = codec.embed_volume(covers, bits, policy=policy, checksum=checksum, gate=gate)

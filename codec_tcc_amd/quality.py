@@ -32,6 +32,12 @@ def moments(a, b) -> np.ndarray:
     uint64 [B, 10] in the order of KEYS (include/codec_tcc.h, codec_quality_moments)."""
     _require_gpu()
     torch = _torch()
+    for name, t in (("a", a), ("b", b)):   # the kernel takes the pointers as they come
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
+            raise TypeError(f"moments({name}=...) must be a torch tensor on a GPU, got {where}")
+    if a.device != b.device:
+        raise TypeError(f"both images must be on one GPU: a is on {a.device}, b on {b.device}")
     if tuple(a.shape) != tuple(b.shape):
         raise ValueError(f"Dimensões diferentes: {tuple(a.shape)} vs {tuple(b.shape)}")   # mse.py:98-99
     if a.dtype != b.dtype:

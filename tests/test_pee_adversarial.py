@@ -279,7 +279,8 @@ def _check_scheme1(enc, cov, sides, stegos, ts=None, what=""):
     from codec_tcc_amd import _lib
     recs, maps = _records_and_maps(enc)
     got = enc.stego.cpu().numpy()
-    for i, kind in enumerate(KINDS):
+    assert len(recs) == len(sides) == len(stegos)   # the whole batch, or its first slices (test_pee_placement.py)
+    for i, kind in enumerate(KINDS[: len(sides)]):
         side, r = sides[i], recs[i]
         tag = (what, kind)
         assert (r.status, r.end) == (side["status"], side["end"]), tag
@@ -299,13 +300,16 @@ def _check_scheme1(enc, cov, sides, stegos, ts=None, what=""):
         assert r.lm_count == int(side["lm"].sum()), tag
 
 
-def _check_extract(codec, enc, cov, pays, embedded, inplace):
-    """codec.extract returns the exact payload prefix and the exact cover."""
+def _check_extract(codec, enc, cov, pays, embedded, inplace, cover=None):
+    """codec.extract returns the exact payload prefix and the exact cover.  cover: the caller's
+    out buffer of an out-of-place extract (a placed view, test_pee_placement.py)."""
     from codec_tcc_amd import framing
     words, back = codec.extract(enc.stego, enc.meta, enc.lm, payload_words=enc.payload_words,
-                                cover=enc.stego if inplace else None)
+                                cover=enc.stego if inplace else cover)
+    assert cover is None or inplace or back.data_ptr() == cover.data_ptr()
     host = words.cpu().numpy()
-    for i in range(len(KINDS)):
+    assert len(host) == len(pays) == len(embedded)
+    for i in range(len(pays)):
         np.testing.assert_array_equal(framing.unpack_bits(host[i], embedded[i]), pays[i][: embedded[i]], err_msg=KINDS[i])
     np.testing.assert_array_equal(back.cpu().numpy(), cov)
 
@@ -397,8 +401,9 @@ def _check_multi(enc, sides, stegos, T=None, ts=None):
     from codec_tcc_amd import _lib
     got = enc.stego.cpu().numpy()
     prs = enc.pass_records()
-    raw = enc.lm.cpu().numpy().view(np.uint8).reshape(4, len(KINDS), -1)
-    for b, kind in enumerate(KINDS):
+    assert len(prs[0]) == len(sides) == len(stegos)
+    raw = enc.lm.cpu().numpy().view(np.uint8).reshape(4, len(sides), -1)
+    for b, kind in enumerate(KINDS[: len(sides)]):
         np.testing.assert_array_equal(got[b], stegos[b], err_msg=kind)
         Tb = T if ts is None else ts[b]
         for p, ps in enumerate(sides[b]["passes"]):
