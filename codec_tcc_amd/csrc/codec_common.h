@@ -386,6 +386,13 @@ static long long debug_knob(const char* name, long long dflt) {
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// codec_pee.hip: the PEE workspace registry (include/codec_tcc.h, codec_pee_workspace_bytes) for
+// workspace-taking entries of other translation units.  P has passed the entry's checks and the
+// workspace holds codec_pee_workspace_bytes(P) bytes or more.  As for every codec_pee call: a
+// call of another shape than the workspace was last used for zeroes that layout first (on
+// `stream`) and the shape is recorded, so the earlier shape's next call zeroes its own again.
+int pee_workspace_enter(const codec_pee_params* P, void* workspace, void* stream);
+
 // CUs of the current device (cached per device): slice-serial dispatch decisions
 static inline int device_cu_count() {
     static int cached[64] = {0};

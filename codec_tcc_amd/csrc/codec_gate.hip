@@ -272,6 +272,10 @@ int codec_pee_gate_capacity(const codec_pee_params* P, const void* cover, int32_
         return set_err(CODEC_EINVAL, "codec_pee_gate_capacity: t_out / g_out / k_out need lengths");
     if (workspace_bytes < codec_pee_gate_workspace_bytes(P, tmax)) return set_err(CODEC_EINVAL, "workspace too small");
     hipStream_t st = as_stream(stream);
+    // the registry, as every workspace-taking call: the bins lie behind THIS shape's layout, so on
+    // a workspace in use for a larger shape they fall inside that shape's state (its capacity
+    // bins); recorded here, the change of shape makes the larger shape's next call zero it first
+    if ((rc = pee_workspace_enter(P, workspace, stream))) return rc;
     uint32_t* gbins = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + align_up(base, 256));
     uint32_t* arrivals = gbins + (size_t)P->B * GT_BINS;
     {

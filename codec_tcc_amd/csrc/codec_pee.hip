@@ -3450,6 +3450,11 @@ static int pee_begin(PeeCall* C, const codec_pee_params* P, int checked, bool an
     return 0;
 }
 
+int pee_workspace_enter(const codec_pee_params* P, void* workspace, void* stream) {   // codec_common.h
+    HIP_TRY(pee_ws_enter(workspace, P, pee_ws(P), as_stream(stream)));
+    return 0;
+}
+
 // ---- what the scheme-1 routes are chosen by.  vec: the 8-pixel vector kernels apply (W % 8
 // == 0 and both images aligned to `align` bytes; 0: one 8-pixel vector of P->bytes, 16 or 8);
 // items: 8-pixel row-pair chunks per slice; onepass: CODEC_PEE_ONEPASS (0 forces the two-pass

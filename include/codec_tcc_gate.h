@@ -60,7 +60,10 @@ size_t codec_pee_gate_workspace_bytes(const codec_pee_params* P, int32_t tmax);
  * switches the selection on: t_out[B], g_out[B] (the chosen T and gate VALUE, GATES[j]) and
  * k_out[B] (the capacity K at the choice), each device int32 and each optional.  t_fixed: 0, or
  * the only T considered (1..tmax).  g_fixed: -1 for the ladder, or a gate 0..65535 (see above).
- * P->T is not used (but checked, as by every entry: >= 1). */
+ * P->T is not used (but checked, as by every entry: >= 1).  The call enters the workspace's
+ * shape record like every codec_pee call (codec_pee_workspace_bytes, "shape change"): its bins lie
+ * behind P's layout, which on a workspace in use for a larger shape is inside that shape's
+ * state, so the larger shape's next call zeroes the workspace first. */
 int codec_pee_gate_capacity(const codec_pee_params* P, const void* cover, int32_t tmax, int32_t t_fixed,
                             int32_t g_fixed, const int32_t* lengths, uint32_t* n, uint32_t* hs, int32_t* t_out,
                             int32_t* g_out, int32_t* k_out, void* workspace, size_t workspace_bytes, void* stream);
