@@ -1,5 +1,6 @@
 """ctypes binding of libcodec_hip.so (include/codec_tcc.h, include/codec_tcc_ext.h,
-include/codec_tcc_crc.h, include/codec_tcc_vol.h, include/codec_tcc_gate.h, include/codec_tcc_gvol.h).
+include/codec_tcc_crc.h, include/codec_tcc_vol.h, include/codec_tcc_gate.h, include/codec_tcc_gvol.h,
+include/codec_tcc_tile.h).
 
 The library is built in-tree (codec_tcc_amd/libcodec_hip.so, see build.py).  There is no
 CPU fallback: if the library cannot be loaded, every entry point raises RuntimeError.
@@ -138,7 +139,8 @@ KERNEL_TAGS = {1: "k_scan_fast", 2: "k_scan_generic", 3: "k_block_exact", 4: "k_
                29: "k_pee_lat_count", 30: "k_pee_lat_embed", 31: "k_pee_lat_dcount", 32: "k_pee_lat_recover",
                33: "k_pee_lat_ss_embed", 34: "k_pee_lat_ss_extract", 35: "k_pee_lat_auto",
                36: "k_crc32", 37: "k_crc32_combine", 38: "k_vol_plan", 39: "k_vol_scatter", 40: "k_vol_gather",
-               41: "k_pee_gate_table", 42: "k_gvol_plan"}
+               41: "k_pee_gate_table", 42: "k_gvol_plan", 43: "k_tile_crc", 44: "k_tile_crc_bytes",
+               45: "k_tile_compare"}
 EXPORTS = tuple(_SIGS)
 # include/codec_tcc_ext.h: entries added after codec_tcc.h's list (EXPORTS) was fixed
 _SIGS_EXT = {
@@ -212,6 +214,17 @@ _SIGS_GVOL = {
                                          _VP, C.c_size_t, _VP]),
 }
 EXPORTS_GVOL = tuple(_SIGS_GVOL)
+# include/codec_tcc_tile.h: tile checksums (checksum.py crc32_tiles / compare_tiles)
+TILE_MIN, TILE_MAX = 4, 1024            # CODEC_TILE_MIN / CODEC_TILE_MAX
+TILE_ROUTE_BYTES, TILE_ROUTE_VECTOR = 1, 2   # CODEC_TILE_ROUTE_*
+_SIGS_TILE = {
+    "codec_crc32_tiles_grid": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32)]),
+    "codec_crc32_tiles_route": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _VP]),
+    "codec_crc32_tiles": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP]),
+    "codec_crc32_tiles_compare": (C.c_int, [C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP]),
+}
+EXPORTS_TILE = tuple(_SIGS_TILE)
 
 _lib = None
 _load_error = None
@@ -240,7 +253,8 @@ def load(path: str = LIB_PATH):
     except OSError as e:  # pragma: no cover - environment specific
         _load_error = e
         raise RuntimeError(f"cannot load {path}: {e}") from e
-    for name, (res, args) in {**_SIGS, **_SIGS_EXT, **_SIGS_CRC, **_SIGS_VOL, **_SIGS_GATE, **_SIGS_GVOL}.items():
+    for name, (res, args) in {**_SIGS, **_SIGS_EXT, **_SIGS_CRC, **_SIGS_VOL, **_SIGS_GATE, **_SIGS_GVOL,
+                              **_SIGS_TILE}.items():
         fn = getattr(lib, name, None)
         if fn is None:
             if name == "codec_build_digest" and not in_tree:   # a diagnostic build (tools/)

@@ -25,8 +25,9 @@ REPO = os.path.dirname(HERE)
 SRCS = [os.path.join(HERE, "csrc", "codec_hip.hip"), os.path.join(HERE, "csrc", "codec_pee.hip"),
         os.path.join(HERE, "csrc", "codec_quality.hip"), os.path.join(HERE, "csrc", "codec_records.hip"),
         os.path.join(HERE, "csrc", "codec_crc.hip"), os.path.join(HERE, "csrc", "codec_vol.hip"),
-        os.path.join(HERE, "csrc", "codec_gate.hip"), os.path.join(HERE, "csrc", "codec_gvol.hip")]
-HDRS = [os.path.join(HERE, "csrc", "codec_common.h")]
+        os.path.join(HERE, "csrc", "codec_gate.hip"), os.path.join(HERE, "csrc", "codec_gvol.hip"),
+        os.path.join(HERE, "csrc", "codec_tile.hip")]
+HDRS = [os.path.join(HERE, "csrc", "codec_common.h"), os.path.join(HERE, "csrc", "codec_crc_gf2.h")]
 OUT = os.path.join(HERE, "libcodec_hip.so")
 INC = os.path.join(REPO, "include")
 ARCH = os.environ.get("CODEC_OFFLOAD_ARCH", "gfx950")
@@ -54,7 +55,8 @@ def _obj(src: str) -> str:
 def _common_deps():
     return HDRS + [os.path.join(INC, "codec_tcc.h"), os.path.join(INC, "codec_tcc_ext.h"),
                    os.path.join(INC, "codec_tcc_crc.h"), os.path.join(INC, "codec_tcc_vol.h"),
-                   os.path.join(INC, "codec_tcc_gate.h"), os.path.join(INC, "codec_tcc_gvol.h")]
+                   os.path.join(INC, "codec_tcc_gate.h"), os.path.join(INC, "codec_tcc_gvol.h"),
+                   os.path.join(INC, "codec_tcc_tile.h")]
 
 
 def _digest(paths, flags) -> str:

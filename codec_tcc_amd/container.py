@@ -33,7 +33,8 @@ MED-PEE scheme 2 (four sublattice passes, oracle/pee_cpu.py) sets the scheme byt
 so a reader of scheme-1 files (scheme byte 0) refuses scheme-2 files instead of misreading.
 
 Either MED-PEE header may end with the 10-byte checksum extension b"C1" + >II (CRC-32 of the
-cover, CRC-32 of the embedded payload bits; checksum.py).  Readers slice the fixed fields by
+cover, CRC-32 of the embedded payload bits; checksum.py), and that may be followed by the tile
+extension b"T1" + >HHHH (th, tw, nty, ntx) + nty * ntx x >I (the cover's CRC-32 per tile).  Readers slice the fixed fields by
 size, so files with it read where it is unknown and files without it are unchanged.
 
 Stego payload codecs: the reference's ids (png 1, j2k 2, jls 3, jxl 4) are kept; id 0
@@ -232,6 +233,59 @@ def _pee_crc_fields(ext: bytes) -> Dict:
     return {"cover_crc32": c, "payload_crc32": p}
 
 
+_PEE_TILE_TAG = b"T1"
+_PEE_TILE_FMT = ">HHHH"
+_TILE_MIN, _TILE_MAX = 4, 1024   # include/codec_tcc_tile.h
+
+
+def pee_tile_extension(th: int, tw: int, table) -> bytes:
+    """The second header extension of a MED-PEE file written with checksum="tiles", appended after
+    the 10-byte b"C1" extension: b"T1" + >HHHH (th, tw, nty, ntx) + nty * ntx x >I, the cover's
+    tile checksums row-major (checksum.tiles_host's table [nty, ntx]).  Readers that know only
+    b"C1" ignore what follows it, so they still read the file and verify the slice CRC."""
+    t = np.asarray(table)
+    if t.ndim != 2 or t.size == 0:
+        raise ValueError("a tile table is a non-empty [nty, ntx] array")
+    nty, ntx = t.shape
+    if not (_TILE_MIN <= int(th) <= _TILE_MAX and _TILE_MIN <= int(tw) <= _TILE_MAX):
+        raise ValueError(f"tile size ({th}, {tw}) outside {_TILE_MIN}..{_TILE_MAX}")
+    if nty > 0xFFFF or ntx > 0xFFFF:
+        raise ValueError(f"a tile grid of {nty} x {ntx} does not fit the extension's 16-bit fields")
+    words = (t.astype(np.int64) & 0xFFFFFFFF).astype(">u4")
+    return _PEE_TILE_TAG + struct.pack(_PEE_TILE_FMT, int(th), int(tw), nty, ntx) + words.tobytes()
+
+
+def _pee_tile_fields(ext: bytes, width: int, height: int) -> Dict:
+    """{'tile': (th, tw), 'tile_crc32': uint32 [nty, ntx]} of the header bytes after the b"C1"
+    extension ({} when they do not start the tile extension); ValueError for a header cut inside
+    it, a tile size out of range or a grid that is not ceil(height / th) x ceil(width / tw)."""
+    if not ext or ext[:2] != _PEE_TILE_TAG[:len(ext[:2])]:
+        return {}
+    n0 = len(_PEE_TILE_TAG) + struct.calcsize(_PEE_TILE_FMT)
+    if len(ext) < n0:
+        raise ValueError(f"truncated MED-PEE header: a tile extension of {len(ext)} bytes, at least {n0} needed")
+    th, tw, nty, ntx = struct.unpack(_PEE_TILE_FMT, ext[2:n0])
+    if not (_TILE_MIN <= th <= _TILE_MAX and _TILE_MIN <= tw <= _TILE_MAX):
+        raise ValueError(f"MED-PEE header: tile size ({th}, {tw}) outside {_TILE_MIN}..{_TILE_MAX}")
+    if (nty, ntx) != (-(-height // th), -(-width // tw)):
+        raise ValueError(f"MED-PEE header: a tile grid of {nty} x {ntx} contradicts {height} x {width} pixels at "
+                         f"tile ({th}, {tw})")
+    n = n0 + 4 * nty * ntx
+    if len(ext) < n:
+        raise ValueError(f"truncated MED-PEE header: a tile extension of {len(ext)} bytes, {n} needed")
+    table = np.frombuffer(ext[n0:n], dtype=">u4").astype(np.uint32).reshape(nty, ntx)
+    return {"tile": (th, tw), "tile_crc32": table}
+
+
+def _pee_ext_fields(ext: bytes, width: int, height: int) -> Dict:
+    """The fields of a header's extensions: the checksum extension's, and the tile extension's
+    when it follows."""
+    md = _pee_crc_fields(ext)
+    if md:
+        md.update(_pee_tile_fields(ext[len(_PEE_CRC_TAG) + struct.calcsize(_PEE_CRC_FMT):], width, height))
+    return md
+
+
 def _pee_shape_check(bpp: int, width: int, height: int):
     if bpp not in (1, 2):
         raise ValueError(f"MED-PEE header: {bpp} bytes per pixel (1 or 2)")
@@ -285,7 +339,7 @@ def parse_pee_gate_bytes(data: bytes) -> Tuple[Dict, bytes, bytes]:
     md = {"version": PEE_VERSION, "scheme": PEE_SCHEME_GATE, "codec": CODEC_NAMES.get(cid, "raw" if cid == 0 else "unknown"),
           "bytes": bpp, "width": width, "height": height, "T": T, "L": L, "end": end, "maxval": maxval,
           "status": status, "gate": gate}
-    md.update(_pee_crc_fields(hdr[n0 + struct.calcsize(_PEE_GATE_FMT):]))
+    md.update(_pee_ext_fields(hdr[n0 + struct.calcsize(_PEE_GATE_FMT):], width, height))
     return md, body[:blob_size], body[blob_size:]
 
 
@@ -326,7 +380,7 @@ def parse_pee2_bytes(data: bytes) -> Tuple[Dict, List[bytes], bytes]:
     md = {"version": PEE_VERSION, "scheme": 2, "codec": CODEC_NAMES.get(cid, "raw" if cid == 0 else "unknown"),
           "bytes": bpp, "width": width, "height": height, "T": T, "maxval": maxval, "L": L, "status": status,
           "passes": passes}
-    md.update(_pee_crc_fields(hdr[n0 + 4 * struct.calcsize(_PEE2_PASS):]))
+    md.update(_pee_ext_fields(hdr[n0 + 4 * struct.calcsize(_PEE2_PASS):], width, height))
     return md, blobs, body[pos:]
 
 
@@ -347,5 +401,5 @@ def parse_pee_bytes(data: bytes) -> Tuple[Dict, bytes, bytes]:
     md = {"version": PEE_VERSION, "codec": CODEC_NAMES.get(cid, "raw" if cid == 0 else "unknown"),
           "bytes": bpp, "width": width, "height": height, "T": T, "L": L, "end": end, "maxval": maxval,
           "status": status}
-    md.update(_pee_crc_fields(hdr[struct.calcsize(_PEE_FMT):]))
+    md.update(_pee_ext_fields(hdr[struct.calcsize(_PEE_FMT):], width, height))
     return md, body[:blob_size], body[blob_size:]

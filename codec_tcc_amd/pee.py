@@ -26,7 +26,7 @@ from __future__ import annotations
 import ctypes as C
 from collections import OrderedDict
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -178,6 +178,8 @@ class PeeEncoded:
     scheme: int = 1                              # 2: four sublattice passes (meta / lm per pass)
     cover_crc: object = None                     # torch.int32 [B] (device): CRC-32 of each cover (checksum=True)
     payload_crc: Optional[List[int]] = None      # CRC-32 of each slice's payload bits (checksum.payload_crc32)
+    cover_tile_crc: object = None                # torch.int32 [B, nty, ntx] (device): CRC-32 per tile (checksum="tiles")
+    tile: Optional[Tuple[int, int]] = None       # the table's (th, tw)
 
     def records(self) -> List[_lib.PeeMeta]:
         """Scheme 1: one record per slice.  Scheme 2: 4 * B records, pass-major."""
@@ -458,7 +460,7 @@ class PeeCodec:
         return caps
 
     def embed(self, covers, payloads, *, stego=None, lm=None, meta=None, packed=None, check: bool = True,
-              checksum: bool = False) -> PeeEncoded:
+              checksum=False, tile=_ck.TILE_DEFAULT) -> PeeEncoded:
         """cover -> stego + location map + per-slice meta.  check=True (default) reads the
         per-slice status back (one sync) and raises RuntimeError if an in-place look-back
         gave up (CODEC_PEE_ELOOKBACK: the slice is not a valid stego); check=False keeps
@@ -466,17 +468,25 @@ class PeeCodec:
         checksum=True: enc.cover_crc = crc32_slices(covers), launched on the same stream BEFORE
         the embed (so an in-place embed checksums the cover, not the stego), and
         enc.payload_crc from the bits on the host (None with caller-packed `packed=` payloads:
-        the bits are not here); decode(enc) then verifies both."""
+        the bits are not here); decode(enc) then verifies both.
+        checksum="tiles": everything checksum=True records, and enc.cover_tile_crc =
+        crc32_tiles(covers, tile) (int32 [B, nty, ntx]; tile: an int or (th, tw), 4..1024), queued
+        before the embed too; a decode whose cover check fails then names the tiles that differ
+        (IntegrityError.tiles)."""
         torch = _torch()
+        checksum, tiled = _ck.checksum_mode(checksum)
+        tile = _ck.check_tile_args(tile) if tiled else None
         # every buffer of the call, before anything is queued (the checksum launch included)
         check_buffers(self.device, self.B, self.H, self.W, self.bytes, lm_words=self.lm_words, scheme=self.scheme,
                       covers=covers, stego=stego, lm=lm, meta=meta, packed=packed)
         if self.scheme == 2 and self.auto and stego is not None and _same_storage(covers, stego):
             raise ValueError("scheme 2 with T='auto' embeds out of place only (a failed trial is undone from "
                              "the cover): pass a stego buffer other than the covers")
-        cover_crc = payload_crc = None
+        cover_crc = payload_crc = tile_crc = None
         if checksum:
             cover_crc = _ck.crc32_slices(covers)   # queued first: the host work below runs beside it
+            if tiled:
+                tile_crc = _ck.crc32_tiles(covers, tile)
             if packed is None:   # pack here (what _embed would do) and checksum the packed rows
                 bits = [framing.to_bits(p) for p in payloads]
                 if len(bits) != self.B:
@@ -487,6 +497,7 @@ class PeeCodec:
                           torch.tensor(lengths, dtype=torch.int32, device=self.device))
         enc = self._embed(covers, payloads, stego, lm, meta, packed, check)
         enc.cover_crc, enc.payload_crc = cover_crc, payload_crc
+        enc.cover_tile_crc, enc.tile = tile_crc, tile
         return enc
 
     def _embed(self, covers, payloads, stego, lm, meta, packed, check) -> PeeEncoded:
@@ -647,7 +658,30 @@ class PeeCodec:
                 raise ValueError(f"{len(enc.payload_crc)} payload checksums for {self.B} slices")
             bad_p = [b for b in range(self.B)
                      if _ck.payload_crc32_packed(rows[b], enc.lengths[b]) != int(enc.payload_crc[b]) & 0xFFFFFFFF]
-        _ck.raise_mismatch(bad_c, bad_p)
+        if bad_c or bad_p:
+            _ck.raise_mismatch(bad_c, bad_p, tiles=self._tile_maps(enc, cover, bad_c), tile=enc.tile,
+                               shape=(self.H, self.W))
+
+    def _tile_maps(self, enc: PeeEncoded, cover, bad_c):
+        """IntegrityError.tiles of a failed verify: None without a tile table, {} when no cover
+        failed, else the differing-tile maps of the slices in bad_c -- the only place decode
+        runs the tile pass (crc32_tiles on the restored cover + compare_tiles, one read-back of
+        counts and bitmap)."""
+        if enc.cover_tile_crc is None:
+            return None
+        return _ck.tile_mismatch_maps(cover, enc.cover_tile_crc, enc.tile, bad_c) if bad_c else {}
+
+    def verify_tiles(self, enc: PeeEncoded, cover) -> np.ndarray:
+        """Host bool [B, nty, ntx]: the tiles of `cover` (a restored [B,H,W] stack on the GPU) whose
+        CRC-32 differs from the table enc carries (embed(..., checksum="tiles")).  Never raises
+        IntegrityError: for callers that decode with verify=False and want the map beside the
+        data.  ValueError for an encoding without a table, or a table of another grid, dtype or
+        device."""
+        if enc.cover_tile_crc is None or enc.tile is None:
+            raise ValueError("the encoding carries no tile table (embed with checksum='tiles')")
+        self._check_buffers(covers=cover)
+        maps = _ck.tile_mismatch_maps(cover, enc.cover_tile_crc, enc.tile, range(self.B))
+        return np.stack([maps[b] for b in range(self.B)])
 
     def decode(self, enc: PeeEncoded, verify=True):
         """(list of 0/1 bit vectors, restored cover tensor); raises if a slice overflowed, and
@@ -753,7 +787,7 @@ class PeeCodec:
         return _torch().from_numpy(framing.pack_bits([bits])[0].reshape(-1)).to(self.device), int(bits.size)
 
     def embed_volume(self, covers, payload, *, policy: str = "even", stego=None, check: bool = True,
-                     checksum: bool = False, buffers=None, packed=None, gate=None) -> "PeeVolume":
+                     checksum=False, buffers=None, packed=None, gate=None, tile=_ck.TILE_DEFAULT) -> "PeeVolume":
         """One payload (str / bytes / 0-1 vector, framing.to_bits) embedded across the whole
         stack: the device plans how many bits each slice takes and at which T (the rule of
         include/codec_tcc_vol.h: policy "even" spreads the bits in proportion to the slices'
@@ -778,8 +812,12 @@ class PeeCodec:
         stream (over the embedded prefix when check=True saw a truncation); decode_volume
         verifies both.  stego may be the covers (in place).  buffers: volume_buffers();
         packed: pack_volume()'s result instead of `payload` (no upload in the call; the payload
-        CRC is then absent, as with embed's packed=)."""
+        CRC is then absent, as with embed's packed=).
+        checksum="tiles": checksum=True plus enc.cover_tile_crc / enc.tile as embed records them;
+        decode_volume then names the tiles of a cover that fails its check."""
         torch = _torch()
+        checksum, tiled = _ck.checksum_mode(checksum)
+        tile = _ck.check_tile_args(tile) if tiled else None
         check_gvol_args(self.gate, gate, self.tmax, self.nc, self.scheme)
         gated = gate is not None
         self._check_buffers(covers=covers, stego=stego)
@@ -803,6 +841,7 @@ class PeeCodec:
         words = packed[0] if packed is not None else \
             torch.from_numpy(framing.pack_bits([bits])[0].reshape(-1)).to(self.device)
         cover_crc = _ck.crc32_slices(covers) if checksum else None   # before an in-place embed
+        tile_crc = _ck.crc32_tiles(covers, tile) if tiled else None
         if stego is None:
             stego = torch.empty_like(covers)
         if buffers is None:
@@ -830,7 +869,7 @@ class PeeCodec:
         if gated:
             config["gate"] = gate if isinstance(gate, str) else int(gate)
         enc = PeeEncoded(stego=stego, lm=lm, meta=meta, lengths=[0] * self.B, payload_words=pw,
-                         config=config, cover_crc=cover_crc)
+                         config=config, cover_crc=cover_crc, cover_tile_crc=tile_crc, tile=tile)
         vol = PeeVolume(enc=enc, total_bits=N, policy=policy, plan=plan, info=info, gate=config.get("gate"),
                         payload_crc=_ck.payload_crc32(bits) if checksum and bits is not None else None)
         if check:
@@ -898,7 +937,10 @@ class PeeCodec:
             if have_p and _ck.payload_crc32(bits) != int(vol.payload_crc) & 0xFFFFFFFF:
                 parts.append("the volume's payload checksum does not match")
             if parts:
-                raise _ck.IntegrityError(f"MED-PEE decode: {'; '.join(parts)} (CRC-32: this is not what was embedded)")
+                tiles = self._tile_maps(enc, cover, bad_c)
+                raise _ck.IntegrityError(f"MED-PEE decode: {'; '.join(parts)} (CRC-32: this is not what was embedded)"
+                                         + _ck.tiles_text(tiles, enc.tile, (self.H, self.W)),
+                                         bad_cover=bad_c, tiles=tiles, tile=enc.tile)
         return bits, cover
 
     def _cover_mismatches(self, enc: PeeEncoded) -> List[int]:
@@ -1161,24 +1203,28 @@ def _config_from_records(enc: "PeeEncoded") -> dict:
 
 
 def encode(covers, payloads: Sequence, *, T=2, tmax: int = 16, maxval: Optional[int] = None,
-           scheme: int = 1, tmin: int = 1, checksum: bool = False, gate=None) -> PeeEncoded:
+           scheme: int = 1, tmin: int = 1, checksum=False, gate=None, tile=_ck.TILE_DEFAULT) -> PeeEncoded:
     """MED-PEE embed of one payload per slice (the package's `encode(..., method="pee")`).
     covers: [B,H,W] / [H,W] uint8/uint16 torch tensor or numpy array; T: expansion threshold
     or "auto" (smallest T <= tmax whose capacity holds each slice's payload); maxval: the
     largest legal pixel value (e.g. 4095 for 12-bit DICOM; default the dtype's maximum);
     scheme 2: four sublattice passes; its T="auto" tries T = tmin .. tmax per slice in one launch.
     checksum=True: the encoding carries the covers' and payloads' CRC-32 and decode() verifies them.
+    checksum="tiles": also one CRC-32 per `tile` (int or (th, tw), 4..1024) of every cover, so that a
+    failed verify names the tiles that differ (PeeCodec.embed).
     gate (scheme 1): a smoothness gate 0..65535 or "auto" (PeeCodec); decode() reads it from the records.
     Raises ValueError when a payload exceeds its slice's capacity."""
     shape = tuple(covers.shape)
     check_gate_args(gate, T, tmax, (int(shape[-2]) // 2) * (int(shape[-1]) // 2) if len(shape) >= 2 else 0, scheme)
+    if _ck.checksum_mode(checksum)[1]:
+        _ck.check_tile_args(tile)
     _require_gpu()
     covers = _as_gpu_batch(covers)
     if isinstance(payloads, (str, bytes, bytearray)):
         payloads = [payloads]
     dt = "uint16" if _elem_bytes(covers) == 2 else "uint8"
     codec = _codec_for(tuple(covers.shape), dt, T=T, tmax=tmax, maxval=maxval, scheme=scheme, tmin=tmin, gate=gate)
-    enc = codec.embed(covers, payloads, checksum=checksum)
+    enc = codec.embed(covers, payloads, checksum=checksum, tile=tile)
     if scheme == 2:
         short = [i for i, (g, n) in enumerate(zip(enc.embedded(), enc.lengths)) if g < n]
         if short:
@@ -1203,7 +1249,7 @@ def decode(enc: PeeEncoded, verify=True, *, restore: bool = True):
 
 
 def encode_volume(covers, payload, *, policy: str = "even", tmax: int = 16, maxval: Optional[int] = None,
-                  checksum: bool = False, scheme: int = 1, gate=None) -> PeeVolume:
+                  checksum=False, scheme: int = 1, gate=None, tile=_ck.TILE_DEFAULT) -> PeeVolume:
     """MED-PEE embed of ONE payload across a [B,H,W] stack (PeeCodec.embed_volume): the bits are
     spread over the slices on the device (policy "even": in proportion to capacity; "fill": in
     slice order), each slice at the smallest T <= tmax that holds its share.  gate: a smoothness
@@ -1216,11 +1262,13 @@ def encode_volume(covers, payload, *, policy: str = "even", tmax: int = 16, maxv
     bits = framing.to_bits(payload)
     check_volume_args(shape if len(shape) != 2 else (1,) + shape, bits.size, policy, scheme)
     check_gvol_args(None, gate, tmax, (int(shape[-2]) // 2) * (int(shape[-1]) // 2), scheme)
+    if _ck.checksum_mode(checksum)[1]:
+        _ck.check_tile_args(tile)
     _require_gpu()
     covers = _as_gpu_batch(covers)
     dt = "uint16" if _elem_bytes(covers) == 2 else "uint8"
     codec = _codec_for(tuple(covers.shape), dt, T="auto", tmax=tmax, maxval=maxval)
-    vol = codec.embed_volume(covers, bits, policy=policy, checksum=checksum, gate=gate)
+    vol = codec.embed_volume(covers, bits, policy=policy, checksum=checksum, gate=gate, tile=tile)
     if vol.embedded_bits < vol.total_bits:
         raise ValueError(f"payload of {vol.total_bits} bits exceeds the volume's PEE capacity "
                          f"{vol.embedded_bits} (tmax={tmax})")

@@ -139,7 +139,7 @@ def decode_bin_exact(filepath: str, search_block_size: Optional[int] = None) -> 
 
 # ------------------------------------------------------------------ MED-PEE files
 def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxval: Optional[int] = None,
-                    codec: str = "raw", scheme: int = 1, tmin: int = 1, checksum: bool = False, gate=None) -> Dict:
+                    codec: str = "raw", scheme: int = 1, tmin: int = 1, checksum=False, gate=None, tile=64) -> Dict:
     """MED-PEE embed of one slice into a version-16 STGC file.  `image` is an array or a
     DICOM path; maxval defaults to the DICOM's full scale 2**BitsStored - 1 (4095 for the
     reference's 12-bit pe.dcm), else the dtype maximum.  T = 'auto' picks the smallest
@@ -150,11 +150,16 @@ def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxva
     checksum=True: the header ends with the checksum extension (container.pee_crc_extension:
     CRC-32 of the cover, from the GPU pass queued before the embed, and of the embedded
     payload bits), which decode_bin_pee verifies; without it the file's bytes are unchanged.
+    checksum="tiles": the tile extension follows it (container.pee_tile_extension: the cover's
+    CRC-32 per `tile`, an int or (th, tw) in 4..1024), so that decode_bin_pee names the tiles of a
+    cover that fails its check; readers that know only the checksum extension read the file as ever.
     gate (scheme 1): a smoothness gate 0..65535 or 'auto' (PeeCodec): the file then carries scheme
     byte 3 and the chosen gate after scheme 1's fixed header fields ('gate' in the result);
     without it the file's bytes are unchanged."""
     from . import checksum as _ck
     from .pee import PeeCodec, check_gate_args, lm_bits
+    checksum, tiled = _ck.checksum_mode(checksum)
+    tile = _ck.check_tile_args(tile) if tiled else None
     if gate is not None:
         shape = getattr(image, "shape", (0, 0))
         check_gate_args(gate, T, tmax, (int(shape[-2]) // 2) * (int(shape[-1]) // 2) if len(shape) >= 2 else 0, scheme)
@@ -171,13 +176,19 @@ def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxva
     h, w = img.shape
     bits = framing.to_bits(payload)
     pc = PeeCodec(1, h, w, dtype=str(img.dtype), T=T, tmin=tmin, tmax=tmax, maxval=maxval, scheme=scheme, gate=gate)
-    enc = pc.embed(torch.from_numpy(np.ascontiguousarray(img)[None]).cuda(), [bits], checksum=checksum)
+    enc = pc.embed(torch.from_numpy(np.ascontiguousarray(img)[None]).cuda(), [bits],
+                   checksum="tiles" if tiled else checksum, **({"tile": tile} if tiled else {}))
 
     def ext(embedded: int) -> Tuple[bytes, Dict]:
         if not checksum:
             return b"", {}
         crcs = {"cover_crc32": _ck.crc_list(enc.cover_crc)[0], "payload_crc32": _ck.payload_crc32(bits[:embedded])}
-        return container.pee_crc_extension(crcs["cover_crc32"], crcs["payload_crc32"]), crcs
+        xb = container.pee_crc_extension(crcs["cover_crc32"], crcs["payload_crc32"])
+        if tiled:
+            crcs["tile"] = tile
+            crcs["tile_crc32"] = enc.cover_tile_crc[0].cpu().numpy().view(np.uint32)
+            xb += container.pee_tile_extension(tile[0], tile[1], crcs["tile_crc32"])
+        return xb, crcs
     if scheme == 2:
         prs = [pr[0] for pr in enc.pass_records()]
         blobs = [container.lm_blob(lm_bits(enc, 0, p)) if prs[p].end >= 0 else b"" for p in range(4)]
@@ -267,7 +278,8 @@ def decode_bin_pee(filepath: str, verify=True) -> Tuple[np.ndarray, np.ndarray]:
     (either scheme): read_pee_bytes on the host, then one extract launch.
     verify=True: a file with the checksum extension is checked -- the restored cover's CRC-32
     (one GPU pass behind the extract) and the payload's against the header's; IntegrityError
-    names what failed.  False skips it; 'require' also raises for a file without checksums."""
+    names what failed, and for a file with the tile extension its `tiles` attribute maps the tiles
+    of the cover that differ.  False skips it; 'require' also raises for a file without checksums."""
     from . import checksum as _ck
     from .pee import PeeCodec
     mode = _ck.verify_mode(verify)
@@ -290,6 +302,11 @@ def decode_bin_pee(filepath: str, verify=True) -> Tuple[np.ndarray, np.ndarray]:
     crc = _ck.crc32_slices(cover) if (mode and have) else None
     bits = framing.unpack_bits(words.cpu().numpy()[0], md["L"])
     if crc is not None:
-        _ck.raise_mismatch([0] if _ck.crc_list(crc)[0] != md["cover_crc32"] else [],
-                           [0] if _ck.payload_crc32(bits) != md["payload_crc32"] else [], "MED-PEE file")
+        bad_c = [0] if _ck.crc_list(crc)[0] != md["cover_crc32"] else []
+        bad_p = [0] if _ck.payload_crc32(bits) != md["payload_crc32"] else []
+        tiles = None
+        if (bad_c or bad_p) and "tile_crc32" in md:   # the tile pass runs only for a cover that failed
+            table = torch.from_numpy(md["tile_crc32"].view(np.int32)[None].copy()).cuda()
+            tiles = _ck.tile_mismatch_maps(cover, table, md["tile"], bad_c) if bad_c else {}
+        _ck.raise_mismatch(bad_c, bad_p, "MED-PEE file", tiles=tiles, tile=md.get("tile"), shape=(h, w))
     return bits, cover.cpu().numpy()[0]
