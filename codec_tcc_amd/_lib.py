@@ -1,6 +1,6 @@
 """ctypes binding of libcodec_hip.so (include/codec_tcc.h, include/codec_tcc_ext.h,
 include/codec_tcc_crc.h, include/codec_tcc_vol.h, include/codec_tcc_gate.h, include/codec_tcc_gvol.h,
-include/codec_tcc_tile.h).
+include/codec_tcc_tile.h, include/codec_tcc_roi.h).
 
 The library is built in-tree (codec_tcc_amd/libcodec_hip.so, see build.py).  There is no
 CPU fallback: if the library cannot be loaded, every entry point raises RuntimeError.
@@ -140,7 +140,7 @@ KERNEL_TAGS = {1: "k_scan_fast", 2: "k_scan_generic", 3: "k_block_exact", 4: "k_
                33: "k_pee_lat_ss_embed", 34: "k_pee_lat_ss_extract", 35: "k_pee_lat_auto",
                36: "k_crc32", 37: "k_crc32_combine", 38: "k_vol_plan", 39: "k_vol_scatter", 40: "k_vol_gather",
                41: "k_pee_gate_table", 42: "k_gvol_plan", 43: "k_tile_crc", 44: "k_tile_crc_bytes",
-               45: "k_tile_compare"}
+               45: "k_tile_compare", 46: "k_roi_bbox"}
 EXPORTS = tuple(_SIGS)
 # include/codec_tcc_ext.h: entries added after codec_tcc.h's list (EXPORTS) was fixed
 _SIGS_EXT = {
@@ -225,6 +225,19 @@ _SIGS_TILE = {
     "codec_crc32_tiles_compare": (C.c_int, [C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP]),
 }
 EXPORTS_TILE = tuple(_SIGS_TILE)
+# include/codec_tcc_roi.h: ROI-protected MED-PEE (roi.py; pee.py, PeeCodec.embed(roi=...))
+ROI_MAX_DIM = 65535       # CODEC_PEE_ROI_MAX_DIM
+_SIGS_ROI = {
+    "codec_pee_roi_capacity": (C.c_int, [C.POINTER(PeeParams), _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP,
+                                         _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "codec_pee_roi_embed": (C.c_int, [C.POINTER(PeeParams), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t,
+                                      _VP]),
+    "codec_pee_roi_embed_auto": (C.c_int, [C.POINTER(PeeParams), _VP, _VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP,
+                                           _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "codec_pee_roi_extract": (C.c_int, [C.POINTER(PeeParams), _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "codec_roi_bbox": (C.c_int, [C.POINTER(PeeParams), _VP, C.c_int32, C.c_int32, _VP, _VP]),
+}
+EXPORTS_ROI = tuple(_SIGS_ROI)
 
 _lib = None
 _load_error = None
@@ -254,7 +267,7 @@ def load(path: str = LIB_PATH):
         _load_error = e
         raise RuntimeError(f"cannot load {path}: {e}") from e
     for name, (res, args) in {**_SIGS, **_SIGS_EXT, **_SIGS_CRC, **_SIGS_VOL, **_SIGS_GATE, **_SIGS_GVOL,
-                              **_SIGS_TILE}.items():
+                              **_SIGS_TILE, **_SIGS_ROI}.items():
         fn = getattr(lib, name, None)
         if fn is None:
             if name == "codec_build_digest" and not in_tree:   # a diagnostic build (tools/)

@@ -486,7 +486,7 @@ def _as_batch(covers):
 
 def encode(covers, payloads: Sequence, *, method: str = "lsb", beta: float = 0.4, block: int = 16,
            align: bool = False, mode: str = "hybrid", nbits: Optional[int] = None, T=2, tmax: int = 16,
-           maxval: Optional[int] = None, scheme: int = 1, tmin: int = 1, gate=None):
+           maxval: Optional[int] = None, scheme: int = 1, tmin: int = 1, gate=None, roi=None):
     """Embed one payload per slice.
 
     method="lsb" (default): the reference's bit-plane scheme, bit-exact with src/codec.py;
@@ -497,16 +497,20 @@ def encode(covers, payloads: Sequence, *, method: str = "lsb", beta: float = 0.4
     smallest T <= tmax per slice), maxval = largest legal pixel value (4095 for 12-bit data),
     scheme = 1 (the (odd, odd) lattice) or 2 (four sublattice passes; T="auto" there tries
     T = tmin .. tmax per slice inside one launch); gate (scheme 1) = a smoothness gate 0..65535
-    or "auto": candidates in a rough context are left alone (pee.PeeCodec).
+    or "auto": candidates in a rough context are left alone (pee.PeeCodec); roi (scheme 1) = a pixel
+    rectangle (y0, x0, y1, x1) for every slice, or [B, 4] of them, that the stego leaves
+    bit-identical to the cover (pee.PeeCodec.embed, roi.roi_bbox).
     Returns a pee.PeeEncoded; beta/block/align/mode/nbits do not apply.
     decode() takes either result."""
     if method == "pee":
         from . import pee
-        return pee.encode(covers, payloads, T=T, tmax=tmax, maxval=maxval, scheme=scheme, tmin=tmin, gate=gate)
+        return pee.encode(covers, payloads, T=T, tmax=tmax, maxval=maxval, scheme=scheme, tmin=tmin, gate=gate, roi=roi)
     if method != "lsb":
         raise ValueError("method must be 'lsb' or 'pee'")
     if gate is not None:
         raise ValueError("gate is method='pee''s")
+    if roi is not None:
+        raise ValueError("roi is method='pee''s")
     _require_gpu()
     covers = _as_batch(covers)
     if isinstance(payloads, (str, bytes, bytearray)):

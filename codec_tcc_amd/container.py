@@ -327,6 +327,8 @@ def create_pee_gate_header(codec: str, bytes_per_px: int, width: int, height: in
 def parse_pee_gate_bytes(data: bytes) -> Tuple[Dict, bytes, bytes]:
     """A gated version-16 STGC file (scheme byte 3) -> (side information with 'gate', lm_blob,
     stego bytes); 'cover_crc32' / 'payload_crc32' when the header carries the checksum extension."""
+    if pee_scheme(data) == PEE_SCHEME_ROI:
+        raise ValueError("a ROI-protected MED-PEE container (scheme byte 4): use parse_pee_roi_bytes")
     if pee_scheme(data) != PEE_SCHEME_GATE:
         raise ValueError("not a gated MED-PEE container (scheme byte 3)")
     n0 = struct.calcsize(_PEE_FMT)
@@ -343,9 +345,57 @@ def parse_pee_gate_bytes(data: bytes) -> Tuple[Dict, bytes, bytes]:
     return md, body[:blob_size], body[blob_size:]
 
 
+PEE_SCHEME_ROI = 4
+_PEE_ROI_FMT = ">HHHH"
+
+
+def create_pee_roi_header(codec: str, bytes_per_px: int, width: int, height: int, T: int, L: int, end: int,
+                          maxval: int, status: int, lm_blob_size: int, gate: int, roi) -> bytes:
+    """Header of a ROI-protected scheme-1 file (scheme byte 4): scheme byte 3's fixed
+    fields (scheme 1's, then the gate as >H -- 65535 when no gate was asked for) followed by the
+    rectangle (y0, x0, y1, x1) as >HHHH.  The optional extensions follow as in every scheme.  A
+    reader that knows scheme bytes 0, 2 and 3 refuses the file, so a protected file is never
+    decoded without its rectangle."""
+    if not 0 <= int(gate) <= 0xFFFF:
+        raise ValueError(f"gate = {gate}: 0..65535")
+    y0, x0, y1, x1 = (int(v) for v in roi)
+    if not (0 <= y0 < y1 <= min(int(height), 0xFFFF) and 0 <= x0 < x1 <= min(int(width), 0xFFFF)):
+        raise ValueError(f"roi = {(y0, x0, y1, x1)}: a non-empty rectangle inside {height} x {width} pixels (at most 65535 a side)")
+    return struct.pack(_PEE_FMT, PEE_VERSION, CODEC_IDS.get(codec.lower(), 0), int(bytes_per_px), PEE_SCHEME_ROI,
+                       width, height, int(T), int(L), int(end), int(maxval), int(status), int(lm_blob_size)) + \
+        struct.pack(_PEE_GATE_FMT, int(gate)) + struct.pack(_PEE_ROI_FMT, y0, x0, y1, x1)
+
+
+def parse_pee_roi_bytes(data: bytes) -> Tuple[Dict, bytes, bytes]:
+    """A ROI-protected version-16 STGC file (scheme byte 4) -> (side information with 'gate' and
+    'roi' = (y0, x0, y1, x1), lm_blob, stego bytes); 'cover_crc32' / 'payload_crc32' (and the tile
+    fields) when the header carries the extensions.  ValueError for a header cut inside the
+    rectangle, and for a rectangle that is empty or not inside the image."""
+    if pee_scheme(data) != PEE_SCHEME_ROI:
+        raise ValueError("not a ROI-protected MED-PEE container (scheme byte 4)")
+    n0 = struct.calcsize(_PEE_FMT)
+    n1 = n0 + struct.calcsize(_PEE_GATE_FMT)
+    n2 = n1 + struct.calcsize(_PEE_ROI_FMT)
+    hdr, body = _pee_header(data, n2, "ROI-protected MED-PEE file")
+    (_v, cid, bpp, _s, width, height, T, L, end, maxval, status, blob_size) = struct.unpack(_PEE_FMT, hdr[:n0])
+    (gate,) = struct.unpack(_PEE_GATE_FMT, hdr[n0:n1])
+    y0, x0, y1, x1 = struct.unpack(_PEE_ROI_FMT, hdr[n1:n2])
+    _pee_shape_check(bpp, width, height)
+    if not (y0 < y1 <= height and x0 < x1 <= width):
+        raise ValueError(f"MED-PEE header: the rectangle (y0, x0, y1, x1) = {(y0, x0, y1, x1)} is empty or not inside "
+                         f"{height} x {width} pixels")
+    if blob_size > len(body):
+        raise ValueError(f"truncated MED-PEE file: a location-map blob of {blob_size} bytes, {len(body)} left")
+    md = {"version": PEE_VERSION, "scheme": PEE_SCHEME_ROI, "codec": CODEC_NAMES.get(cid, "raw" if cid == 0 else "unknown"),
+          "bytes": bpp, "width": width, "height": height, "T": T, "L": L, "end": end, "maxval": maxval,
+          "status": status, "gate": gate, "roi": (y0, x0, y1, x1)}
+    md.update(_pee_ext_fields(hdr[n2:], width, height))
+    return md, body[:blob_size], body[blob_size:]
+
+
 def pee_scheme(data: bytes) -> int:
-    """1, 2 or 3: the MED-PEE scheme of a version-16 STGC file (its scheme byte; 3 = scheme 1
-    with a smoothness gate)."""
+    """1, 2, 3 or 4: the MED-PEE scheme of a version-16 STGC file (its scheme byte; 3 = scheme 1
+    with a smoothness gate, 4 = scheme 1 with a protected rectangle and a gate)."""
     if data[:4] != MAGIC:
         raise ValueError("Arquivo inválido ou com assinatura incorreta.")   # codec.py:698
     if len(data) < 8:
@@ -354,7 +404,7 @@ def pee_scheme(data: bytes) -> int:
     hdr = data[8:8 + hlen]
     if len(hdr) < 4 or hdr[0] != PEE_VERSION:
         raise ValueError("not a MED-PEE container (version 16)")
-    if hdr[3] not in (0, PEE_SCHEME2, PEE_SCHEME_GATE):
+    if hdr[3] not in (0, PEE_SCHEME2, PEE_SCHEME_GATE, PEE_SCHEME_ROI):
         raise ValueError(f"unknown MED-PEE scheme byte {hdr[3]}")
     return 1 if hdr[3] == 0 else int(hdr[3])
 
@@ -388,6 +438,8 @@ def parse_pee_bytes(data: bytes) -> Tuple[Dict, bytes, bytes]:
     """A version-16 STGC file of scheme 1 -> (side information, lm_blob, stego bytes);
     'cover_crc32' / 'payload_crc32' when the header carries the checksum extension."""
     scheme = pee_scheme(data)
+    if scheme == PEE_SCHEME_ROI:
+        raise ValueError("a ROI-protected MED-PEE container (scheme byte 4): use parse_pee_roi_bytes")
     if scheme == PEE_SCHEME_GATE:
         raise ValueError("a gated MED-PEE container (scheme byte 3): use parse_pee_gate_bytes")
     if scheme != 1:

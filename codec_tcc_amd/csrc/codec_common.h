@@ -278,6 +278,47 @@ __device__ int block_max_i32(int x, int* sh) {
     return r;
 }
 
+// ---- MED-PEE region of interest (codec_pee.hip, "region of interest"; include/codec_tcc_roi.h)
+struct PeeRoi {
+    int i0, ni, j0, nj;   // protected candidate rows [i0, i0 + ni) and columns [j0, j0 + nj); ni = 0: none
+    uint32_t w0, w2;      // the record words
+};
+__device__ __forceinline__ PeeRoi pee_roi_words(uint32_t w0, uint32_t w2) {
+    PeeRoi R;
+    R.i0 = (int)(w0 >> 17);
+    R.ni = max((int)(w2 >> 17) - R.i0, 0);
+    R.j0 = (int)((w0 & 0xFFFFu) >> 1);
+    R.nj = max((int)((w2 & 0xFFFFu) >> 1) - R.j0, 0);
+    R.w0 = w0; R.w2 = w2;
+    return R;
+}
+// slice b's rectangle of the embed side's device array rps [B][4] (NULL: none).  Empty or
+// out-of-range values (the host layer refuses them) count as no rectangle.
+__device__ __forceinline__ PeeRoi pee_roi_slice(const int32_t* __restrict__ rps, int b) {
+    if (!rps) return pee_roi_words(0u, 0u);
+    const int y0 = rps[4 * b], x0 = rps[4 * b + 1], y1 = rps[4 * b + 2], x1 = rps[4 * b + 3];
+    const bool ok = (y0 >= 0) & (x0 >= 0) & (y0 < y1) & (x0 < x1) & (y1 <= 65535) & (x1 <= 65535);
+    return ok ? pee_roi_words(((uint32_t)y0 << 16) | (uint32_t)x0, ((uint32_t)y1 << 16) | (uint32_t)x1)
+              : pee_roi_words(0u, 0u);
+}
+// the rectangle a record carries (use = 0: the call ignores the two words, codec_pee_gate_extract)
+__device__ __forceinline__ PeeRoi pee_rec_roi(const codec_pee_meta* M, int use) {
+    return use ? pee_roi_words((uint32_t)M->reserved[0], (uint32_t)M->reserved[2]) : pee_roi_words(0u, 0u);
+}
+__device__ __forceinline__ bool pee_roi_in(const PeeRoi& R, int i, int j) {
+    return ((unsigned)(i - R.i0) < (unsigned)R.ni) & ((unsigned)(j - R.j0) < (unsigned)R.nj);
+}
+
+// What a kernel's trailing argument pack `ROI... roi` says about rectangles.  Empty (every
+// instantiation that existed before the rectangles did, with its argument list, symbol-for-symbol
+// kernarg layout and instruction text): none.  The embed side's _roi launches pass the device
+// array (const int32_t*), the extract side's the tag PeeRoiRec: "take it from the record".
+struct PeeRoiRec {};
+__device__ __forceinline__ PeeRoi pee_roi_arg(int) { return pee_roi_words(0u, 0u); }
+__device__ __forceinline__ PeeRoi pee_roi_arg(int b, const int32_t* rps) { return pee_roi_slice(rps, b); }
+__device__ __forceinline__ PeeRoi pee_roi_arg(const codec_pee_meta*) { return pee_roi_words(0u, 0u); }
+__device__ __forceinline__ PeeRoi pee_roi_arg(const codec_pee_meta* M, PeeRoiRec) { return pee_rec_roi(M, 1); }
+
 template <typename T> struct Vec8;
 template <> struct Vec8<uint16_t> { typedef uint4 type; };
 template <> struct Vec8<uint8_t> { typedef uint2 type; };
@@ -392,6 +433,13 @@ static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; 
 // call of another shape than the workspace was last used for zeroes that layout first (on
 // `stream`) and the shape is recorded, so the earlier shape's next call zeroes its own again.
 int pee_workspace_enter(const codec_pee_params* P, void* workspace, void* stream);
+
+// the ROI entries' own argument check (include/codec_tcc_roi.h): the record words hold 16 bits per coordinate
+#define PEE_ROI_MAX_DIM 65535   // = CODEC_PEE_ROI_MAX_DIM
+static inline int pee_roi_dim_check(const codec_pee_params* P, const char* who) {
+    if (P->H > PEE_ROI_MAX_DIM || P->W > PEE_ROI_MAX_DIM) return set_err(CODEC_EINVAL, "%s: H and W must be <= 65535", who);
+    return 0;
+}
 
 // CUs of the current device (cached per device): slice-serial dispatch decisions
 static inline int device_cu_count() {

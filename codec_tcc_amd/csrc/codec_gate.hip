@@ -22,6 +22,7 @@
 // pass (k_pee_gate_zero): the tail of the workspace carries nothing from call to call.
 #include "codec_common.h"
 #include "codec_tcc_gate.h"
+#include "codec_tcc_roi.h"
 
 #define GT_CLASSES CODEC_PEE_GATE_CLASSES
 #define GT_TMAX CODEC_PEE_GATE_TMAX
@@ -51,9 +52,12 @@ __device__ __forceinline__ int gt_class(int d) {
     return d <= 4 ? d : (x >= 128 ? 15 : j);
 }
 
-// bin update for the (up to) four candidates of one item: packed byte counters, lane-private
+// bin update for the (up to) four candidates of one item: packed byte counters, lane-private.
+// which: the first `which` candidates count; MASK (the instantiations with rectangles): bit q of
+// `which` set = candidate q counts (it exists and lies outside the slice's rectangle)
+template <bool MASK>
 __device__ __forceinline__ void gt_add4(uint32_t* cnt, int tid, const int (&x)[4], const int (&a)[4],
-                                        const int (&bb)[4], const int (&cc)[4], int nq, int tmax, int maxval,
+                                        const int (&bb)[4], const int (&cc)[4], int which, int tmax, int maxval,
                                         int g_fixed) {
     int ad[4];
     uint32_t inc[4];
@@ -66,7 +70,7 @@ __device__ __forceinline__ void gt_add4(uint32_t* cnt, int tid, const int (&x)[4
         const int d = max(max(a[q], bb[q]), cc[q]) - min(min(a[q], bb[q]), cc[q]);
         const int j = g_fixed >= 0 ? (d <= g_fixed ? 0 : GT_CLASSES - 1) : gt_class(d);
         ad[q] = (row * 4 + (j >> 2)) * 256 + tid;
-        inc[q] = q < nq ? 1u << (8 * (j & 3)) : 0u;
+        inc[q] = (MASK ? ((which >> q) & 1) != 0 : q < which) ? 1u << (8 * (j & 3)) : 0u;
     }
 #pragma unroll
     for (int q = 1; q < 4; ++q)
@@ -132,13 +136,15 @@ __device__ void gt_select(const uint32_t* tbl, int tmax, int t_fixed, int g_fixe
     if (k_out) *k_out = (int32_t)(have ? bestK : k_inf);
 }
 
-template <typename T, bool VEC>
+// ROI... roi: nothing, or the slices' rectangles (codec_pee_roi_capacity; codec_common.h, pee_roi_arg)
+template <typename T, bool VEC, typename... ROI>
 __global__ __launch_bounds__(256) void k_pee_gate_table(const T* __restrict__ img, int H, int W, int maxval, int tmax,
                                                         int t_fixed, int g_fixed, uint32_t* __restrict__ gbins_all,
                                                         uint32_t* __restrict__ arrivals,
                                                         const int32_t* __restrict__ lengths, uint32_t* __restrict__ n_out,
                                                         uint32_t* __restrict__ hs_out, int32_t* __restrict__ t_out,
-                                                        int32_t* __restrict__ g_out, int32_t* __restrict__ k_out) {
+                                                        int32_t* __restrict__ g_out, int32_t* __restrict__ k_out,
+                                                        ROI... roi) {
     typedef typename Vec8<T>::type V;
     __shared__ uint32_t cnt[(GT_TMAX + 1) * 4 * 256];   // [(tmax + 1) * 4][256] packed byte counters: 68 KB
     __shared__ uint32_t bins[GT_BINS];
@@ -146,6 +152,9 @@ __global__ __launch_bounds__(256) void k_pee_gate_table(const T* __restrict__ im
     const int b = blockIdx.y, tid = threadIdx.x;
     const int nw = (tmax + 1) * 4, nb = (tmax + 1) * GT_CLASSES;
     const T* src = img + (size_t)b * H * W;
+    // the slice's rectangle (codec_pee_roi_capacity; NULL: none): protected candidates fall into no class
+    constexpr bool HAS_ROI = sizeof...(ROI) != 0;
+    const PeeRoi R = pee_roi_arg(b, roi...);
     for (int w = 0; w < nw; ++w) cnt[w * 256 + tid] = 0u;
     for (int i = tid; i < nb; i += 256) bins[i] = 0u;
     __syncthreads();
@@ -158,11 +167,17 @@ __global__ __launch_bounds__(256) void k_pee_gate_table(const T* __restrict__ im
         for (uint32_t it = i0 + (uint32_t)tid; it < i1; it += 256 * U) {
             V v0[U], v1[U];
             bool in[U];
+            int okm[U];   // with rectangles: the item's candidates outside its slice's
 #pragma unroll
             for (int k = 0; k < U; ++k) {
                 const uint32_t ik = it + 256u * k;
                 in[k] = ik < i1;
                 const uint32_t r = ik / CR, c = ik - r * CR;
+                okm[k] = 0;
+                if constexpr (HAS_ROI) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) okm[k] |= (in[k] && !pee_roi_in(R, (int)r, (int)(4u * c) + q)) ? 1 << q : 0;
+                }
                 const size_t o0 = in[k] ? (size_t)(2 * r) * W + (size_t)c * 8 : 0;   // clamped: a valid address
                 v0[k] = *reinterpret_cast<const V*>(src + o0);
                 v1[k] = *reinterpret_cast<const V*>(src + o0 + W);
@@ -175,7 +190,7 @@ __global__ __launch_bounds__(256) void k_pee_gate_table(const T* __restrict__ im
                     x[q] = (int)gt_px(v1[k], 2 * q + 1); a[q] = (int)gt_px(v1[k], 2 * q);
                     bb[q] = (int)gt_px(v0[k], 2 * q + 1); cc[q] = (int)gt_px(v0[k], 2 * q);
                 }
-                gt_add4(cnt, tid, x, a, bb, cc, in[k] ? 4 : 0, tmax, maxval, g_fixed);
+                gt_add4<HAS_ROI>(cnt, tid, x, a, bb, cc, HAS_ROI ? okm[k] : (in[k] ? 4 : 0), tmax, maxval, g_fixed);
             }
         }
     } else {
@@ -188,7 +203,7 @@ __global__ __launch_bounds__(256) void k_pee_gate_table(const T* __restrict__ im
             const size_t y = 2 * (size_t)i + 1, xx = 2 * (size_t)j + 1;
             x[0] = src[y * W + xx]; a[0] = src[y * W + xx - 1];
             bb[0] = src[(y - 1) * W + xx]; cc[0] = src[(y - 1) * W + xx - 1];
-            gt_add4(cnt, tid, x, a, bb, cc, 1, tmax, maxval, g_fixed);
+            gt_add4<HAS_ROI>(cnt, tid, x, a, bb, cc, pee_roi_in(R, i, j) ? 0 : 1, tmax, maxval, g_fixed);
         }
     }
     __syncthreads();
@@ -251,6 +266,11 @@ static int gate_check(const codec_pee_params* P, int32_t tmax, int32_t t_fixed, 
     return 0;
 }
 
+static int gate_capacity(const codec_pee_params* P, const void* cover, int32_t tmax, int32_t t_fixed, int32_t g_fixed,
+                         const int32_t* lengths, const int32_t* rps, uint32_t* n, uint32_t* hs, int32_t* t_out,
+                         int32_t* g_out, int32_t* k_out, void* workspace, size_t workspace_bytes, void* stream,
+                         const char* who, bool roi);
+
 extern "C" {
 
 size_t codec_pee_gate_workspace_bytes(const codec_pee_params* P, int32_t tmax) {
@@ -263,13 +283,25 @@ size_t codec_pee_gate_workspace_bytes(const codec_pee_params* P, int32_t tmax) {
 int codec_pee_gate_capacity(const codec_pee_params* P, const void* cover, int32_t tmax, int32_t t_fixed,
                             int32_t g_fixed, const int32_t* lengths, uint32_t* n, uint32_t* hs, int32_t* t_out,
                             int32_t* g_out, int32_t* k_out, void* workspace, size_t workspace_bytes, void* stream) {
-    int rc = gate_check(P, tmax, t_fixed, g_fixed, "codec_pee_gate_capacity");
+    return gate_capacity(P, cover, tmax, t_fixed, g_fixed, lengths, nullptr, n, hs, t_out, g_out, k_out, workspace,
+                         workspace_bytes, stream, "codec_pee_gate_capacity", false);
+}
+
+}  // extern "C"
+
+// the table pass of codec_pee_gate_capacity and codec_pee_roi_capacity (rps: per-slice
+// rectangles on the device, NULL for none; `roi`: the call is a ROI call and checks as one)
+static int gate_capacity(const codec_pee_params* P, const void* cover, int32_t tmax, int32_t t_fixed, int32_t g_fixed,
+                         const int32_t* lengths, const int32_t* rps, uint32_t* n, uint32_t* hs, int32_t* t_out,
+                         int32_t* g_out, int32_t* k_out, void* workspace, size_t workspace_bytes, void* stream,
+                         const char* who, bool roi) {
+    int rc = gate_check(P, tmax, t_fixed, g_fixed, who);
     if (rc) return rc;
     const size_t base = codec_pee_workspace_bytes(P);
     if (!base) return CODEC_EINVAL;   // codec_pee_workspace_bytes set the text
-    if (!cover || !workspace) return set_err(CODEC_EINVAL, "codec_pee_gate_capacity: NULL pointer argument");
-    if ((t_out || g_out || k_out) && !lengths)
-        return set_err(CODEC_EINVAL, "codec_pee_gate_capacity: t_out / g_out / k_out need lengths");
+    if (roi && (rc = pee_roi_dim_check(P, who))) return rc;
+    if (!cover || !workspace) return set_err(CODEC_EINVAL, "%s: NULL pointer argument", who);
+    if ((t_out || g_out || k_out) && !lengths) return set_err(CODEC_EINVAL, "%s: t_out / g_out / k_out need lengths", who);
     if (workspace_bytes < codec_pee_gate_workspace_bytes(P, tmax)) return set_err(CODEC_EINVAL, "workspace too small");
     hipStream_t st = as_stream(stream);
     // the registry, as every workspace-taking call: the bins lie behind THIS shape's layout, so on
@@ -288,14 +320,46 @@ int codec_pee_gate_capacity(const codec_pee_params* P, const void* cover, int32_
     const long long units = vec ? (long long)(P->H / 2) * (P->W / 8) : (long long)(P->H / 2) * (P->W / 2);
     ProfScope prof(st, CODEC_K_PEE_GATE_TABLE);
     dim3 grid((unsigned)std::max(1LL, (units + GT_PER_WG - 1) / GT_PER_WG), (unsigned)P->B);
-#define PGT(TT, VV) hipLaunchKernelGGL((k_pee_gate_table<TT, VV>), grid, dim3(256), 0, st, static_cast<const TT*>(cover), \
-                                       P->H, P->W, P->maxval, (int)tmax, (int)t_fixed, (int)g_fixed, gbins, arrivals, lengths, \
-                                       n, hs, t_out, g_out, k_out)
-    if (P->bytes == 2) { if (vec) PGT(uint16_t, true); else PGT(uint16_t, false); }
-    else { if (vec) PGT(uint8_t, true); else PGT(uint8_t, false); }
+#define PGT(TT, VV, ...) hipLaunchKernelGGL((k_pee_gate_table<TT, VV, ##__VA_ARGS__>), grid, dim3(256), 0, st, \
+                                            static_cast<const TT*>(cover), P->H, P->W, P->maxval, (int)tmax, (int)t_fixed, \
+                                            (int)g_fixed, gbins, arrivals, lengths, n, hs, t_out, g_out, k_out
+    if (rps) {
+        if (P->bytes == 2) { if (vec) PGT(uint16_t, true, const int32_t*), rps); else PGT(uint16_t, false, const int32_t*), rps); }
+        else { if (vec) PGT(uint8_t, true, const int32_t*), rps); else PGT(uint8_t, false, const int32_t*), rps); }
+    } else {
+        if (P->bytes == 2) { if (vec) PGT(uint16_t, true)); else PGT(uint16_t, false)); }
+        else { if (vec) PGT(uint8_t, true)); else PGT(uint8_t, false)); }
+    }
 #undef PGT
     LAUNCH_CHECK("k_pee_gate_table");
     return 0;
+}
+
+extern "C" {
+
+int codec_pee_roi_capacity(const codec_pee_params* P, const void* cover, int32_t tmax, int32_t t_fixed,
+                           int32_t g_fixed, const int32_t* lengths, const int32_t* roi, uint32_t* n, uint32_t* hs,
+                           int32_t* t_out, int32_t* g_out, int32_t* k_out, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+    return gate_capacity(P, cover, tmax, t_fixed, g_fixed, lengths, roi, n, hs, t_out, g_out, k_out, workspace,
+                         workspace_bytes, stream, "codec_pee_roi_capacity", true);
+}
+
+int codec_pee_roi_embed_auto(const codec_pee_params* P, const void* cover, void* stego, const uint64_t* payload,
+                             const int32_t* lengths, int32_t tmax, int32_t t_fixed, int32_t g_fixed, const int32_t* roi,
+                             int32_t* t_out, int32_t* g_out, codec_pee_meta* meta, uint64_t* lm, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    int rc = gate_check(P, tmax, t_fixed, g_fixed, "codec_pee_roi_embed_auto");
+    if (rc) return rc;
+    if (!codec_pee_workspace_bytes(P)) return CODEC_EINVAL;   // it set the text
+    if ((rc = pee_roi_dim_check(P, "codec_pee_roi_embed_auto"))) return rc;
+    if (!cover || !stego || !payload || !lengths || !t_out || !g_out || !meta || !lm || !workspace)
+        return set_err(CODEC_EINVAL, "codec_pee_roi_embed_auto: NULL pointer argument");
+    rc = codec_pee_roi_capacity(P, cover, tmax, t_fixed, g_fixed, lengths, roi, nullptr, nullptr, t_out, g_out, nullptr,
+                                workspace, workspace_bytes, stream);
+    if (rc) return rc;
+    return codec_pee_roi_embed(P, cover, stego, payload, lengths, t_out, g_out, roi, meta, lm, workspace, workspace_bytes,
+                               stream);
 }
 
 int codec_pee_gate_embed_auto(const codec_pee_params* P, const void* cover, void* stego, const uint64_t* payload,

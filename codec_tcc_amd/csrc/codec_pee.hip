@@ -14,6 +14,7 @@
 //            -> k_pee_recover (prefix tiles: bits + restored pixels)
 #include "codec_common.h"
 #include "codec_tcc_ext.h"
+#include "codec_tcc_roi.h"
 
 #include <map>
 #include <mutex>
@@ -80,16 +81,30 @@ __device__ __forceinline__ PeeCand pee_classify(int x, int a, int b, int c, int 
 // (a shift by 0 never overflows, whatever the cover holds above maxval).  GATE = false
 // instantiations compile to the code they were before.
 #define PEE_GATE_OFF 0x7FFFFFFF   // every candidate active
+// ---- region of interest (tests/pee_roi_spec.py; include/codec_tcc_roi.h): a second, purely
+// geometric reason for a candidate to be inactive.  The slice's half-open pixel rectangle
+// (y0, x0, y1, x1) travels as the two record words w0 = y0 << 16 | x0 (reserved[0]) and
+// w2 = y1 << 16 | x1 (reserved[2]; 0 = none).  Candidate (i, j) sits at pixel (2i + 1, 2j + 1),
+// so it is protected iff y0 >> 1 <= i < y1 >> 1 and x0 >> 1 <= j < x1 >> 1: two unsigned
+// compares against per-slice (scalar) values.  Both sides derive the candidate ranges from the
+// WORDS, so an embed and the extract of its record always agree, whatever the array held; a
+// rectangle only changes which candidates count as active and never an address.  The GATE =
+// true instantiations carry it (a uniform per-slice load); GATE = false ones never see it.
+// (struct PeeRoi and its helpers: codec_common.h, shared with codec_gate.hip's table pass)
+// (pee_roi_arg, PeeRoiRec: what a kernel's trailing argument pack `ROI... roi` says -- codec_common.h)
+// (i, j) = the candidate's row and column on the candidate lattice; GATE = false ignores them
 template <bool GATE>
-__device__ __forceinline__ int pee_gate_t(int a, int b, int c, int T, int G) {
+__device__ __forceinline__ int pee_gate_t(int a, int b, int c, int T, int G, const PeeRoi& R, int i, int j) {
     if constexpr (!GATE) return T;
     const int d = max(max(a, b), c) - min(min(a, b), c);
-    return d <= G ? T : 0;
+    const int t = d <= G ? T : 0;
+    return pee_roi_in(R, i, j) ? 0 : t;   // folds away where the kernel has no rectangle (pee_roi_arg)
 }
 // classification at the candidate's own threshold *te
 template <bool GATE>
-__device__ __forceinline__ PeeCand pee_classify_g(int x, int a, int b, int c, int T, int maxval, int G, int* te) {
-    *te = pee_gate_t<GATE>(a, b, c, T, G);
+__device__ __forceinline__ PeeCand pee_classify_g(int x, int a, int b, int c, int T, int maxval, int G, const PeeRoi& R,
+                                                  int i, int j, int* te) {
+    *te = pee_gate_t<GATE>(a, b, c, T, G, R, i, j);
     PeeCand r = pee_classify(x, a, b, c, *te, maxval);
     if constexpr (GATE) r.safe |= *te == 0;
     return r;
@@ -180,11 +195,11 @@ struct Quad {
 // 8 loads issued up front), tiles swept grid-stride over the whole batch in address order
 // (global tile g = slice * ntiles + t), so the resident waves read one moving window of
 // HBM; the wave's shuffle reduction writes the tile count directly (no LDS, no barrier).
-template <typename T, bool NT, bool GATE = false>
+template <typename T, bool NT, bool GATE = false, typename... ROI>
 __global__ __launch_bounds__(256) void k_pee_scan(const T* __restrict__ cover, T* __restrict__ stego, int H, int W,
                                                   int T0, int maxval, uint32_t* __restrict__ tile_cnt_all,
                                                   int ntiles_max, int B, const int32_t* __restrict__ tps,
-                                                  const int32_t* __restrict__ gps) {
+                                                  const int32_t* __restrict__ gps, ROI... roi) {
     typedef typename Vec8<T>::type V;
     const size_t npx = (size_t)H * W;
     const int CR = W / 8, hc = H / 2;
@@ -197,16 +212,19 @@ __global__ __launch_bounds__(256) void k_pee_scan(const T* __restrict__ cover, T
         const uint32_t b = g / ntiles, t = g - b * ntiles;
         const int Tthr = tps ? tps[b] : T0;   // per-slice threshold (capacity control) or one for all
         const int G = GATE ? gps[b] : PEE_GATE_OFF;
+        const PeeRoi R = pee_roi_arg((int)b, roi...);
         const T* src = cover + b * npx;
         T* dst = stego + b * npx;
         V v0[4], v1[4];
         size_t o0[4];
+        int ri[4], cj[4];   // the item's candidate row and first candidate column (ROI only)
         bool ok[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const uint32_t it = t * 256u + (uint32_t)(u * 64 + lane);
             ok[u] = it < items;
             const uint32_t r = it / (uint32_t)CR, c = it - r * (uint32_t)CR;
+            ri[u] = (int)r; cj[u] = (int)(4u * c);
             o0[u] = (size_t)(2 * r) * W + (size_t)c * 8;
             if (ok[u]) {
                 v0[u] = ldv<NT>(reinterpret_cast<const V*>(src + o0[u]));
@@ -228,7 +246,7 @@ __global__ __launch_bounds__(256) void k_pee_scan(const T* __restrict__ cover, T
                     x = (int)px8(v1[u], 2 * k + 1); a = (int)px8(v1[u], 2 * k); bb = (int)px8(v0[u], 2 * k + 1); cc = (int)px8(v0[u], 2 * k);
                 }
                 int te;
-                const PeeCand pc = pee_classify_g<GATE>(x, a, bb, cc, Tthr, maxval, G, &te);
+                const PeeCand pc = pee_classify_g<GATE>(x, a, bb, cc, Tthr, maxval, G, R, ri[u], cj[u] + k, &te);
                 cnt += (pc.expand && pc.safe) ? 1u : 0u;
             }
         }
@@ -246,15 +264,16 @@ __global__ __launch_bounds__(256) void k_pee_scan(const T* __restrict__ cover, T
 }
 
 // ---- scan for any shape: counts only (the copy is a separate stream copy)
-template <typename T, bool GATE = false>
+template <typename T, bool GATE = false, typename... ROI>
 __global__ __launch_bounds__(256) void k_pee_count(const T* __restrict__ img, int H, int W, int T0, int maxval,
                                                    int tiles_per_wg, uint32_t* __restrict__ tile_cnt_all,
                                                    int ntiles_max, const int32_t* __restrict__ tps,
-                                                   const int32_t* __restrict__ gps) {
+                                                   const int32_t* __restrict__ gps, ROI... roi) {
     __shared__ uint32_t sh[8];
     const int b = blockIdx.y;
     const int Tthr = tps ? tps[b] : T0;
     const int G = GATE ? gps[b] : PEE_GATE_OFF;
+    const PeeRoi R = pee_roi_arg(b, roi...);
     const T* src = img + (size_t)b * H * W;
     const int wc = W / 2, nc = (H / 2) * wc;
     const int ntiles = (nc + PEE_TILE - 1) / PEE_TILE;
@@ -270,7 +289,7 @@ __global__ __launch_bounds__(256) void k_pee_count(const T* __restrict__ img, in
                 int x, a, bb, cc;
                 pee_load(src, W, wc, k, &x, &a, &bb, &cc);
                 int te;
-                const PeeCand pc = pee_classify_g<GATE>(x, a, bb, cc, Tthr, maxval, G, &te);
+                const PeeCand pc = pee_classify_g<GATE>(x, a, bb, cc, Tthr, maxval, G, R, k / wc, k - (k / wc) * wc, &te);
                 cnt += (pc.expand && pc.safe) ? 1u : 0u;
             }
         }
@@ -280,14 +299,14 @@ __global__ __launch_bounds__(256) void k_pee_count(const T* __restrict__ img, in
 }
 
 // ---- per slice: exclusive tile offsets, capacity, tile holding bit L-1, exact `end`
-template <typename T, bool GATE = false>
+template <typename T, bool GATE = false, typename... ROI>
 __global__ __launch_bounds__(256) void k_pee_locate(const T* __restrict__ img, int H, int W, int T0, int maxval,
                                                     const int32_t* __restrict__ lengths,
                                                     const uint32_t* __restrict__ tile_cnt_all,
                                                     uint32_t* __restrict__ tile_off_all, int ntiles_max,
                                                     codec_pee_meta* __restrict__ meta_all,
                                                     const int32_t* __restrict__ tps,
-                                                    const int32_t* __restrict__ gps) {
+                                                    const int32_t* __restrict__ gps, ROI... roi) {
     __shared__ uint32_t sh[8];
     __shared__ int s_tile;
     __shared__ uint32_t s_base;
@@ -295,6 +314,7 @@ __global__ __launch_bounds__(256) void k_pee_locate(const T* __restrict__ img, i
     const int b = blockIdx.x;
     const int Tthr = tps ? tps[b] : T0;
     const int G = GATE ? gps[b] : PEE_GATE_OFF;
+    const PeeRoi R = pee_roi_arg(b, roi...);
     const int wc = W / 2, nc = (H / 2) * wc;
     const int ntiles = (nc + PEE_TILE - 1) / PEE_TILE;
     const uint32_t* cnt = tile_cnt_all + (size_t)b * ntiles_max;
@@ -325,7 +345,7 @@ __global__ __launch_bounds__(256) void k_pee_locate(const T* __restrict__ img, i
                 int x, a, bb, cc;
                 pee_load(src, W, wc, k, &x, &a, &bb, &cc);
                 int te;
-                const PeeCand pc = pee_classify_g<GATE>(x, a, bb, cc, Tthr, maxval, G, &te);
+                const PeeCand pc = pee_classify_g<GATE>(x, a, bb, cc, Tthr, maxval, G, R, k / wc, k - (k / wc) * wc, &te);
                 if (pc.expand && pc.safe) { flags |= 1u << u; ++local; }
             }
         }
@@ -364,23 +384,24 @@ __global__ __launch_bounds__(256) void k_pee_locate(const T* __restrict__ img, i
         M->flags = 0;
         // reserved[1] = 0 says "ungated" to every reader: written here too (the record buffer
         // is the caller's, not zeroed on this path)
-        M->reserved[0] = 0; M->reserved[1] = GATE ? G + 1 : 0; M->reserved[2] = 0;
+        M->reserved[0] = (int)R.w0; M->reserved[1] = GATE ? G + 1 : 0; M->reserved[2] = (int)R.w2;   // no rectangle: 0
     }
 }
 
 // ---- embed: prefix tiles only
-template <typename T, bool VEC, bool GATE = false>
+template <typename T, bool VEC, bool GATE = false, typename... ROI>
 __global__ __launch_bounds__(256) void k_pee_embed(const T* __restrict__ cover, T* __restrict__ stego, int H, int W,
                                                    const u64* __restrict__ payload_all, int pw,
                                                    const uint32_t* __restrict__ tile_off_all, int ntiles_max,
                                                    codec_pee_meta* __restrict__ meta_all,
-                                                   u64* __restrict__ lm_all, int lmw) {
+                                                   u64* __restrict__ lm_all, int lmw, ROI... roi) {
     __shared__ uint32_t sh[8];
     __shared__ uint32_t lm32[PEE_TILE / 32];
     const int b = blockIdx.y;
     codec_pee_meta* M = meta_all + b;
     const int tile_end = M->tile_end, end = M->end, Tthr = M->T, maxval = M->maxval;
     const int G = GATE ? pee_rec_gate(M) : PEE_GATE_OFF;   // k_pee_locate wrote it
+    const PeeRoi R = pee_roi_arg(M, roi...);                // and the rectangle's words
     const int wc = W / 2;
     const size_t npx = (size_t)H * W;
     const T* src = cover + b * npx;
@@ -400,7 +421,8 @@ __global__ __launch_bounds__(256) void k_pee_embed(const T* __restrict__ cover, 
         for (int u = 0; u < 4; ++u) {
             pc[u].expand = pc[u].safe = pc[u].right = false;
             if (k0 + u <= end) {
-                pc[u] = pee_classify_g<GATE>(q.x[u], q.a[u], q.b[u], q.c[u], Tthr, maxval, G, &te[u]);
+                pc[u] = pee_classify_g<GATE>(q.x[u], q.a[u], q.b[u], q.c[u], Tthr, maxval, G, R, (k0 + u) / wc,
+                                             (k0 + u) - ((k0 + u) / wc) * wc, &te[u]);
                 local += (pc[u].expand && pc[u].safe) ? 1u : 0u;
             }
         }
@@ -609,17 +631,18 @@ __global__ __launch_bounds__(256) void k_pee_ehist(const T* __restrict__ img, in
 // workgroup-per-tile k_pee_dcount at 256 x 2048^2).  (A wave-per-tile embed measured
 // slower than k_pee_embed -- 0.109 vs 0.099 ms: its cursor needs a scan per item slot
 // followed by a dependent payload load -- and was dropped.)
-template <typename T, bool GATE = false>
+template <typename T, bool GATE = false, typename... ROI>
 __global__ __launch_bounds__(256) void k_pee_dcount_w(const T* __restrict__ stego, int H, int W,
                                                       const codec_pee_meta* __restrict__ meta_all,
                                                       const u64* __restrict__ lm_all, int lmw,
-                                                      uint32_t* __restrict__ tile_cnt_all, int ntiles_max) {
+                                                      uint32_t* __restrict__ tile_cnt_all, int ntiles_max, ROI... roi) {
     typedef typename Vec8<T>::type V;
     const int b = blockIdx.y;
     const codec_pee_meta* M = meta_all + b;
     const int end = pee_clamp_end(M->end, (H / 2) * (W / 2)), tile_end = pee_clamp_tile_end(M->tile_end, end);
     const int Tthr = M->T;
     const int G = GATE ? pee_rec_gate(M) : PEE_GATE_OFF;
+    const PeeRoi R = pee_roi_arg(M, roi...);
     const T* src = stego + (size_t)b * H * W;
     const u64* lm = lm_all + (size_t)b * lmw;
     const int lane = threadIdx.x & 63;
@@ -645,12 +668,17 @@ __global__ __launch_bounds__(256) void k_pee_dcount_w(const T* __restrict__ steg
             if (!ok[u]) continue;
             const int k0 = (int)(4 * ((uint32_t)t * 256u + (uint32_t)(u * 64 + lane)));
             const uint32_t nib = (uint32_t)(lm[k0 >> 6] >> (k0 & 63)) & 0xFu;   // 4 | k0: one word
+            int ri = 0, cj = 0;   // ROI only: the item's candidate row and first candidate column
+            if constexpr (sizeof...(ROI) != 0) {
+                ri = (k0 >> 2) / CR;
+                cj = 4 * ((k0 >> 2) - ri * CR);
+            }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 if (k0 + e > end || ((nib >> e) & 1u)) continue;
                 const int na = (int)get_px(v1[u], 2 * e), nb = (int)get_px(v0[u], 2 * e + 1), nw = (int)get_px(v0[u], 2 * e);
                 const int e2 = (int)get_px(v1[u], 2 * e + 1) - med3(na, nb, nw);
-                const int te = pee_gate_t<GATE>(na, nb, nw, Tthr, G);
+                const int te = pee_gate_t<GATE>(na, nb, nw, Tthr, G, R, ri, cj + e);
                 local += (e2 >= -2 * te && e2 < 2 * te) ? 1u : 0u;
             }
         }
@@ -664,18 +692,19 @@ __global__ __launch_bounds__(256) void k_pee_dcount_w(const T* __restrict__ steg
 // instead of seven -- the bit cursor is a wave scan plus the (double-buffered) totals of
 // the tile's earlier waves, location-map words are OR-reduced over 16 lanes with shuffles
 // and stored directly, the unsafe count goes out with one atomic per wave at the end.
-template <typename T, bool GATE = false>
+template <typename T, bool GATE = false, typename... ROI>
 __global__ __launch_bounds__(256) void k_pee_embed_v(const T* __restrict__ cover, T* __restrict__ stego, int H, int W,
                                                      const u64* __restrict__ payload_all, int pw,
                                                      const uint32_t* __restrict__ tile_off_all, int ntiles_max,
                                                      codec_pee_meta* __restrict__ meta_all,
-                                                     u64* __restrict__ lm_all, int lmw) {
+                                                     u64* __restrict__ lm_all, int lmw, ROI... roi) {
     typedef typename Vec8<T>::type V;
     __shared__ uint32_t wtot[2][4];
     const int b = blockIdx.y;
     codec_pee_meta* M = meta_all + b;
     const int tile_end = M->tile_end, end = M->end, Tthr = M->T, maxval = M->maxval;
     const int G = GATE ? pee_rec_gate(M) : PEE_GATE_OFF;   // k_pee_locate wrote it
+    const PeeRoi R = pee_roi_arg(M, roi...);                // and the rectangle's words
     const size_t npx = (size_t)H * W;
     const T* src = cover + b * npx;
     T* dst = stego + b * npx;
@@ -705,7 +734,7 @@ __global__ __launch_bounds__(256) void k_pee_embed_v(const T* __restrict__ cover
             pc[u].expand = pc[u].safe = pc[u].right = false;
             if (ok && k0 + u <= end) {
                 pc[u] = pee_classify_g<GATE>((int)get_px(v1, 2 * u + 1), (int)get_px(v1, 2 * u), (int)get_px(v0, 2 * u + 1),
-                                             (int)get_px(v0, 2 * u), Tthr, maxval, G, &te[u]);
+                                             (int)get_px(v0, 2 * u), Tthr, maxval, G, R, r, 4 * c + u, &te[u]);
                 local += (pc[u].expand && pc[u].safe) ? 1u : 0u;
             }
         }
@@ -781,11 +810,11 @@ __device__ __forceinline__ bool lm_bit(const u64* lm, int k, int lmw) {
     return (k >> 6) < lmw && ((lm[k >> 6] >> (k & 63)) & 1ull);
 }
 
-template <typename T, bool VEC, bool GATE = false>
+template <typename T, bool VEC, bool GATE = false, typename... ROI>
 __global__ __launch_bounds__(256) void k_pee_dcount(const T* __restrict__ stego, int H, int W,
                                                     const codec_pee_meta* __restrict__ meta_all,
                                                     const u64* __restrict__ lm_all, int lmw,
-                                                    uint32_t* __restrict__ tile_cnt_all, int ntiles_max) {
+                                                    uint32_t* __restrict__ tile_cnt_all, int ntiles_max, ROI... roi) {
     __shared__ uint32_t sh[8];
     const int b = blockIdx.y;
     const codec_pee_meta* M = meta_all + b;
@@ -793,6 +822,7 @@ __global__ __launch_bounds__(256) void k_pee_dcount(const T* __restrict__ stego,
     const int end = pee_clamp_end(M->end, (H / 2) * wc), tile_end = pee_clamp_tile_end(M->tile_end, end);
     const int Tthr = M->T;
     const int G = GATE ? pee_rec_gate(M) : PEE_GATE_OFF;
+    const PeeRoi R = pee_roi_arg(M, roi...);
     const T* src = stego + (size_t)b * H * W;
     const u64* lm = lm_all + (size_t)b * lmw;
     for (int t = blockIdx.x; t <= tile_end; t += gridDim.x) {
@@ -805,7 +835,7 @@ __global__ __launch_bounds__(256) void k_pee_dcount(const T* __restrict__ stego,
             const int k = k0 + u;
             if (k <= end && !lm_bit(lm, k, lmw)) {
                 const int e2 = q.x[u] - med3(q.a[u], q.b[u], q.c[u]);
-                const int te = pee_gate_t<GATE>(q.a[u], q.b[u], q.c[u], Tthr, G);
+                const int te = pee_gate_t<GATE>(q.a[u], q.b[u], q.c[u], Tthr, G, R, k / wc, k - (k / wc) * wc);
                 local += (e2 >= -2 * te && e2 < 2 * te) ? 1u : 0u;
             }
         }
@@ -835,12 +865,12 @@ __global__ __launch_bounds__(256) void k_pee_offsets(const codec_pee_meta* __res
     }
 }
 
-template <typename T, bool VEC, bool GATE = false>
+template <typename T, bool VEC, bool GATE = false, typename... ROI>
 __global__ __launch_bounds__(256) void k_pee_recover(const T* __restrict__ stego, T* __restrict__ cover, int H, int W,
                                                      const codec_pee_meta* __restrict__ meta_all,
                                                      const u64* __restrict__ lm_all, int lmw,
                                                      const uint32_t* __restrict__ tile_off_all, int ntiles_max,
-                                                     u64* __restrict__ payload_all, int pw) {
+                                                     u64* __restrict__ payload_all, int pw, ROI... roi) {
     __shared__ uint32_t sh[8];
     const int b = blockIdx.y;
     const codec_pee_meta* M = meta_all + b;
@@ -848,6 +878,7 @@ __global__ __launch_bounds__(256) void k_pee_recover(const T* __restrict__ stego
     const int end = pee_clamp_end(M->end, (H / 2) * wc), tile_end = pee_clamp_tile_end(M->tile_end, end);
     const int Tthr = M->T;
     const int G = GATE ? pee_rec_gate(M) : PEE_GATE_OFF;
+    const PeeRoi R = pee_roi_arg(M, roi...);
     const uint32_t plim = pee_bit_limit(M->L, pw);   // bits of rank >= min(L, 64 pw) are dropped
     const size_t npx = (size_t)H * W;
     const T* src = stego + b * npx;
@@ -871,7 +902,7 @@ __global__ __launch_bounds__(256) void k_pee_recover(const T* __restrict__ stego
             ps[u] = 0;
             if (act[u]) {
                 ps[u] = med3(q.a[u], q.b[u], q.c[u]);
-                te[u] = pee_gate_t<GATE>(q.a[u], q.b[u], q.c[u], Tthr, G);
+                te[u] = pee_gate_t<GATE>(q.a[u], q.b[u], q.c[u], Tthr, G, R, k / wc, k - (k / wc) * wc);
                 const int e2 = q.x[u] - ps[u];
                 inner[u] = e2 >= -2 * te[u] && e2 < 2 * te[u];
                 local += inner[u] ? 1u : 0u;
@@ -914,13 +945,13 @@ __global__ __launch_bounds__(256) void k_pee_recover(const T* __restrict__ stego
 // batch in address order; a workgroup iteration covers 4 whole tiles (u-slot u = tile
 // base/256 + u), and slots whose tile lies in the slice's prefix (<= tile_end) recover
 // bits and pixels in registers with a block scan for the cursor.
-template <typename T, bool NT, bool GATE = false>
+template <typename T, bool NT, bool GATE = false, typename... ROI>
 __global__ __launch_bounds__(256) void k_pee_restore_gs(const T* __restrict__ stego, T* __restrict__ cover, int H, int W,
                                                         uint32_t items_per_slice, uint32_t total_items,
                                                         const codec_pee_meta* __restrict__ meta_all,
                                                         const u64* __restrict__ lm_all, int lmw,
                                                         const uint32_t* __restrict__ tile_off_all, int ntiles_max,
-                                                        u64* __restrict__ payload_all, int pw) {
+                                                        u64* __restrict__ payload_all, int pw, ROI... roi) {
     typedef typename Vec8<T>::type V;
     __shared__ uint32_t sh[8];
     const int CR = W / 8;
@@ -930,12 +961,14 @@ __global__ __launch_bounds__(256) void k_pee_restore_gs(const T* __restrict__ st
     for (uint32_t base = blockIdx.x * 1024u; base < total_items; base += stride) {
         V a0[4], a1[4];
         size_t o0[4];
+        int ri[4] = {0, 0, 0, 0}, cj[4] = {0, 0, 0, 0};   // candidate row, first candidate column (ROI only)
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const uint32_t g = base + u * 256u + threadIdx.x;
             if (g < total_items) {
                 const uint32_t b = g / items_per_slice, it = g - b * items_per_slice;
                 const uint32_t r = it / CR, c = it - r * CR;
+                ri[u] = (int)r; cj[u] = (int)(4u * c);
                 o0[u] = b * npx + (size_t)(2 * r) * W + (size_t)c * 8;
                 a0[u] = ldv<NT>(reinterpret_cast<const V*>(stego + o0[u]));
                 a1[u] = ldv<NT>(reinterpret_cast<const V*>(stego + o0[u] + W));
@@ -951,6 +984,7 @@ __global__ __launch_bounds__(256) void k_pee_restore_gs(const T* __restrict__ st
                 // t < tiles_per_slice bounds every candidate index by nc whatever `end` says
                 const int end = M->end, Tthr = M->T;
                 const int G = GATE ? pee_rec_gate(M) : PEE_GATE_OFF;
+                const PeeRoi R = pee_roi_arg(M, roi...);
                 const uint32_t plim = pee_bit_limit(M->L, pw);   // as k_pee_recover
                 const u64* lm = lm_all + (size_t)b * lmw;
                 const int k0 = (int)t * PEE_TILE + 4 * threadIdx.x;
@@ -968,7 +1002,7 @@ __global__ __launch_bounds__(256) void k_pee_restore_gs(const T* __restrict__ st
                     if (act[q]) {
                         const int na = (int)get_px(a1[u], 2 * q), nb = (int)get_px(a0[u], 2 * q + 1), nw = (int)get_px(a0[u], 2 * q);
                         ps[q] = med3(na, nb, nw);
-                        te[q] = pee_gate_t<GATE>(na, nb, nw, Tthr, G);
+                        te[q] = pee_gate_t<GATE>(na, nb, nw, Tthr, G, R, ri[u], cj[u] + q);
                         const int e2 = xs[q] - ps[q];
                         inner[q] = e2 >= -2 * te[q] && e2 < 2 * te[q];
                         local += inner[q] ? 1u : 0u;
@@ -1070,6 +1104,7 @@ struct EmbedCount {
     uint32_t items;
     int Tthr, maxval;
     int G = PEE_GATE_OFF;   // GATE: the slice's gate (inactive candidates count nowhere)
+    PeeRoi R = {0, 0, 0, 0, 0u, 0u};   // GATE: the slice's rectangle (protected candidates neither)
     __device__ u64 operator()(int j) const {   // expandable | unsafe << 32 (a status word's value)
         typedef typename Vec8<T>::type V;
         const int lane = threadIdx.x & 63;
@@ -1085,7 +1120,8 @@ struct EmbedCount {
             for (int q = 0; q < 4; ++q) {
                 int te;
                 const PeeCand pc = pee_classify_g<GATE>((int)get_px(v1, 2 * q + 1), (int)get_px(v1, 2 * q),
-                                                        (int)get_px(v0, 2 * q + 1), (int)get_px(v0, 2 * q), Tthr, maxval, G, &te);
+                                                        (int)get_px(v0, 2 * q + 1), (int)get_px(v0, 2 * q), Tthr, maxval, G, R,
+                                                        (int)r, (int)(4u * cc) + q, &te);
                 n += (pc.expand && pc.safe) ? 1u : 0u;
                 un += pc.safe ? 0u : 1u;
             }
@@ -1110,6 +1146,7 @@ struct ExtractCount {
     uint32_t items;
     int end, Tthr;
     int G = PEE_GATE_OFF;   // GATE: the record's gate
+    PeeRoi R = {0, 0, 0, 0, 0u, 0u};   // GATE: the record's rectangle
     __device__ u64 operator()(int j) const {
         typedef typename Vec8<T>::type V;
         const int lane = threadIdx.x & 63;
@@ -1127,7 +1164,7 @@ struct ExtractCount {
                 if ((int)(4 * it) + q > end || ((lw >> q) & 1ull)) continue;
                 const int na = (int)get_px(v1, 2 * q), nb = (int)get_px(v0, 2 * q + 1), nw = (int)get_px(v0, 2 * q);
                 const int e2 = (int)get_px(v1, 2 * q + 1) - med3(na, nb, nw);
-                const int te = pee_gate_t<GATE>(na, nb, nw, Tthr, G);
+                const int te = pee_gate_t<GATE>(na, nb, nw, Tthr, G, R, (int)r, (int)(4u * cc) + q);
                 n += (e2 >= -2 * te && e2 < 2 * te) ? 1u : 0u;
             }
         }
@@ -1421,14 +1458,14 @@ __device__ __forceinline__ int pee_sc_tag(int epoch) { return epoch % 63 + 1; }
 #define PEE_X1_LB __launch_bounds__(256)
 #endif
 // GATE (codec_pee_gate_embed; never with SC): gps[b] is slice b's gate
-template <typename T, bool NT, bool INPLACE, bool SC = false, bool GATE = false>
+template <typename T, bool NT, bool INPLACE, bool SC = false, bool GATE = false, typename... ROI>
 __global__ PEE_E1_LB void k_pee_embed1(const T* __restrict__ cover, T* stego, int H, int W, int T0,
                                                     int maxval, const int32_t* __restrict__ lengths,
                                                     const u64* __restrict__ payload_all, int pw, int nchunks, int B,
                                                     u64* status_all, uint32_t* ctl, codec_pee_meta* meta_all,
                                                     u64* __restrict__ lm_all, int lmw, int mode, uint32_t spin_max,
                                                     int dbg_skip, uint32_t* diag, const int32_t* __restrict__ tps,
-                                                    int sc_epoch, int dbg_stale, const int32_t* __restrict__ gps) {
+                                                    int sc_epoch, int dbg_stale, const int32_t* __restrict__ gps, ROI... roi) {
     typedef typename Vec8<T>::type V;
     __shared__ u64 sh64[8];
     __shared__ uint32_t sh[8];
@@ -1458,6 +1495,7 @@ __global__ PEE_E1_LB void k_pee_embed1(const T* __restrict__ cover, T* stego, in
         const uint32_t L = (uint32_t)max(0, lengths[b]);
         const int Tthr = tps ? tps[b] : T0;   // per-slice threshold (capacity control) or one for all
         const int G = GATE ? gps[b] : PEE_GATE_OFF;
+        const PeeRoi R = pee_roi_arg(b, roi...);
         codec_pee_meta* M = meta_all + b;
         const T* src = cover + b * npx;
         T* dst = stego + b * npx;
@@ -1545,6 +1583,7 @@ __global__ PEE_E1_LB void k_pee_embed1(const T* __restrict__ cover, T* stego, in
             continue;
         }
         uint32_t esm = 0, safem = 0, rightm = 0;   // bit 4u+q
+        uint32_t protm = 0;                        // ROI: the candidates inside the slice's rectangle
         u64 packed = 0;
         uint32_t uns = 0;   // unsafe candidates (location-map bits when the chunk lies before `end`)
 #pragma unroll
@@ -1552,13 +1591,15 @@ __global__ PEE_E1_LB void k_pee_embed1(const T* __restrict__ cover, T* stego, in
             const uint32_t it = (uint32_t)c * PEE_CHUNK + u * 256u + tid;
             if (it < items) {
                 uint32_t n = 0;
+                const uint32_t ir = it / (uint32_t)CR, ic = it - ir * (uint32_t)CR;   // ROI only: the item's row pair, chunk
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     int te;
                     const PeeCand pc = pee_classify_g<GATE>((int)get_px(a1[u], 2 * q + 1), (int)get_px(a1[u], 2 * q),
                                                             (int)get_px(a0[u], 2 * q + 1), (int)get_px(a0[u], 2 * q), Tthr,
-                                                            maxval, G, &te);
+                                                            maxval, G, R, (int)ir, (int)(4u * ic) + q, &te);
                     const uint32_t bit = 1u << (4 * u + q);
+                    if constexpr (sizeof...(ROI) != 0) protm |= pee_roi_in(R, (int)ir, (int)(4u * ic) + q) ? bit : 0u;
                     if (pc.safe) safem |= bit;
                     if (pc.right) rightm |= bit;
                     if (pc.expand && pc.safe) { esm |= bit; ++n; }
@@ -1594,7 +1635,7 @@ __global__ PEE_E1_LB void k_pee_embed1(const T* __restrict__ cover, T* stego, in
                 bool to = false, fb = false;
                 LbSum ex;
                 if (INPLACE) ex = lb_exclusive(st, c, &to, &fb, spin_max, NoFallback(), fin_flag, L);
-                else ex = lb_exclusive<sc>(st, c, &to, &fb, spin_max, EmbedCount<T, GATE>{src, W, CR, items, Tthr, maxval, G},
+                else ex = lb_exclusive<sc>(st, c, &to, &fb, spin_max, EmbedCount<T, GATE>{src, W, CR, items, Tthr, maxval, G, R},
                                            fin_flag, L, tag, fin_val);
                 if (tid == 0) {
                     if constexpr (sc) {
@@ -1626,6 +1667,7 @@ __global__ PEE_E1_LB void k_pee_embed1(const T* __restrict__ cover, T* stego, in
                 if (L == 0) { M->end = -1; M->tile_end = -1; }   // status: below (out of place) / memset (in place)
                 if (sc) M->reserved[0] = M->reserved[1] = M->reserved[2] = 0;
                 if constexpr (GATE) M->reserved[1] = G + 1;   // the rest of the record was zeroed before the pass
+                if constexpr (sizeof...(ROI) != 0) { M->reserved[0] = (int)R.w0; M->reserved[2] = (int)R.w2; }
             }
             // the chunk holding `end` (or the last one on overflow) reports the capacity seen so
             // far: exact when it is the last chunk, else a lower bound (later chunks are not counted)
@@ -1699,7 +1741,9 @@ __global__ PEE_E1_LB void k_pee_embed1(const T* __restrict__ cover, T* stego, in
                     const int x = (int)get_px(a1[u], 2 * q + 1);
                     const int na = (int)get_px(a1[u], 2 * q), nb = (int)get_px(a0[u], 2 * q + 1), nw = (int)get_px(a0[u], 2 * q);
                     const int pr = med3(na, nb, nw);
-                    const int te = pee_gate_t<GATE>(na, nb, nw, Tthr, G);   // 0: the shift of an inactive candidate
+                    // 0: the shift of an inactive candidate (protm: inside the rectangle, found above)
+                    const int te = (sizeof...(ROI) != 0 && ((protm >> (4 * u + q)) & 1u))
+                                       ? 0 : pee_gate_t<GATE>(na, nb, nw, Tthr, G, PeeRoi{0, 0, 0, 0, 0u, 0u}, 0, 0);
                     const int nv_e = 2 * x - pr + (int)((field >> pre) & 1ull);   // p + 2e + bit
                     const int nv_s = (rb & bit) ? x + te : x - te;
                     const int nv = (proc & ((sb & bit) != 0u)) ? ((eb & bit) ? nv_e : nv_s) : x;
@@ -1821,13 +1865,13 @@ struct PeeReadAhead {
 // extract: chunks up to the one holding `end` recover bits + pixels (look-back over the
 // inner-candidate counts); later chunks are a plain copy (out of place) or skipped.
 // GATE (codec_pee_gate_extract; never with SC): the gate is the record's (pee_rec_gate)
-template <typename T, bool NT, bool INPLACE, bool SC = false, bool GATE = false>
+template <typename T, bool NT, bool INPLACE, bool SC = false, bool GATE = false, typename... ROI>
 __global__ PEE_X1_LB void k_pee_extract1(const T* stego, T* cover, int H, int W,
                                                       const codec_pee_meta* __restrict__ meta_all,
                                                       const u64* __restrict__ lm_all, int lmw, int nchunks, int B,
                                                       u64* status_all, uint32_t* ctl, u64* __restrict__ payload_all,
                                                       int pw, int mode, uint32_t spin_max, int dbg_skip, uint32_t* diag,
-                                                      int sc_epoch, int dbg_stale) {
+                                                      int sc_epoch, int dbg_stale, ROI... roi) {
     typedef typename Vec8<T>::type V;
     __shared__ u64 sh64[8];
     __shared__ uint32_t s_v, s_excl;
@@ -1868,6 +1912,7 @@ __global__ PEE_X1_LB void k_pee_extract1(const T* stego, T* cover, int H, int W,
         const codec_pee_meta* M = meta_all + b;
         const int end = pee_clamp_end(M->end, (int)(4u * items)), Tthr = M->T;   // nc = 4 items (8 | W)
         const int G = GATE ? pee_rec_gate(M) : PEE_GATE_OFF;
+        const PeeRoi R = pee_roi_arg(M, roi...);
         const uint32_t plim = pee_bit_limit(M->L, pw);   // bits of rank >= min(L, 64 pw) are dropped
 #ifdef PEE_X_COPYONLY   // diagnostic build (tools): every chunk a plain copy
         const int cend = -1;
@@ -1926,6 +1971,7 @@ __global__ PEE_X1_LB void k_pee_extract1(const T* stego, T* cover, int H, int W,
         }
         if (c <= cend) {
             uint32_t actm = 0, innm = 0;
+            uint32_t protm = 0;   // ROI: the active-by-map candidates inside the record's rectangle
             u64 packed = 0;
             if (!noticket) {   // the map words of the ticketed chunk, all four in flight at once
 #pragma unroll
@@ -1940,6 +1986,7 @@ __global__ PEE_X1_LB void k_pee_extract1(const T* stego, T* cover, int H, int W,
                 if (it >= items) continue;
                 const u64 lw = lwv[u] >> ((4 * it) & 63);   // 4 bits, same word
                 uint32_t n = 0;
+                const uint32_t ir = it / (uint32_t)CR, ic = it - ir * (uint32_t)CR;   // ROI only: the item's row pair, chunk
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int k = (int)(4 * it) + q;
@@ -1947,7 +1994,8 @@ __global__ PEE_X1_LB void k_pee_extract1(const T* stego, T* cover, int H, int W,
                     actm |= 1u << (4 * u + q);
                     const int na = (int)get_px(a1[u], 2 * q), nb = (int)get_px(a0[u], 2 * q + 1), nw = (int)get_px(a0[u], 2 * q);
                     const int p = med3(na, nb, nw);
-                    const int te = pee_gate_t<GATE>(na, nb, nw, Tthr, G);
+                    const int te = pee_gate_t<GATE>(na, nb, nw, Tthr, G, R, (int)ir, (int)(4u * ic) + q);
+                    if constexpr (sizeof...(ROI) != 0) protm |= pee_roi_in(R, (int)ir, (int)(4u * ic) + q) ? 1u << (4 * u + q) : 0u;
                     const int e2 = (int)get_px(a1[u], 2 * q + 1) - p;
                     if (e2 >= -2 * te && e2 < 2 * te) { innm |= 1u << (4 * u + q); ++n; }
                 }
@@ -1967,7 +2015,7 @@ __global__ PEE_X1_LB void k_pee_extract1(const T* stego, T* cover, int H, int W,
                     bool to = false, fb = false;
                     LbSum ex;
                     if (INPLACE) ex = lb_exclusive(st, c, &to, &fb, spin_max, NoFallback());
-                    else ex = lb_exclusive(st, c, &to, &fb, spin_max, ExtractCount<T, GATE>{src, lm, W, CR, items, end, Tthr, G},
+                    else ex = lb_exclusive(st, c, &to, &fb, spin_max, ExtractCount<T, GATE>{src, lm, W, CR, items, end, Tthr, G, R},
                                            nullptr, 0u, sc ? tag : -1);
                     if (tid == 0) {
                         if (publish) lb_store(st + c, LB_INC | ((ex.e + agg) & 0xFFFFFFFFull) | tagw);
@@ -1996,7 +2044,9 @@ __global__ PEE_X1_LB void k_pee_extract1(const T* stego, T* cover, int H, int W,
                     const int x = (int)get_px(a1[u], 2 * q + 1);
                     const int na = (int)get_px(a1[u], 2 * q), nb = (int)get_px(a0[u], 2 * q + 1), nw = (int)get_px(a0[u], 2 * q);
                     const int p = med3(na, nb, nw);
-                    const int te = pee_gate_t<GATE>(na, nb, nw, Tthr, G);   // 0: an inactive candidate stays
+                    // 0: an inactive candidate stays (protm: inside the rectangle, found above)
+                    const int te = (sizeof...(ROI) != 0 && ((protm >> (4 * u + q)) & 1u))
+                                       ? 0 : pee_gate_t<GATE>(na, nb, nw, Tthr, G, PeeRoi{0, 0, 0, 0, 0u, 0u}, 0, 0);
                     const int e2 = x - p;
                     const bool inner = (im & bit) != 0u;
                     bits |= (inner ? (uint32_t)(e2 & 1) : 0u) << __popc(im & (bit - 1u));
@@ -3617,13 +3667,15 @@ int codec_pee_embed(const codec_pee_params* P, const void* cover, void* stego, c
 }
 
 static int pee_embed_impl(const codec_pee_params* P, const void* cover, void* stego, const uint64_t* payload,
-                          const int32_t* lengths, const int32_t* tps, const int32_t* gps, codec_pee_meta* meta,
-                          uint64_t* lm, void* workspace, size_t workspace_bytes, void* stream);
+                          const int32_t* lengths, const int32_t* tps, const int32_t* gps, const int32_t* rps,
+                          codec_pee_meta* meta, uint64_t* lm, void* workspace, size_t workspace_bytes, void* stream,
+                          const char* who = "codec_pee_embed");
 
 int codec_pee_embed_ts(const codec_pee_params* P, const void* cover, void* stego, const uint64_t* payload,
                        const int32_t* lengths, const int32_t* tps, codec_pee_meta* meta, uint64_t* lm, void* workspace,
                        size_t workspace_bytes, void* stream) {
-    return pee_embed_impl(P, cover, stego, payload, lengths, tps, nullptr, meta, lm, workspace, workspace_bytes, stream);
+    return pee_embed_impl(P, cover, stego, payload, lengths, tps, nullptr, nullptr, meta, lm, workspace, workspace_bytes,
+                          stream);
 }
 
 // include/codec_tcc_gate.h: the embed with a per-slice smoothness gate.  Same routes as the
@@ -3634,17 +3686,32 @@ int codec_pee_gate_embed(const codec_pee_params* P, const void* cover, void* ste
                          const int32_t* lengths, const int32_t* t_slices, const int32_t* g_slices, codec_pee_meta* meta,
                          uint64_t* lm, void* workspace, size_t workspace_bytes, void* stream) {
     if (!t_slices || !g_slices) return set_err(CODEC_EINVAL, "codec_pee_gate_embed: NULL pointer argument");
-    return pee_embed_impl(P, cover, stego, payload, lengths, t_slices, g_slices, meta, lm, workspace, workspace_bytes, stream);
+    return pee_embed_impl(P, cover, stego, payload, lengths, t_slices, g_slices, nullptr, meta, lm, workspace,
+                          workspace_bytes, stream);
+}
+
+// include/codec_tcc_roi.h: the gated embed with a per-slice rectangle that is never modified
+// (roi: device int32 [B][4], or NULL for none).  The routes are the gated call's.
+int codec_pee_roi_embed(const codec_pee_params* P, const void* cover, void* stego, const uint64_t* payload,
+                        const int32_t* lengths, const int32_t* t_slices, const int32_t* g_slices, const int32_t* roi,
+                        codec_pee_meta* meta, uint64_t* lm, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = pee_check(P);
+    if (rc) return rc;
+    if ((rc = pee_roi_dim_check(P, "codec_pee_roi_embed"))) return rc;
+    if (!t_slices || !g_slices) return set_err(CODEC_EINVAL, "codec_pee_roi_embed: NULL pointer argument");
+    return pee_embed_impl(P, cover, stego, payload, lengths, t_slices, g_slices, roi, meta, lm, workspace, workspace_bytes,
+                          stream, "codec_pee_roi_embed");
 }
 
 }  // extern "C"
 
 // the embed's routes for one pixel type; gps: per-slice gates on the device
-// (codec_pee_gate_embed), or NULL for the ungated call
+// (codec_pee_gate_embed), or NULL for the ungated call; rps: per-slice rectangles on the device
+// (codec_pee_roi_embed; only with gps), or NULL
 template <typename TT>
 static int pee_embed_t(const codec_pee_params* P, const PeeCall& C, const TT* cover, TT* stego, const u64* payload,
-                       const int32_t* lengths, const int32_t* tps, const int32_t* gps, codec_pee_meta* meta, u64* lm,
-                       void* workspace) {
+                       const int32_t* lengths, const int32_t* tps, const int32_t* gps, const int32_t* rps,
+                       codec_pee_meta* meta, u64* lm, void* workspace) {
     constexpr bool U16 = std::is_same_v<TT, uint16_t>;
     const bool gate = gps != nullptr;
     const PeeWs& L = C.L;
@@ -3722,14 +3789,15 @@ static int pee_embed_t(const codec_pee_params* P, const PeeCall& C, const TT* co
                                     inplace ? lm : nullptr, inplace ? (size_t)P->B * P->lm_words * 8 : 0);
         if (rc) return rc;
         ProfScope prof(st, CODEC_K_PEE_EMBED1);
-        auto go = [&](auto kern) {
+        auto go = [&](auto kern, auto... roi) {   // roi: the rectangles, for the ROI instantiations
             hipLaunchKernelGGL(kern, dim3((unsigned)S.g), dim3(256), 0, st, cover, stego, P->H, P->W, P->T, P->maxval,
                                lengths, payload, P->payload_words, L.nchunks, P->B, S.stw, S.ctl, meta, lm, P->lm_words,
-                               S.mode, S.spin_max, S.dbg_skip, S.diag, tps, S.sc_epoch, S.dbg_stale, gps);
+                               S.mode, S.spin_max, S.dbg_skip, S.diag, tps, S.sc_epoch, S.dbg_stale, gps, roi...);
         };
         // gated: non-temporal accesses only (CODEC_NT is an A/B knob of the ungated kernels);
         // self-cleaning: out of place only (flat)
-        if (gate) pee_flag(inplace, [&](auto ip) { go(k_pee_embed1<TT, true, ip(), false, true>); });
+        if (rps) pee_flag(inplace, [&](auto ip) { go(k_pee_embed1<TT, true, ip(), false, true, const int32_t*>, rps); });
+        else if (gate) pee_flag(inplace, [&](auto ip) { go(k_pee_embed1<TT, true, ip(), false, true>); });
         else if (S.sc() && !inplace) pee_flag(nt, [&](auto n) { go(k_pee_embed1<TT, n(), false, true>); });
         else pee_flag(nt, inplace, [&](auto n, auto ip) { go(k_pee_embed1<TT, n(), ip(), false>); });
         LAUNCH_CHECK("k_pee_embed1");
@@ -3751,16 +3819,20 @@ static int pee_embed_t(const codec_pee_params* P, const PeeCall& C, const TT* co
             long long gw = knob("CODEC_PEE_SCAN_GS_WGS", 32768);   // tools/tune_pee.py
             if (gw > (tot + 3) / 4) gw = (tot + 3) / 4;
             if (gw < 1) gw = 1;
-            auto go = [&](auto kern) {
+            auto go = [&](auto kern, auto... roi) {
                 hipLaunchKernelGGL(kern, dim3((unsigned)gw), dim3(256), 0, st, cover, stego, P->H, P->W, P->T, P->maxval,
-                                   cnt, L.ntiles_max, P->B, tps, gps);
+                                   cnt, L.ntiles_max, P->B, tps, gps, roi...);
             };
-            if (gate) go(k_pee_scan<TT, true, true>);   // gated: non-temporal only
+            if (rps) go(k_pee_scan<TT, true, true, const int32_t*>, rps);
+            else if (gate) go(k_pee_scan<TT, true, true>);   // gated: non-temporal only
             else pee_flag(nt, [&](auto n) { go(k_pee_scan<TT, n(), false>); });
             LAUNCH_CHECK("k_pee_scan");
         } else {
             if (!inplace) HIP_TRY(hipMemcpyAsync(stego, cover, (size_t)npx * P->B * P->bytes, hipMemcpyDeviceToDevice, st));
-            pee_flag(gate, [&](auto gv) {
+            if (rps)
+                hipLaunchKernelGGL((k_pee_count<TT, true, const int32_t*>), grid, dim3(256), 0, st, cover, P->H, P->W, P->T,
+                                   P->maxval, per, cnt, L.ntiles_max, tps, gps, rps);
+            else pee_flag(gate, [&](auto gv) {
                 hipLaunchKernelGGL((k_pee_count<TT, gv()>), grid, dim3(256), 0, st, cover, P->H, P->W, P->T, P->maxval, per,
                                    cnt, L.ntiles_max, tps, gps);
             });
@@ -3769,7 +3841,10 @@ static int pee_embed_t(const codec_pee_params* P, const PeeCall& C, const TT* co
     }
     {
         ProfScope prof(st, CODEC_K_PEE_LOCATE);
-        pee_flag(gate, [&](auto gv) {
+        if (rps)
+            hipLaunchKernelGGL((k_pee_locate<TT, true, const int32_t*>), dim3(P->B), dim3(256), 0, st, cover, P->H, P->W, P->T,
+                               P->maxval, lengths, cnt, off, L.ntiles_max, meta, tps, gps, rps);
+        else pee_flag(gate, [&](auto gv) {
             hipLaunchKernelGGL((k_pee_locate<TT, gv()>), dim3(P->B), dim3(256), 0, st, cover, P->H, P->W, P->T, P->maxval,
                                lengths, cnt, off, L.ntiles_max, meta, tps, gps);
         });
@@ -3779,33 +3854,37 @@ static int pee_embed_t(const codec_pee_params* P, const PeeCall& C, const TT* co
         ProfScope prof(st, CODEC_K_PEE_EMBED);
         const int g = (int)knob("CODEC_PEE_EMBED_WGS", 64);
         dim3 grid(g < L.ntiles_max ? g : L.ntiles_max, P->B);
-        auto go = [&](auto kern) {   // k_pee_embed_v and k_pee_embed take the same arguments
+        auto go = [&](auto kern, auto... roi) {   // k_pee_embed_v and k_pee_embed take the same arguments
             hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, cover, stego, P->H, P->W, payload, P->payload_words, off,
-                               L.ntiles_max, meta, lm, P->lm_words);
+                               L.ntiles_max, meta, lm, P->lm_words, roi...);
         };
+        const PeeRoiRec rec;   // the ROI instantiations read the words k_pee_locate wrote into the record
         if (vec && knob("CODEC_PEE_EMBED_V", 1)) {
-            pee_flag(gate, [&](auto gv) { go(k_pee_embed_v<TT, gv()>); });
+            if (rps) go(k_pee_embed_v<TT, true, PeeRoiRec>, rec);
+            else pee_flag(gate, [&](auto gv) { go(k_pee_embed_v<TT, gv()>); });
             LAUNCH_CHECK("k_pee_embed_v");
             return 0;
         }
-        pee_flag(vec, gate, [&](auto v, auto gv) { go(k_pee_embed<TT, v(), gv()>); });
+        if (rps) pee_flag(vec, [&](auto v) { go(k_pee_embed<TT, v(), true, PeeRoiRec>, rec); });
+        else pee_flag(vec, gate, [&](auto v, auto gv) { go(k_pee_embed<TT, v(), gv()>); });
         LAUNCH_CHECK("k_pee_embed");
     }
     return 0;
 }
 
 static int pee_embed_impl(const codec_pee_params* P, const void* cover, void* stego, const uint64_t* payload,
-                          const int32_t* lengths, const int32_t* tps, const int32_t* gps, codec_pee_meta* meta,
-                          uint64_t* lm, void* workspace, size_t workspace_bytes, void* stream) {
+                          const int32_t* lengths, const int32_t* tps, const int32_t* gps, const int32_t* rps,
+                          codec_pee_meta* meta, uint64_t* lm, void* workspace, size_t workspace_bytes, void* stream,
+                          const char* who) {
     PeeCall C;
     int rc = pee_begin(&C, P, pee_check(P), !cover || !stego || !payload || !lengths || !meta || !lm || !workspace,
-                       "codec_pee_embed", pee_no_more, workspace, workspace_bytes, stream, PEE_ENTER);
+                       who, pee_no_more, workspace, workspace_bytes, stream, PEE_ENTER);
     if (rc) return rc;
     return pee_pixel(P->bytes, [&](auto px) {
         using TT = decltype(px);
         return pee_embed_t(P, C, static_cast<const TT*>(cover), static_cast<TT*>(stego),
-                           reinterpret_cast<const u64*>(payload), lengths, tps, gps, meta, reinterpret_cast<u64*>(lm),
-                           workspace);
+                           reinterpret_cast<const u64*>(payload), lengths, tps, gps, rps, meta,
+                           reinterpret_cast<u64*>(lm), workspace);
     });
 }
 
@@ -3915,8 +3994,10 @@ int codec_pee_embed_auto(const codec_pee_params* P, const void* cover, void* ste
 // slice-serial kernels and the self-cleaning look-back
 template <typename TT>
 static int pee_extract_t(const codec_pee_params* P, const PeeCall& C, const TT* stego, const codec_pee_meta* meta,
-                         const u64* lm, TT* cover_out, u64* payload_out, void* workspace, bool gate) {
+                         const u64* lm, TT* cover_out, u64* payload_out, void* workspace, bool gate, bool use_roi) {
     constexpr bool U16 = std::is_same_v<TT, uint16_t>;
+    const bool roi = gate && use_roi;   // the ROI instantiations: gated, and honouring the records' rectangle words
+    const PeeRoiRec rec;
     const PeeWs& L = C.L;
     hipStream_t st = C.st;
     uint32_t* cnt = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + L.cnt);
@@ -3976,13 +4057,14 @@ static int pee_extract_t(const codec_pee_params* P, const PeeCall& C, const TT* 
                                     "CODEC_PEE_X_GROUP", payload_out, (size_t)P->B * P->payload_words * 8, nullptr, 0);
         if (rc) return rc;
         ProfScope prof(st, CODEC_K_PEE_EXTRACT1);
-        auto go = [&](auto kern) {
+        auto go = [&](auto kern, auto... r) {
             hipLaunchKernelGGL(kern, dim3((unsigned)S.g), dim3(256), 0, st, stego, cover_out, P->H, P->W, meta, lm,
                                P->lm_words, L.nchunks, P->B, S.stw, S.ctl, payload_out, P->payload_words, S.mode,
-                               S.spin_max, S.dbg_skip, S.diag, S.sc_epoch, S.dbg_stale);
+                               S.spin_max, S.dbg_skip, S.diag, S.sc_epoch, S.dbg_stale, r...);
         };
         // gated: non-temporal accesses only, as the gated embed; self-cleaning: out of place only
-        if (gate) pee_flag(inplace, [&](auto ip) { go(k_pee_extract1<TT, true, ip(), false, true>); });
+        if (roi) pee_flag(inplace, [&](auto ip) { go(k_pee_extract1<TT, true, ip(), false, true, PeeRoiRec>, rec); });
+        else if (gate) pee_flag(inplace, [&](auto ip) { go(k_pee_extract1<TT, true, ip(), false, true>); });
         else if (S.sc() && !inplace) pee_flag(nt, [&](auto n) { go(k_pee_extract1<TT, n(), false, true>); });
         else pee_flag(nt, inplace, [&](auto n, auto ip) { go(k_pee_extract1<TT, n(), ip(), false>); });
         LAUNCH_CHECK("k_pee_extract1");
@@ -3995,8 +4077,8 @@ static int pee_extract_t(const codec_pee_params* P, const PeeCall& C, const TT* 
     const int g = (int)knob("CODEC_PEE_EMBED_WGS", 64);
     dim3 grid(g < L.ntiles_max ? g : L.ntiles_max, P->B);
     // k_pee_dcount_w / k_pee_dcount, then the tile offsets
-    auto dcount = [&](auto kern, dim3 gr) {
-        hipLaunchKernelGGL(kern, gr, dim3(256), 0, st, stego, P->H, P->W, meta, lm, P->lm_words, cnt, L.ntiles_max);
+    auto dcount = [&](auto kern, dim3 gr, auto... r) {
+        hipLaunchKernelGGL(kern, gr, dim3(256), 0, st, stego, P->H, P->W, meta, lm, P->lm_words, cnt, L.ntiles_max, r...);
     };
     auto offsets = [&]() {
         hipLaunchKernelGGL(k_pee_offsets, dim3(P->B), dim3(256), 0, st, meta, cnt, off, L.ntiles_max);
@@ -4008,9 +4090,11 @@ static int pee_extract_t(const codec_pee_params* P, const PeeCall& C, const TT* 
             ProfScope prof(st, CODEC_K_PEE_DCOUNT);
             if (knob("CODEC_PEE_WAVE_TILES", 1)) {
                 const int gw = (int)knob("CODEC_PEE_DCOUNT_W_WGS", 8);   // 4 waves (tiles) per workgroup
-                pee_flag(gate, [&](auto gv) { dcount(k_pee_dcount_w<TT, gv()>, dim3(gw, P->B)); });
+                if (roi) dcount(k_pee_dcount_w<TT, true, PeeRoiRec>, dim3(gw, P->B), rec);
+                else pee_flag(gate, [&](auto gv) { dcount(k_pee_dcount_w<TT, gv()>, dim3(gw, P->B)); });
             } else {
-                pee_flag(gate, [&](auto gv) { dcount(k_pee_dcount<TT, true, gv()>, grid); });
+                if (roi) dcount(k_pee_dcount<TT, true, true, PeeRoiRec>, grid, rec);
+                else pee_flag(gate, [&](auto gv) { dcount(k_pee_dcount<TT, true, gv()>, grid); });
             }
             LAUNCH_CHECK("k_pee_dcount");
             offsets();
@@ -4021,11 +4105,12 @@ static int pee_extract_t(const codec_pee_params* P, const PeeCall& C, const TT* 
         long long gg = (total + 1023) / 1024;
         const long long cap = knob("CODEC_PEE_RESTORE_WGS", 1 << 30);
         if (gg > cap) gg = cap;
-        auto go = [&](auto kern) {
+        auto go = [&](auto kern, auto... r) {
             hipLaunchKernelGGL(kern, dim3((unsigned)gg), dim3(256), 0, st, stego, cover_out, P->H, P->W, (uint32_t)items,
-                               total, meta, lm, P->lm_words, off, L.ntiles_max, payload_out, P->payload_words);
+                               total, meta, lm, P->lm_words, off, L.ntiles_max, payload_out, P->payload_words, r...);
         };
-        if (gate) go(k_pee_restore_gs<TT, true, true>);   // gated: non-temporal only
+        if (roi) go(k_pee_restore_gs<TT, true, true, PeeRoiRec>, rec);
+        else if (gate) go(k_pee_restore_gs<TT, true, true>);   // gated: non-temporal only
         else pee_flag(nt, [&](auto n) { go(k_pee_restore_gs<TT, n(), false>); });
         LAUNCH_CHECK("k_pee_restore_gs");
         return 0;
@@ -4044,17 +4129,20 @@ static int pee_extract_t(const codec_pee_params* P, const PeeCall& C, const TT* 
     }
     {
         ProfScope prof(st, CODEC_K_PEE_DCOUNT);
-        pee_flag(vec, gate, [&](auto v, auto gv) { dcount(k_pee_dcount<TT, v(), gv()>, grid); });
+        if (roi) pee_flag(vec, [&](auto v) { dcount(k_pee_dcount<TT, v(), true, PeeRoiRec>, grid, rec); });
+        else pee_flag(vec, gate, [&](auto v, auto gv) { dcount(k_pee_dcount<TT, v(), gv()>, grid); });
         LAUNCH_CHECK("k_pee_dcount");
         offsets();
         LAUNCH_CHECK("k_pee_offsets");
     }
     {
         ProfScope prof(st, CODEC_K_PEE_RECOVER);
-        pee_flag(vec, gate, [&](auto v, auto gv) {
-            hipLaunchKernelGGL((k_pee_recover<TT, v(), gv()>), grid, dim3(256), 0, st, stego, cover_out, P->H, P->W, meta, lm,
-                               P->lm_words, off, L.ntiles_max, payload_out, P->payload_words);
-        });
+        auto recover = [&](auto kern, auto... r) {
+            hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, stego, cover_out, P->H, P->W, meta, lm, P->lm_words, off,
+                               L.ntiles_max, payload_out, P->payload_words, r...);
+        };
+        if (roi) pee_flag(vec, [&](auto v) { recover(k_pee_recover<TT, v(), true, PeeRoiRec>, rec); });
+        else pee_flag(vec, gate, [&](auto v, auto gv) { recover(k_pee_recover<TT, v(), gv()>); });
         LAUNCH_CHECK("k_pee_recover");
     }
     return 0;
@@ -4062,15 +4150,15 @@ static int pee_extract_t(const codec_pee_params* P, const PeeCall& C, const TT* 
 
 static int pee_extract_impl(const codec_pee_params* P, const void* stego, const codec_pee_meta* meta, const uint64_t* lm,
                             void* cover_out, uint64_t* payload_out, void* workspace, size_t workspace_bytes, void* stream,
-                            bool gate) {
+                            bool gate, bool use_roi = false, const char* who = "codec_pee_extract") {
     PeeCall C;
     int rc = pee_begin(&C, P, pee_check(P), !stego || !meta || !lm || !cover_out || !payload_out || !workspace,
-                       "codec_pee_extract", pee_no_more, workspace, workspace_bytes, stream, PEE_ENTER);
+                       who, pee_no_more, workspace, workspace_bytes, stream, PEE_ENTER);
     if (rc) return rc;
     return pee_pixel(P->bytes, [&](auto px) {
         using TT = decltype(px);
         return pee_extract_t(P, C, static_cast<const TT*>(stego), meta, reinterpret_cast<const u64*>(lm),
-                             static_cast<TT*>(cover_out), reinterpret_cast<u64*>(payload_out), workspace, gate);
+                             static_cast<TT*>(cover_out), reinterpret_cast<u64*>(payload_out), workspace, gate, use_roi);
     });
 }
 
@@ -4086,6 +4174,17 @@ int codec_pee_extract(const codec_pee_params* P, const void* stego, const codec_
 int codec_pee_gate_extract(const codec_pee_params* P, const void* stego, const codec_pee_meta* meta, const uint64_t* lm,
                            void* cover_out, uint64_t* payload_out, void* workspace, size_t workspace_bytes, void* stream) {
     return pee_extract_impl(P, stego, meta, lm, cover_out, payload_out, workspace, workspace_bytes, stream, true);
+}
+
+// include/codec_tcc_roi.h: the gated extract that also takes each record's rectangle
+// (reserved[0], reserved[2]; reserved[2] = 0: none, so this call reads every scheme-1 record)
+int codec_pee_roi_extract(const codec_pee_params* P, const void* stego, const codec_pee_meta* meta, const uint64_t* lm,
+                          void* cover_out, uint64_t* payload_out, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = pee_check(P);
+    if (rc) return rc;
+    if ((rc = pee_roi_dim_check(P, "codec_pee_roi_extract"))) return rc;
+    return pee_extract_impl(P, stego, meta, lm, cover_out, payload_out, workspace, workspace_bytes, stream, true, true,
+                            "codec_pee_roi_extract");
 }
 
 }  // extern "C"

@@ -20,6 +20,10 @@ Volume payloads (scheme 1; include/codec_tcc_vol.h): one bitstream across the wh
 with the per-slice bit counts and T chosen on the device from the capacity curves.  With
 embed_volume(..., gate="auto") (or an integer gate; include/codec_tcc_gvol.h) the plan is over
 (T, G): the smoothness gate of PeeCodec(gate=...) chosen for the volume and again per slice.
+
+Regions of interest (scheme 1; include/codec_tcc_roi.h, roi.py): codec.embed(..., roi=) takes a
+per-slice pixel rectangle that the stego leaves bit-identical to the cover; the records carry
+it, decode() needs no configuration.
 """
 from __future__ import annotations
 
@@ -30,7 +34,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _lib, checksum as _ck, framing
+from . import _lib, checksum as _ck, framing, roi as _roi
 from .codec import _elem_bytes, _require_gpu, _stream, _torch
 
 
@@ -43,11 +47,13 @@ def lattice_geometry(lattice: int, H: int, W: int):
 
 
 def make_record(H: int, W: int, *, T: int, maxval: int, L: int, end: int, status: int, lattice: int = 0,
-                gate: Optional[int] = None) -> _lib.PeeMeta:
+                gate: Optional[int] = None, roi=None) -> _lib.PeeMeta:
     """The codec_pee_meta an embed of lattice `lattice` writes for this side information (what a
     file header or a side dict of oracle/pee_cpu.py carries); the geometry fields follow from H x W.  The
     values are stored as given -- check_records() judges them.  gate: the smoothness gate G of a
-    gated scheme-1 embedding (reserved[1] = G + 1; include/codec_tcc_gate.h), None = ungated."""
+    gated scheme-1 embedding (reserved[1] = G + 1; include/codec_tcc_gate.h), None = ungated.
+    roi: the rectangle (y0, x0, y1, x1) of a ROI embedding (reserved[0], reserved[2];
+    include/codec_tcc_roi.h); such a record always carries a gate word (65536 without a gate)."""
     _y0, _x0, hc, wc = lattice_geometry(lattice, H, W)
     nc = hc * wc
     m = _lib.PeeMeta()
@@ -58,6 +64,11 @@ def make_record(H: int, W: int, *, T: int, maxval: int, L: int, end: int, status
     m.reserved[0] = lattice
     if gate is not None:
         m.reserved[1] = int(gate) + 1
+    if roi is not None:
+        w0, w2 = _roi.pack_words(roi)
+        m.reserved[0], m.reserved[2] = _roi.as_signed(w0), _roi.as_signed(w2)
+        if gate is None:
+            m.reserved[1] = _lib.GATE_MAX + 1
     return m
 
 
@@ -79,6 +90,8 @@ def check_records(records, H: int, W: int, *, scheme: int, payload_words: int, l
       h, w, nc, ntiles = the geometry's; scheme 2: reserved[0] = the pass; scheme 1:
         reserved[1] in 0..65536 (0 = ungated, else the smoothness gate G + 1; a gated record
         obeys every rule below unchanged -- `end` indexes all candidates, active or not);
+        scheme 1 with reserved[2] != 0 (a ROI record, include/codec_tcc_roi.h): reserved[0] and
+        reserved[2] unpack to y0 < y1 <= H and x0 < x1 <= W, and reserved[1] is in 1..65536;
       status 0: L = 0 and end = -1, or 1 <= L <= end + 1 <= nc_p;
       status 1 (the pass filled up): end = nc_p - 1 and 0 <= L <= nc_p (L = 0 when the
         capacity is 0 and bits were left over);
@@ -131,6 +144,16 @@ def check_records(records, H: int, W: int, *, scheme: int, payload_words: int, l
                 bad(b, p, "reserved[0]", int(r.reserved[0]), "the pass's lattice")
             if scheme == 1 and not 0 <= int(r.reserved[1]) <= _lib.GATE_MAX + 1:
                 bad(b, p, "reserved[1]", int(r.reserved[1]), f"0 (ungated) or a gate + 1 in 1..{_lib.GATE_MAX + 1}")
+            if scheme == 1 and int(r.reserved[2]) != 0:   # a ROI record
+                y0, x0, y1, x1 = _roi.record_roi(r)
+                if not y0 < y1 <= H:
+                    bad(b, p, "reserved[2]" if y1 > H else "reserved[0]", int(r.reserved[2] if y1 > H else r.reserved[0]),
+                        f"the ROI's rows y0 = {y0}, y1 = {y1}: y0 < y1 <= H = {H}")
+                if not x0 < x1 <= W:
+                    bad(b, p, "reserved[2]" if x1 > W else "reserved[0]", int(r.reserved[2] if x1 > W else r.reserved[0]),
+                        f"the ROI's columns x0 = {x0}, x1 = {x1}: x0 < x1 <= W = {W}")
+                if int(r.reserved[1]) == 0:
+                    bad(b, p, "reserved[1]", 0, f"a ROI record carries a gate + 1 in 1..{_lib.GATE_MAX + 1}")
             if status == 0:
                 if L == 0:
                     if end != -1:
@@ -187,6 +210,14 @@ class PeeEncoded:
         n = len(raw) // _lib.PEE_META_BYTES
         return [_lib.PeeMeta.from_buffer_copy(raw, i * _lib.PEE_META_BYTES) for i in range(n)]
 
+    @property
+    def roi(self) -> List[Tuple[int, int, int, int]]:
+        """Scheme 1: the per-slice rectangles (y0, x0, y1, x1) read from the records ((0, 0, 0, 0):
+        none).  One read-back."""
+        if self.scheme != 1:
+            raise ValueError("regions of interest are scheme 1's")
+        return _roi.records_roi(self.records())
+
     def pass_records(self) -> List[List[_lib.PeeMeta]]:
         """Scheme 2: records[p][b] of pass p (scheme 1: one pass)."""
         recs = self.records()
@@ -239,6 +270,32 @@ def check_gate_args(gate, T, tmax: int, nc: int, scheme: int = 1) -> None:
         raise ValueError(f"gate='auto' with a fixed T takes T in 1..tmax = {int(tmax)}, got {T}")
     if int(nc) > _lib.GATE_MAX_NC:
         raise ValueError(f"{int(nc)} candidates per slice exceed the gated selection's 2^26")
+
+
+_TILE_UNSET = object()   # embed(tile=) not given: checksum.TILE_DEFAULT (a ROI call with tiles insists on one)
+
+
+def check_roi_args(roi, B: int, H: int, W: int, *, scheme: int = 1, T=None, tmax: int = 16, gate=None, tiled: bool = False,
+                   tile_given: bool = True):
+    """The argument rules of embed(..., roi=) (include/codec_tcc_roi.h), as ValueError before
+    anything is queued; returns roi.normalize_roi's host array (None for roi=None).  Pure host
+    code but for the read-back of a device tensor's values."""
+    if roi is None:
+        return None
+    if int(scheme) != 1:
+        raise ValueError("a region of interest is scheme 1's: scheme 2's later passes modify the pixels scheme 1 "
+                         "leaves alone (DESIGN §3i)")
+    if tiled and not tile_given:
+        raise ValueError("roi= with checksum='tiles' takes an explicit tile=: choose the grid with the rectangle in "
+                         "view (DESIGN §3i)")
+    _roi.check_roi_shape(H, W)
+    nc = (int(H) // 2) * (int(W) // 2)
+    if gate is None:   # the ROI calls are gated calls: the table and the selection's limits apply
+        if T == "auto" and not 1 <= int(tmax) <= _lib.GATE_TMAX:
+            raise ValueError(f"roi= with T='auto' takes tmax in 1..{_lib.GATE_TMAX} (the gated selection's), got {tmax}")
+        if nc > _lib.GATE_MAX_NC:
+            raise ValueError(f"{nc} candidates per slice exceed the gated selection's 2^26")
+    return _roi.normalize_roi(roi, B, H, W)
 
 
 def check_gvol_args(codec_gate, gate, tmax: int, nc: int, scheme: int = 1) -> None:
@@ -408,6 +465,31 @@ class PeeCodec:
         return (torch.from_numpy(packed).to(self.device), lengths,
                 torch.tensor(lengths, dtype=torch.int32, device=self.device))
 
+    def pack_roi(self, roi):
+        """roi.PackedRoi for embed(..., roi=): the rectangles judged (roi.normalize_roi: None, one
+        4-tuple for every slice, or [B, 4]) and uploaded once, for calls that must not read back
+        or upload (a captured graph), as pack_payloads is for the payloads."""
+        if isinstance(roi, _roi.PackedRoi):
+            return roi
+        host = check_roi_args(roi, self.B, self.H, self.W, scheme=self.scheme, T="auto" if self.auto else self.T,
+                              tmax=self.tmax, gate=self.gate)
+        if host is None:
+            return None
+        return _roi.PackedRoi(host, _torch().from_numpy(host).to(self.device))
+
+    def _roi_slices(self):
+        """(t_slices, g_slices) of a ROI call: the codec's own where it is gated, else tensors kept
+        beside them (g = 65535: no gate asked for)."""
+        torch = _torch()
+        if self.gate is not None:
+            return self.t_slices, self.g_slices
+        g = self.__dict__.get("_roi_g")
+        if g is None:
+            g = self._roi_g = torch.full((self.B,), _lib.GATE_MAX, dtype=torch.int32, device=self.device)
+            self._roi_t = self.t_slices if self.auto else torch.full((self.B,), self.T, dtype=torch.int32,
+                                                                      device=self.device)
+        return self._roi_t, g
+
     def _table_workspace(self, tmax: int):
         """The workspace of a codec_pee_gate_capacity call: the codec's own when it is a gated
         one's, else a table-only one kept beside it (the call uses the tail alone)."""
@@ -422,35 +504,44 @@ class PeeCodec:
             ws = self._gate_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return ws
 
-    def gate_table(self, covers, tmax: Optional[int] = None, gate: Optional[int] = None):
+    def gate_table(self, covers, tmax: Optional[int] = None, gate: Optional[int] = None, roi=None):
         """(n, hs): the gated capacity table of every slice as int32 device tensors [B, 16] and
         [B, tmax, 16] (include/codec_tcc_gate.h): n[b, j] = candidates of roughness class j
         (first j with D <= _lib.GATES[j]), hs[b, u, j] = those whose expansion is safe and whose
         folded error is u.  hs.cumsum(1).cumsum(2)[b, T - 1, j] is the capacity at
-        (T, GATES[j]).  gate: the two-class table of one gate instead (class 0 = D <= gate)."""
+        (T, GATES[j]).  gate: the two-class table of one gate instead (class 0 = D <= gate).
+        roi: the slices' rectangles (embed's roi=): protected candidates fall into no class."""
         torch = _torch()
         if self.scheme != 1:
             raise ValueError("the smoothness gate is scheme 1's")
         tmax = self.tmax if tmax is None else int(tmax)
         check_gate_args(0 if gate is None else gate, 1, tmax, self.nc)
         self._check_buffers(covers=covers)
+        rects = self.pack_roi(roi)
         n = torch.empty((self.B, 16), dtype=torch.int32, device=self.device)
         hs = torch.empty((self.B, tmax, 16), dtype=torch.int32, device=self.device)
         ws = self._table_workspace(tmax)
+        if rects is not None:
+            _lib.check(_lib.load().codec_pee_roi_capacity(
+                C.byref(self._params(1)), covers.data_ptr(), tmax, 0, -1 if gate is None else int(gate), None,
+                rects.device.data_ptr(), n.data_ptr(), hs.data_ptr(), None, None, None, ws.data_ptr(), ws.numel(), _stream()),
+                "codec_pee_roi_capacity")
+            return n, hs
         _lib.check(_lib.load().codec_pee_gate_capacity(
             C.byref(self._params(1)), covers.data_ptr(), tmax, 0, -1 if gate is None else int(gate), None, n.data_ptr(),
             hs.data_ptr(), None, None, None, ws.data_ptr(), ws.numel(), _stream()), "codec_pee_gate_capacity")
         return n, hs
 
-    def capacity(self, covers, tmax: Optional[int] = None, gate: Optional[int] = None):
+    def capacity(self, covers, tmax: Optional[int] = None, gate: Optional[int] = None, roi=None):
         """int32 [B, tmax] device tensor: exact capacity of each slice at T = 1..tmax.
         Bounded by the candidate lattice: at most (H // 2) * (W // 2) bits per slice -- a
         quarter of the pixels; the other three quarters are the MED context, never modified.
-        gate: the capacities under that smoothness gate (active candidates only)."""
+        gate: the capacities under that smoothness gate (active candidates only).
+        roi: the capacities outside the slices' rectangles (embed's roi=; with or without a gate)."""
         torch = _torch()
         tmax = self.tmax if tmax is None else int(tmax)
-        if gate is not None:
-            _n, hs = self.gate_table(covers, tmax, gate)
+        if gate is not None or roi is not None:
+            _n, hs = self.gate_table(covers, tmax, _lib.GATE_MAX if gate is None else gate, roi=roi)
             return hs[:, :, 0].cumsum(1).to(torch.int32)
         self._check_buffers(covers=covers)
         caps = torch.empty((self.B, tmax), dtype=torch.int32, device=self.device)
@@ -460,7 +551,7 @@ class PeeCodec:
         return caps
 
     def embed(self, covers, payloads, *, stego=None, lm=None, meta=None, packed=None, check: bool = True,
-              checksum=False, tile=_ck.TILE_DEFAULT) -> PeeEncoded:
+              checksum=False, tile=_TILE_UNSET, roi=None) -> PeeEncoded:
         """cover -> stego + location map + per-slice meta.  check=True (default) reads the
         per-slice status back (one sync) and raises RuntimeError if an in-place look-back
         gave up (CODEC_PEE_ELOOKBACK: the slice is not a valid stego); check=False keeps
@@ -472,10 +563,27 @@ class PeeCodec:
         checksum="tiles": everything checksum=True records, and enc.cover_tile_crc =
         crc32_tiles(covers, tile) (int32 [B, nty, ntx]; tile: an int or (th, tw), 4..1024), queued
         before the embed too; a decode whose cover check fails then names the tiles that differ
-        (IntegrityError.tiles)."""
+        (IntegrityError.tiles).
+        roi (scheme 1; include/codec_tcc_roi.h): None, one rectangle (y0, x0, y1, x1)
+        for every slice, a [B, 4] array / list / device tensor, or pack_roi()'s result.  The stego
+        is bit-identical to the cover on every pixel of a slice's rectangle: candidates inside it
+        are left alone and count nowhere, exactly as those a smoothness gate rejects.  The records
+        carry the rectangle (enc.roi) and decode() follows them.  With T="auto" / gate="auto" the
+        capacity table leaves the protected candidates out.  checksum=True composes (the CRCs are
+        the cover's); checksum="tiles" does with an explicit tile=.
+        tile: the default is a private "not given" marker that stands for checksum.TILE_DEFAULT (64),
+        exactly as before; it exists so that a call with roi= and checksum="tiles" can tell whether
+        the tile was chosen by the caller."""
         torch = _torch()
         checksum, tiled = _ck.checksum_mode(checksum)
+        tile_given = tile is not _TILE_UNSET
+        if not tile_given:
+            tile = _ck.TILE_DEFAULT
         tile = _ck.check_tile_args(tile) if tiled else None
+        if roi is not None:   # judged (and uploaded) before anything is queued, the checksum launches included
+            if tiled and not tile_given:
+                check_roi_args((0, 0, 0, 0), self.B, self.H, self.W, scheme=self.scheme, tiled=True, tile_given=False)
+            roi = self.pack_roi(roi)
         # every buffer of the call, before anything is queued (the checksum launch included)
         check_buffers(self.device, self.B, self.H, self.W, self.bytes, lm_words=self.lm_words, scheme=self.scheme,
                       covers=covers, stego=stego, lm=lm, meta=meta, packed=packed)
@@ -495,14 +603,15 @@ class PeeCodec:
                 payload_crc = [_ck.payload_crc32_packed(rows[b], lengths[b]) for b in range(self.B)]
                 packed = (torch.from_numpy(rows).to(self.device), lengths,
                           torch.tensor(lengths, dtype=torch.int32, device=self.device))
-        enc = self._embed(covers, payloads, stego, lm, meta, packed, check)
+        enc = self._embed(covers, payloads, stego, lm, meta, packed, check, roi)
         enc.cover_crc, enc.payload_crc = cover_crc, payload_crc
         enc.cover_tile_crc, enc.tile = tile_crc, tile
         return enc
 
-    def _embed(self, covers, payloads, stego, lm, meta, packed, check) -> PeeEncoded:
+    def _embed(self, covers, payloads, stego, lm, meta, packed, check, roi=None) -> PeeEncoded:
         torch = _torch()
         words, lengths, lens_t = packed if packed is not None else self.pack_payloads(payloads)
+        rects = self.pack_roi(roi) if roi is not None else None
         if stego is None:
             stego = torch.empty_like(covers)
         if self.scheme == 2:
@@ -514,7 +623,32 @@ class PeeCodec:
         P = self._params(words.shape[1])
         lib = _lib.load()
 
+        def launch_roi():
+            # the gated routes with the slices' rectangles (include/codec_tcc_roi.h)
+            rp = rects.device.data_ptr()
+            ts, gs = self._roi_slices()
+            if self.gate is not None and (self.auto or self.gate == "auto"):
+                tmax = self.tmax if self.auto else self.T
+                _lib.check(lib.codec_pee_roi_embed_auto(
+                    C.byref(P), covers.data_ptr(), stego.data_ptr(), words.data_ptr(), lens_t.data_ptr(), tmax,
+                    0 if self.auto else self.T, -1 if self.gate == "auto" else self.gate, rp, ts.data_ptr(), gs.data_ptr(),
+                    meta.data_ptr(), lm.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), _stream()),
+                    "codec_pee_roi_embed_auto")
+                return
+            if self.auto:   # an ungated codec: the smallest T that holds the payload outside the rectangle,
+                # from the table pass on the table workspace (as gate_table), then the embed on the codec's own
+                tws = self._table_workspace(self.tmax)
+                _lib.check(lib.codec_pee_roi_capacity(
+                    C.byref(P), covers.data_ptr(), self.tmax, 0, _lib.GATE_MAX, lens_t.data_ptr(), rp, None, None,
+                    ts.data_ptr(), gs.data_ptr(), None, tws.data_ptr(), tws.numel(), _stream()), "codec_pee_roi_capacity")
+            _lib.check(lib.codec_pee_roi_embed(
+                C.byref(P), covers.data_ptr(), stego.data_ptr(), words.data_ptr(), lens_t.data_ptr(), ts.data_ptr(),
+                gs.data_ptr(), rp, meta.data_ptr(), lm.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(),
+                _stream()), "codec_pee_roi_embed")
+
         def launch():
+            if rects is not None:
+                return launch_roi()
             if self.gate is not None and (self.auto or self.gate == "auto"):
                 # the gated table, the (T, G) selection and the embed queued on this stream
                 tmax = self.tmax if self.auto else self.T
@@ -580,10 +714,13 @@ class PeeCodec:
             _raise_lookback(recs)
         return enc
 
-    def extract(self, stego, meta, lm, *, payload_words: int, cover=None, payload=None, gated: Optional[bool] = None):
+    def extract(self, stego, meta, lm, *, payload_words: int, cover=None, payload=None, gated: Optional[bool] = None,
+                roi: bool = False):
         """gated: decode through codec_pee_gate_extract, which takes each record's gate
         (reserved[1]; it reads ungated records too).  None: this codec's own setting; decode()
-        passes what the records say."""
+        passes what the records say.  roi=True: through codec_pee_roi_extract, which takes the
+        gate and the rectangle (reserved[0], reserved[2]) from each record and reads every other
+        scheme-1 record too; decode() passes what the records say."""
         torch = _torch()
         check_buffers(self.device, self.B, self.H, self.W, self.bytes, lm_words=self.lm_words, scheme=self.scheme,
                       stego=stego, cover=cover, lm=lm, meta=meta, payload=payload, payload_words=payload_words)
@@ -597,6 +734,9 @@ class PeeCodec:
         gated = self.gate is not None if gated is None else bool(gated)
         fn, what = (_lib.load().codec_pee_gate_extract, "codec_pee_gate_extract") if gated else \
             (_lib.load().codec_pee_extract, "codec_pee_extract")
+        if roi:
+            _roi.check_roi_shape(self.H, self.W)
+            fn, what = _lib.load().codec_pee_roi_extract, "codec_pee_roi_extract"
         self._guarded(lambda: _lib.check(fn(
             C.byref(P), stego.data_ptr(), meta.data_ptr(), lm.data_ptr(), cover.data_ptr(), payload.data_ptr(),
             self.workspace.data_ptr(), self.workspace.numel(), _stream()), what))
@@ -720,7 +860,8 @@ class PeeCodec:
         self._check(enc, recs)
         # the gate is the records': a gated embedding decodes on any scheme-1 codec of the shape
         words, cover = self.extract(enc.stego, enc.meta, enc.lm, payload_words=enc.payload_words,
-                                    gated=any(int(r.reserved[1]) != 0 for r in recs))
+                                    gated=any(int(r.reserved[1]) != 0 for r in recs),
+                                    roi=any(int(r.reserved[2]) != 0 for r in recs))
         self._cover_crc = _ck.crc32_slices(cover) if crc else None
         host = self._payload_rows = words.cpu().numpy()
         if self.lookback_failed(enc.payload_words):
@@ -787,7 +928,8 @@ class PeeCodec:
         return _torch().from_numpy(framing.pack_bits([bits])[0].reshape(-1)).to(self.device), int(bits.size)
 
     def embed_volume(self, covers, payload, *, policy: str = "even", stego=None, check: bool = True,
-                     checksum=False, buffers=None, packed=None, gate=None, tile=_ck.TILE_DEFAULT) -> "PeeVolume":
+                     checksum=False, buffers=None, packed=None, gate=None, tile=_ck.TILE_DEFAULT,
+                     roi=None) -> "PeeVolume":
         """One payload (str / bytes / 0-1 vector, framing.to_bits) embedded across the whole
         stack: the device plans how many bits each slice takes and at which T (the rule of
         include/codec_tcc_vol.h: policy "even" spreads the bits in proportion to the slices'
@@ -814,8 +956,12 @@ class PeeCodec:
         packed: pack_volume()'s result instead of `payload` (no upload in the call; the payload
         CRC is then absent, as with embed's packed=).
         checksum="tiles": checksum=True plus enc.cover_tile_crc / enc.tile as embed records them;
-        decode_volume then names the tiles of a cover that fails its check."""
+        decode_volume then names the tiles of a cover that fails its check.
+        roi: must be None -- volume payloads take no region of interest."""
         torch = _torch()
+        if roi is not None:
+            raise ValueError("volume payloads take no region of interest: the plan's capacities are the whole "
+                             "slices' (DESIGN §3i); embed per slice with embed(..., roi=)")
         checksum, tiled = _ck.checksum_mode(checksum)
         tile = _ck.check_tile_args(tile) if tiled else None
         check_gvol_args(self.gate, gate, self.tmax, self.nc, self.scheme)
@@ -1203,7 +1349,7 @@ def _config_from_records(enc: "PeeEncoded") -> dict:
 
 
 def encode(covers, payloads: Sequence, *, T=2, tmax: int = 16, maxval: Optional[int] = None,
-           scheme: int = 1, tmin: int = 1, checksum=False, gate=None, tile=_ck.TILE_DEFAULT) -> PeeEncoded:
+           scheme: int = 1, tmin: int = 1, checksum=False, gate=None, tile=_TILE_UNSET, roi=None) -> PeeEncoded:
     """MED-PEE embed of one payload per slice (the package's `encode(..., method="pee")`).
     covers: [B,H,W] / [H,W] uint8/uint16 torch tensor or numpy array; T: expansion threshold
     or "auto" (smallest T <= tmax whose capacity holds each slice's payload); maxval: the
@@ -1213,18 +1359,24 @@ def encode(covers, payloads: Sequence, *, T=2, tmax: int = 16, maxval: Optional[
     checksum="tiles": also one CRC-32 per `tile` (int or (th, tw), 4..1024) of every cover, so that a
     failed verify names the tiles that differ (PeeCodec.embed).
     gate (scheme 1): a smoothness gate 0..65535 or "auto" (PeeCodec); decode() reads it from the records.
+    roi (scheme 1): a rectangle (y0, x0, y1, x1) for every slice or [B, 4] of them that the stego leaves
+    untouched (PeeCodec.embed); decode() reads it from the records.
+    tile: not given = checksum.TILE_DEFAULT (64), as before (PeeCodec.embed explains the marker).
     Raises ValueError when a payload exceeds its slice's capacity."""
     shape = tuple(covers.shape)
     check_gate_args(gate, T, tmax, (int(shape[-2]) // 2) * (int(shape[-1]) // 2) if len(shape) >= 2 else 0, scheme)
+    if roi is not None:   # every rule but the values', which need the batch shape (PeeCodec.embed)
+        check_roi_args((0, 0, 0, 0), 1, int(shape[-2]), int(shape[-1]), scheme=scheme, T=T, tmax=tmax, gate=gate,
+                       tiled=_ck.checksum_mode(checksum)[1], tile_given=tile is not _TILE_UNSET)
     if _ck.checksum_mode(checksum)[1]:
-        _ck.check_tile_args(tile)
+        _ck.check_tile_args(_ck.TILE_DEFAULT if tile is _TILE_UNSET else tile)
     _require_gpu()
     covers = _as_gpu_batch(covers)
     if isinstance(payloads, (str, bytes, bytearray)):
         payloads = [payloads]
     dt = "uint16" if _elem_bytes(covers) == 2 else "uint8"
     codec = _codec_for(tuple(covers.shape), dt, T=T, tmax=tmax, maxval=maxval, scheme=scheme, tmin=tmin, gate=gate)
-    enc = codec.embed(covers, payloads, checksum=checksum, tile=tile)
+    enc = codec.embed(covers, payloads, checksum=checksum, tile=tile, roi=roi)
     if scheme == 2:
         short = [i for i, (g, n) in enumerate(zip(enc.embedded(), enc.lengths)) if g < n]
         if short:

@@ -139,7 +139,8 @@ def decode_bin_exact(filepath: str, search_block_size: Optional[int] = None) -> 
 
 # ------------------------------------------------------------------ MED-PEE files
 def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxval: Optional[int] = None,
-                    codec: str = "raw", scheme: int = 1, tmin: int = 1, checksum=False, gate=None, tile=64) -> Dict:
+                    codec: str = "raw", scheme: int = 1, tmin: int = 1, checksum=False, gate=None, tile=64,
+                    roi=None) -> Dict:
     """MED-PEE embed of one slice into a version-16 STGC file.  `image` is an array or a
     DICOM path; maxval defaults to the DICOM's full scale 2**BitsStored - 1 (4095 for the
     reference's 12-bit pe.dcm), else the dtype maximum.  T = 'auto' picks the smallest
@@ -155,9 +156,13 @@ def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxva
     cover that fails its check; readers that know only the checksum extension read the file as ever.
     gate (scheme 1): a smoothness gate 0..65535 or 'auto' (PeeCodec): the file then carries scheme
     byte 3 and the chosen gate after scheme 1's fixed header fields ('gate' in the result);
-    without it the file's bytes are unchanged."""
+    without it the file's bytes are unchanged.
+    roi (scheme 1): a rectangle (y0, x0, y1, x1) the stego leaves bit-identical to the cover
+    (PeeCodec.embed): the file then carries scheme byte 4 -- byte 3's fields (the gate
+    65535 when none was asked for) and the rectangle ('roi' in the result).  An empty rectangle is
+    no rectangle: the file is what it is without roi=.  Without roi the file's bytes are unchanged."""
     from . import checksum as _ck
-    from .pee import PeeCodec, check_gate_args, lm_bits
+    from .pee import PeeCodec, check_gate_args, check_roi_args, lm_bits
     checksum, tiled = _ck.checksum_mode(checksum)
     tile = _ck.check_tile_args(tile) if tiled else None
     if gate is not None:
@@ -174,10 +179,14 @@ def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxva
     if img.ndim != 2 or img.dtype not in (np.uint8, np.uint16):
         raise ValueError("A imagem deve ser 2D uint8 ou uint16.")
     h, w = img.shape
+    if roi is not None:   # judged before the codec is built or anything queued; an empty rectangle: none
+        rect = check_roi_args(roi, 1, h, w, scheme=scheme, T=T, tmax=tmax, gate=gate)
+        roi = tuple(int(v) for v in rect[0]) if rect[0].any() else None
     bits = framing.to_bits(payload)
     pc = PeeCodec(1, h, w, dtype=str(img.dtype), T=T, tmin=tmin, tmax=tmax, maxval=maxval, scheme=scheme, gate=gate)
     enc = pc.embed(torch.from_numpy(np.ascontiguousarray(img)[None]).cuda(), [bits],
-                   checksum="tiles" if tiled else checksum, **({"tile": tile} if tiled else {}))
+                   checksum="tiles" if tiled else checksum, **({"tile": tile} if tiled else {}),
+                   **({"roi": roi} if roi is not None else {}))
 
     def ext(embedded: int) -> Tuple[bytes, Dict]:
         if not checksum:
@@ -208,7 +217,12 @@ def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxva
     lmb = container.lm_blob(lm_bits(enc, 0)) if r.end >= 0 else b""
     stego = enc.stego.cpu().numpy()[0]
     gated = {}
-    if gate is None:
+    if roi is not None:   # the gate and the rectangle the record carries
+        from .roi import record_roi
+        gated = {"gate": int(r.reserved[1]) - 1, "roi": record_roi(r), "scheme": container.PEE_SCHEME_ROI}
+        hdr = container.create_pee_roi_header(codec, img.dtype.itemsize, w, h, r.T, embedded, r.end, r.maxval,
+                                              r.status, len(lmb), gated["gate"], gated["roi"])
+    elif gate is None:
         hdr = container.create_pee_header(codec, img.dtype.itemsize, w, h, r.T, embedded, r.end, r.maxval, r.status,
                                           len(lmb))
     else:   # the gate the record carries (gate='auto': the slice's chosen one)
@@ -241,10 +255,14 @@ def read_pee_bytes(raw: bytes) -> PeeFile:
     records), before anything reaches a kernel."""
     from .pee import check_records, make_record
     scheme = container.pee_scheme(raw)
-    gate = None
+    gate = roi = None
     if scheme == 2:
         md, blobs, data = container.parse_pee2_bytes(raw)
         passes = md["passes"]
+    elif scheme == container.PEE_SCHEME_ROI:    # scheme 1 with a protected rectangle: one ROI record
+        md, blob, data = container.parse_pee_roi_bytes(raw)   # (refuses a rectangle outside the image)
+        blobs, passes = [blob], [{"L": md["L"], "end": md["end"], "status": md["status"]}]
+        scheme, gate, roi = 1, md["gate"], md["roi"]
     elif scheme == container.PEE_SCHEME_GATE:   # scheme 1 with a smoothness gate: one gated record
         md, blob, data = container.parse_pee_gate_bytes(raw)
         blobs, passes = [blob], [{"L": md["L"], "end": md["end"], "status": md["status"]}]
@@ -261,7 +279,7 @@ def read_pee_bytes(raw: bytes) -> PeeFile:
     lm_words = max(1, ((h // 2) * (w // 2) + 63) // 64)
     pw = max(1, (md["L"] + 63) // 64)
     records = [[make_record(h, w, T=md["T"], maxval=md["maxval"], L=ps["L"], end=ps["end"], status=ps["status"],
-                            lattice=p, gate=gate)] for p, ps in enumerate(passes)]
+                            lattice=p, gate=gate, roi=roi)] for p, ps in enumerate(passes)]
     check_records(records, h, w, scheme=scheme, payload_words=pw, lm_words=lm_words, bytes=md["bytes"],
                   lengths=[md["L"]] if scheme == 2 else None)
     if md["status"] not in (0, 1) or any(ps["status"] not in (0, 1) for ps in passes):
@@ -298,7 +316,8 @@ def decode_bin_pee(filepath: str, verify=True) -> Tuple[np.ndarray, np.ndarray]:
     if pf.scheme == 1:
         meta_t, lm_t = meta_t[0], lm_t[0]
     words, cover = pc.extract(torch.from_numpy(np.ascontiguousarray(pf.stego)[None]).cuda(), meta_t, lm_t,
-                              payload_words=pf.payload_words, **({"gated": True} if "gate" in md else {}))
+                              payload_words=pf.payload_words, **({"gated": True} if "gate" in md else {}),
+                              **({"roi": True} if "roi" in md else {}))
     crc = _ck.crc32_slices(cover) if (mode and have) else None
     bits = framing.unpack_bits(words.cpu().numpy()[0], md["L"])
     if crc is not None:

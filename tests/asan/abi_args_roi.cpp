@@ -1,0 +1,237 @@
+// Host sanitizer check of the argument validation of include/codec_tcc_roi.h's entries, as
+// abi_args_gate.cpp is for codec_tcc_gate.h: linked against the host-only
+// -fsanitize=address,undefined build of the library and tests/asan/hip_stubs.cpp
+// (tests/test_asan_abi_roi.py builds and runs it).  Every bad call must return its negative
+// status with an error text and no device operation; every call with good arguments must get
+// past the checks, i.e. reach its first device operation (which the stubs refuse and count).
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include "codec_tcc_roi.h"
+
+static int g_fail = 0, g_n = 0;
+extern "C" int hip_stub_device_ops(void);   // tests/asan/hip_stubs.cpp
+
+#define EXPECT_NEG(expr)                                                                           \
+    do {                                                                                           \
+        ++g_n;                                                                                     \
+        const long long r_ = (long long)(expr);                                                    \
+        if (r_ >= 0) {                                                                             \
+            fprintf(stderr, "FAIL line %d: %s returned %lld (want < 0)\n", __LINE__, #expr, r_);   \
+            ++g_fail;                                                                              \
+        } else if (!codec_last_error() || !codec_last_error()[0]) {                                \
+            fprintf(stderr, "FAIL line %d: %s gave no error message\n", __LINE__, #expr);          \
+            ++g_fail;                                                                              \
+        }                                                                                          \
+    } while (0)
+
+#define EXPECT_EQ(expr, want)                                                                      \
+    do {                                                                                           \
+        ++g_n;                                                                                     \
+        const unsigned long long r_ = (unsigned long long)(expr), w_ = (unsigned long long)(want); \
+        if (r_ != w_) {                                                                            \
+            fprintf(stderr, "FAIL line %d: %s = %llu (want %llu)\n", __LINE__, #expr, r_, w_);     \
+            ++g_fail;                                                                              \
+        }                                                                                          \
+    } while (0)
+
+static codec_pee_params good() {
+    codec_pee_params P;
+    memset(&P, 0, sizeof(P));
+    P.B = 5; P.H = 64; P.W = 96; P.bytes = 2; P.T = 1; P.maxval = 4095;
+    P.payload_words = 4; P.lm_words = 24;   // (64 / 2) * (96 / 2) = 1536 candidates
+    return P;
+}
+
+// the parameter sets every entry must refuse
+static int bad_params(codec_pee_params* out) {
+    int k = 0;
+    codec_pee_params P;
+    P = good(); P.B = 0; out[k++] = P;
+    P = good(); P.B = -3; out[k++] = P;
+    P = good(); P.B = INT32_MIN; out[k++] = P;
+    P = good(); P.H = 0; out[k++] = P;
+    P = good(); P.W = -1; out[k++] = P;
+    P = good(); P.H = 65536; P.W = 65536; P.lm_words = 1 << 24; out[k++] = P;      // H * W past 2^31
+    P = good(); P.bytes = 0; out[k++] = P;
+    P = good(); P.bytes = 4; out[k++] = P;
+    P = good(); P.T = 0; out[k++] = P;
+    P = good(); P.maxval = 0; out[k++] = P;
+    P = good(); P.maxval = 65536; out[k++] = P;
+    P = good(); P.bytes = 1; P.maxval = 256; out[k++] = P;
+    P = good(); P.payload_words = 0; out[k++] = P;
+    P = good(); P.payload_words = -1; out[k++] = P;
+    P = good(); P.lm_words = 0; out[k++] = P;
+    P = good(); P.lm_words = 23; out[k++] = P;                                     // 1472 < 1536 candidates
+    return k;
+}
+
+int main() {
+    alignas(64) static unsigned char buf[1 << 16];
+    void* p = buf;
+    int32_t* i32 = reinterpret_cast<int32_t*>(buf);
+    uint32_t* u32 = reinterpret_cast<uint32_t*>(buf);
+    uint64_t* u64p = reinterpret_cast<uint64_t*>(buf);
+    codec_pee_meta* meta = reinterpret_cast<codec_pee_meta*>(buf);
+    const size_t big = (size_t)1 << 40;
+
+    if (codec_abi_version() != 1) { fprintf(stderr, "FAIL abi version\n"); return 2; }
+
+    codec_pee_params G = good();
+    const size_t pws = codec_pee_workspace_bytes(&G);
+    const size_t gws = codec_pee_gate_workspace_bytes(&G, 16);
+    if (!pws || gws <= pws) {
+        fprintf(stderr, "FAIL workspace sizes of good arguments: %zu / %zu\n", pws, gws);
+        ++g_fail;
+    }
+
+#define CAP(P, cover, tmax, tf, gf, len, roi, n, hs, t, g, k, ws, wsb) \
+    codec_pee_roi_capacity(P, cover, tmax, tf, gf, len, roi, n, hs, t, g, k, ws, wsb, nullptr)
+#define EMB(P, cover, stego, pay, len, t, g, roi, m, lm, ws, wsb) \
+    codec_pee_roi_embed(P, cover, stego, pay, len, t, g, roi, m, lm, ws, wsb, nullptr)
+#define AUTO(P, cover, stego, pay, len, tmax, tf, gf, roi, t, g, m, lm, ws, wsb) \
+    codec_pee_roi_embed_auto(P, cover, stego, pay, len, tmax, tf, gf, roi, t, g, m, lm, ws, wsb, nullptr)
+#define EXT(P, stego, m, lm, cover, pay, ws, wsb) codec_pee_roi_extract(P, stego, m, lm, cover, pay, ws, wsb, nullptr)
+#define BOX(P, img, level, margin, out) codec_roi_bbox(P, img, level, margin, out, nullptr)
+
+    // ---- bad parameter sets: every entry, with and without a rectangle array
+    codec_pee_params bad[32];
+    const int nbad = bad_params(bad);
+    for (int k = 0; k < nbad; ++k) {
+        const codec_pee_params* B = &bad[k];
+        EXPECT_NEG(CAP(B, p, 16, 0, -1, i32, i32, u32, u32, i32, i32, i32, p, big));
+        EXPECT_NEG(EMB(B, p, p, u64p, i32, i32, i32, i32, meta, u64p, p, big));
+        EXPECT_NEG(EMB(B, p, p, u64p, i32, i32, i32, nullptr, meta, u64p, p, big));
+        EXPECT_NEG(AUTO(B, p, p, u64p, i32, 16, 0, -1, i32, i32, i32, meta, u64p, p, big));
+        EXPECT_NEG(EXT(B, p, meta, u64p, p, u64p, p, big));
+        EXPECT_NEG(BOX(B, p, 0, 0, i32));
+    }
+    EXPECT_NEG(CAP(nullptr, p, 16, 0, -1, i32, i32, u32, u32, i32, i32, i32, p, big));
+    EXPECT_NEG(EMB(nullptr, p, p, u64p, i32, i32, i32, i32, meta, u64p, p, big));
+    EXPECT_NEG(AUTO(nullptr, p, p, u64p, i32, 16, 0, -1, i32, i32, i32, meta, u64p, p, big));
+    EXPECT_NEG(EXT(nullptr, p, meta, u64p, p, u64p, p, big));
+    EXPECT_NEG(BOX(nullptr, p, 0, 0, i32));
+    // H or W above 65535: the record words hold 16 bits per coordinate -- every ROI entry refuses
+    for (int k = 0; k < 2; ++k) {
+        codec_pee_params P = good();
+        P.B = 1;
+        if (k == 0) { P.H = 65536; P.W = 8; } else { P.H = 8; P.W = 65536; }
+        P.lm_words = (4 * 32768 + 63) / 64;
+        if (!codec_pee_workspace_bytes(&P)) { fprintf(stderr, "FAIL: the tall / wide shape is not a codec_pee one\n"); ++g_fail; }
+        EXPECT_NEG(CAP(&P, p, 16, 0, -1, i32, i32, u32, u32, i32, i32, i32, p, big));
+        EXPECT_NEG(EMB(&P, p, p, u64p, i32, i32, i32, i32, meta, u64p, p, big));
+        EXPECT_NEG(AUTO(&P, p, p, u64p, i32, 16, 0, -1, i32, i32, i32, meta, u64p, p, big));
+        EXPECT_NEG(EXT(&P, p, meta, u64p, p, u64p, p, big));
+        EXPECT_NEG(BOX(&P, p, 0, 0, i32));
+    }
+    // more than 2^26 candidates per slice: the table and the selection refuse
+    {
+        codec_pee_params P = good();
+        P.B = 1; P.H = 16386; P.W = 16386; P.lm_words = (8193 * 8193 + 63) / 64;
+        EXPECT_NEG(CAP(&P, p, 16, 0, -1, i32, i32, u32, u32, i32, i32, i32, p, big));
+        EXPECT_NEG(AUTO(&P, p, p, u64p, i32, 16, 0, -1, i32, i32, i32, meta, u64p, p, big));
+    }
+
+    // ---- codec_pee_roi_capacity
+    EXPECT_NEG(CAP(&G, nullptr, 16, 0, -1, i32, i32, u32, u32, i32, i32, i32, p, gws));
+    EXPECT_NEG(CAP(&G, p, 16, 0, -1, i32, i32, u32, u32, i32, i32, i32, nullptr, gws));
+    EXPECT_NEG(CAP(&G, p, 0, 0, -1, i32, i32, u32, u32, i32, i32, i32, p, gws));
+    EXPECT_NEG(CAP(&G, p, 17, 0, -1, i32, i32, u32, u32, i32, i32, i32, p, big));
+    EXPECT_NEG(CAP(&G, p, INT32_MIN, 0, -1, i32, i32, u32, u32, i32, i32, i32, p, gws));
+    EXPECT_NEG(CAP(&G, p, 16, -1, -1, i32, i32, u32, u32, i32, i32, i32, p, gws));
+    EXPECT_NEG(CAP(&G, p, 16, 17, -1, i32, i32, u32, u32, i32, i32, i32, p, gws));
+    EXPECT_NEG(CAP(&G, p, 4, 5, -1, i32, i32, u32, u32, i32, i32, i32, p, gws));
+    EXPECT_NEG(CAP(&G, p, 16, 0, -2, i32, i32, u32, u32, i32, i32, i32, p, gws));
+    EXPECT_NEG(CAP(&G, p, 16, 0, 65536, i32, i32, u32, u32, i32, i32, i32, p, gws));
+    EXPECT_NEG(CAP(&G, p, 16, 0, -1, nullptr, i32, u32, u32, i32, nullptr, nullptr, p, gws));   // outputs without lengths
+    EXPECT_NEG(CAP(&G, p, 16, 0, -1, nullptr, i32, u32, u32, nullptr, i32, nullptr, p, gws));
+    EXPECT_NEG(CAP(&G, p, 16, 0, -1, nullptr, nullptr, u32, u32, nullptr, nullptr, i32, p, gws));
+    EXPECT_NEG(CAP(&G, p, 16, 0, -1, i32, i32, u32, u32, i32, i32, i32, p, gws - 1));          // short workspaces
+    EXPECT_NEG(CAP(&G, p, 16, 0, -1, i32, i32, u32, u32, i32, i32, i32, p, pws));
+    EXPECT_NEG(CAP(&G, p, 16, 0, -1, i32, nullptr, u32, u32, i32, i32, i32, p, 0));
+
+    // ---- codec_pee_roi_embed
+    EXPECT_NEG(EMB(&G, nullptr, p, u64p, i32, i32, i32, i32, meta, u64p, p, pws));
+    EXPECT_NEG(EMB(&G, p, nullptr, u64p, i32, i32, i32, i32, meta, u64p, p, pws));
+    EXPECT_NEG(EMB(&G, p, p, nullptr, i32, i32, i32, i32, meta, u64p, p, pws));
+    EXPECT_NEG(EMB(&G, p, p, u64p, nullptr, i32, i32, i32, meta, u64p, p, pws));
+    EXPECT_NEG(EMB(&G, p, p, u64p, i32, nullptr, i32, i32, meta, u64p, p, pws));
+    EXPECT_NEG(EMB(&G, p, p, u64p, i32, i32, nullptr, i32, meta, u64p, p, pws));
+    EXPECT_NEG(EMB(&G, p, p, u64p, i32, i32, i32, i32, nullptr, u64p, p, pws));
+    EXPECT_NEG(EMB(&G, p, p, u64p, i32, i32, i32, i32, meta, nullptr, p, pws));
+    EXPECT_NEG(EMB(&G, p, p, u64p, i32, i32, i32, i32, meta, u64p, nullptr, pws));
+    EXPECT_NEG(EMB(&G, p, p, u64p, i32, i32, i32, i32, meta, u64p, p, pws - 1));
+    EXPECT_NEG(EMB(&G, p, p, u64p, i32, i32, i32, nullptr, meta, u64p, p, 0));
+
+    // ---- codec_pee_roi_embed_auto
+    EXPECT_NEG(AUTO(&G, nullptr, p, u64p, i32, 16, 0, -1, i32, i32, i32, meta, u64p, p, gws));
+    EXPECT_NEG(AUTO(&G, p, nullptr, u64p, i32, 16, 0, -1, i32, i32, i32, meta, u64p, p, gws));
+    EXPECT_NEG(AUTO(&G, p, p, nullptr, i32, 16, 0, -1, i32, i32, i32, meta, u64p, p, gws));
+    EXPECT_NEG(AUTO(&G, p, p, u64p, nullptr, 16, 0, -1, i32, i32, i32, meta, u64p, p, gws));
+    EXPECT_NEG(AUTO(&G, p, p, u64p, i32, 16, 0, -1, i32, nullptr, i32, meta, u64p, p, gws));
+    EXPECT_NEG(AUTO(&G, p, p, u64p, i32, 16, 0, -1, i32, i32, nullptr, meta, u64p, p, gws));
+    EXPECT_NEG(AUTO(&G, p, p, u64p, i32, 16, 0, -1, i32, i32, i32, nullptr, u64p, p, gws));
+    EXPECT_NEG(AUTO(&G, p, p, u64p, i32, 16, 0, -1, i32, i32, i32, meta, nullptr, p, gws));
+    EXPECT_NEG(AUTO(&G, p, p, u64p, i32, 16, 0, -1, i32, i32, i32, meta, u64p, nullptr, gws));
+    EXPECT_NEG(AUTO(&G, p, p, u64p, i32, 0, 0, -1, i32, i32, i32, meta, u64p, p, gws));
+    EXPECT_NEG(AUTO(&G, p, p, u64p, i32, 17, 0, -1, i32, i32, i32, meta, u64p, p, big));
+    EXPECT_NEG(AUTO(&G, p, p, u64p, i32, 16, 17, -1, i32, i32, i32, meta, u64p, p, gws));
+    EXPECT_NEG(AUTO(&G, p, p, u64p, i32, 16, 0, 65536, i32, i32, i32, meta, u64p, p, gws));
+    EXPECT_NEG(AUTO(&G, p, p, u64p, i32, 16, 0, -1, i32, i32, i32, meta, u64p, p, gws - 1));
+    EXPECT_NEG(AUTO(&G, p, p, u64p, i32, 16, 0, -1, nullptr, i32, i32, meta, u64p, p, pws));
+
+    // ---- codec_pee_roi_extract
+    EXPECT_NEG(EXT(&G, nullptr, meta, u64p, p, u64p, p, pws));
+    EXPECT_NEG(EXT(&G, p, nullptr, u64p, p, u64p, p, pws));
+    EXPECT_NEG(EXT(&G, p, meta, nullptr, p, u64p, p, pws));
+    EXPECT_NEG(EXT(&G, p, meta, u64p, nullptr, u64p, p, pws));
+    EXPECT_NEG(EXT(&G, p, meta, u64p, p, nullptr, p, pws));
+    EXPECT_NEG(EXT(&G, p, meta, u64p, p, u64p, nullptr, pws));
+    EXPECT_NEG(EXT(&G, p, meta, u64p, p, u64p, p, pws - 1));
+    EXPECT_NEG(EXT(&G, p, meta, u64p, p, u64p, p, 0));
+
+    // ---- codec_roi_bbox
+    EXPECT_NEG(BOX(&G, nullptr, 0, 0, i32));
+    EXPECT_NEG(BOX(&G, p, 0, 0, nullptr));
+    EXPECT_NEG(BOX(&G, p, -1, 0, i32));
+    EXPECT_NEG(BOX(&G, p, 65536, 0, i32));
+    EXPECT_NEG(BOX(&G, p, INT32_MIN, 0, i32));
+    EXPECT_NEG(BOX(&G, p, 0, -1, i32));
+    EXPECT_NEG(BOX(&G, p, 0, 65536, i32));
+    EXPECT_NEG(BOX(&G, p, 0, INT32_MAX, i32));
+
+    if (hip_stub_device_ops() != 0) {
+        fprintf(stderr, "FAIL: %d device operations were attempted by argument-error calls\n", hip_stub_device_ops());
+        ++g_fail;
+    }
+
+    // ---- good arguments: each entry gets past its checks and reaches a device operation, which
+    // the stubs refuse and count.  The buffer stands in for device memory:
+    // nothing dereferences it on the host.
+    {
+        static unsigned char ws[1 << 22];
+        if (gws > sizeof(ws)) { fprintf(stderr, "FAIL: workspace of the good shape is %zu bytes\n", gws); return 2; }
+        int ops = hip_stub_device_ops();
+#define EXPECT_REACHED(expr)                                                                           \
+    do {                                                                                               \
+        ++g_n;                                                                                         \
+        (void)(expr);   /* whatever the refused launches make of it */                                 \
+        if (hip_stub_device_ops() <= ops) {                                                            \
+            fprintf(stderr, "FAIL line %d: %s stopped before any device operation: %s\n", __LINE__, #expr, codec_last_error()); \
+            ++g_fail;                                                                                  \
+        }                                                                                              \
+        ops = hip_stub_device_ops();                                                                   \
+    } while (0)
+        EXPECT_REACHED(BOX(&G, p, 0, 3, i32));
+        EXPECT_REACHED(BOX(&G, buf + 2, 65535, 65535, i32));                                    // an offset view
+        EXPECT_REACHED(CAP(&G, p, 16, 0, -1, i32, i32, u32, u32, i32, i32, i32, ws, gws));
+        EXPECT_REACHED(CAP(&G, p, 16, 3, 24, nullptr, nullptr, u32, nullptr, nullptr, nullptr, nullptr, ws, gws));
+        EXPECT_REACHED(EMB(&G, p, p, u64p, i32, i32, i32, i32, meta, u64p, ws, pws));
+        EXPECT_REACHED(EMB(&G, p, buf + 32768, u64p, i32, i32, i32, nullptr, meta, u64p, ws, gws));
+        EXPECT_REACHED(AUTO(&G, p, p, u64p, i32, 16, 0, -1, i32, i32, i32, meta, u64p, ws, gws));
+        EXPECT_REACHED(EXT(&G, p, meta, u64p, p, u64p, ws, pws));
+    }
+    printf("abi_args_roi: %d calls, %d failures\n", g_n, g_fail);
+    return g_fail ? 1 : 0;
+}

@@ -3,7 +3,7 @@
 
     hipcc <build flags without -shared> -Iinclude --cuda-device-only -S \\
           codec_tcc_amd/csrc/codec_pee.hip -o a.s        # once per tree
-    python tools/isa_diff.py a.s b.s [--quiet]
+    python tools/isa_diff.py a.s b.s [--quiet] [--by-template]
 
 For every kernel symbol (`.amdhsa_kernel NAME`) of either file the report gives: on which
 side it exists; the resource numbers (VGPR, AGPR, SGPR, LDS bytes, scratch bytes, occupancy,
@@ -18,6 +18,14 @@ others) goes with the kernel's resources, and everything else -- device function
 inlined, `__device__` globals, LDS symbols, the `.set` lines -- is compared as a bag of lines,
 labels blanked, since the emission order may move.  The `__hip_cuid_<hash>` lines, which hash
 the source path, are left out.
+
+--by-template pairs the kernels by name and template arguments and leaves the parameter list
+out of the symbol (`_Z10k_pee_scanItLb1ELb0EE` of `_Z10k_pee_scanItLb1ELb0EEvPKT_...`; an empty
+trailing template-argument pack, `J` `E`, is dropped from it).  A template that gains a trailing
+pack renames every instantiation, the ones with an empty pack too, and the question is then
+whether those kept their resources, argument list and text: the lines that carry the symbol
+itself are left out of the comparison, everything else is compared as usual.  Symbols the
+pattern does not fit, or that would collide, keep their full name.
 
 Exit status 0 when both files hold the same kernels with equal resources and text and the rest
 is equal, else 1.
@@ -97,6 +105,23 @@ def parse(path: str):
     return out, rest
 
 
+TEMPLATE_KEY = re.compile(r"_Z\d+[A-Za-z_][A-Za-z_0-9]*?I(?:[a-z]|L[a-z]\d+E|JE)+E(?=v)")
+
+
+def by_template(kernels: dict) -> dict:
+    """The kernels keyed by name and template arguments where that is unambiguous."""
+    keys = {}
+    for name in kernels:
+        m = TEMPLATE_KEY.match(name)
+        keys[name] = m.group(0).replace("JE", "") if m else name
+    count = collections.Counter(keys.values())
+    out = {}
+    for name, k in kernels.items():
+        out[keys[name] if count[keys[name]] == 1 else name] = dict(
+            k, **{part: [ln for ln in k[part] if name not in ln] for part in ("meta", "text", "amdhsa")})
+    return out
+
+
 def numbers(k: dict) -> str:
     return " ".join(f"{short}={k['info'].get(key, '?')}" for key, short in INFO_KEYS)
 
@@ -108,6 +133,8 @@ def main(argv) -> int:
         print(__doc__, file=sys.stderr)
         return 2
     (a, rest_a), (b, rest_b) = parse(paths[0]), parse(paths[1])
+    if "--by-template" in argv:
+        a, b = by_template(a), by_template(b)
     only_a = sorted(set(a) - set(b))
     only_b = sorted(set(b) - set(a))
     res_diff = text_diff = 0
