@@ -1,6 +1,6 @@
 """ctypes binding of libcodec_hip.so (include/codec_tcc.h, include/codec_tcc_ext.h,
 include/codec_tcc_crc.h, include/codec_tcc_vol.h, include/codec_tcc_gate.h, include/codec_tcc_gvol.h,
-include/codec_tcc_tile.h, include/codec_tcc_roi.h).
+include/codec_tcc_tile.h, include/codec_tcc_roi.h, include/codec_tcc_aead.h).
 
 The library is built in-tree (codec_tcc_amd/libcodec_hip.so, see build.py).  There is no
 CPU fallback: if the library cannot be loaded, every entry point raises RuntimeError.
@@ -140,7 +140,8 @@ KERNEL_TAGS = {1: "k_scan_fast", 2: "k_scan_generic", 3: "k_block_exact", 4: "k_
                33: "k_pee_lat_ss_embed", 34: "k_pee_lat_ss_extract", 35: "k_pee_lat_auto",
                36: "k_crc32", 37: "k_crc32_combine", 38: "k_vol_plan", 39: "k_vol_scatter", 40: "k_vol_gather",
                41: "k_pee_gate_table", 42: "k_gvol_plan", 43: "k_tile_crc", 44: "k_tile_crc_bytes",
-               45: "k_tile_compare", 46: "k_roi_bbox"}
+               45: "k_tile_compare", 46: "k_roi_bbox", 47: "k_chacha20_rows", 48: "k_poly1305_prep", 49: "k_poly1305",
+               50: "k_poly1305_finish", 51: "k_aead_release"}
 EXPORTS = tuple(_SIGS)
 # include/codec_tcc_ext.h: entries added after codec_tcc.h's list (EXPORTS) was fixed
 _SIGS_EXT = {
@@ -239,6 +240,26 @@ _SIGS_ROI = {
 }
 EXPORTS_ROI = tuple(_SIGS_ROI)
 
+
+class AeadCtx(C.Structure):
+    _fields_ = [("key", C.c_uint32 * 8), ("nonce", C.c_uint32 * 2), ("reserved", C.c_uint32 * 2)]
+
+
+AEAD_CTX_BYTES = C.sizeof(AeadCtx)           # 48
+AEAD_STREAM_INDEX = 0x80000000               # CODEC_AEAD_STREAM_INDEX
+AEAD_MAX_ROW_WORDS = 1 << 25                 # CODEC_AEAD_MAX_ROW_WORDS
+# include/codec_tcc_aead.h: keyed MED-PEE, ChaCha20-Poly1305 (aead.py; pee.py, PeeCodec.embed(key=...))
+_SIGS_AEAD = {
+    "codec_poly1305_chunk_bytes": (C.c_size_t, []),
+    "codec_aead_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32]),
+    "codec_chacha20_rows": (C.c_int, [_VP, C.c_int32, C.c_uint32, _VP, C.c_int32, _VP, _VP, _VP]),
+    "codec_poly1305_tags": (C.c_int, [_VP, C.c_int32, C.c_uint32, _VP, C.c_int64, _VP, C.c_int32, _VP, _VP, _VP,
+                                      C.c_size_t, _VP]),
+    "codec_poly1305_tags_otk": (C.c_int, [_VP, C.c_int32, _VP, C.c_int64, _VP, C.c_int32, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "codec_aead_release": (C.c_int, [_VP, C.c_int32, C.c_uint32, _VP, _VP, _VP, C.c_int32, _VP, _VP, _VP, _VP]),
+}
+EXPORTS_AEAD = tuple(_SIGS_AEAD)
+
 _lib = None
 _load_error = None
 # -D flags of diagnostic builds (tools/): never the product library
@@ -267,7 +288,7 @@ def load(path: str = LIB_PATH):
         _load_error = e
         raise RuntimeError(f"cannot load {path}: {e}") from e
     for name, (res, args) in {**_SIGS, **_SIGS_EXT, **_SIGS_CRC, **_SIGS_VOL, **_SIGS_GATE, **_SIGS_GVOL,
-                              **_SIGS_TILE, **_SIGS_ROI}.items():
+                              **_SIGS_TILE, **_SIGS_ROI, **_SIGS_AEAD}.items():
         fn = getattr(lib, name, None)
         if fn is None:
             if name == "codec_build_digest" and not in_tree:   # a diagnostic build (tools/)

@@ -32,10 +32,16 @@ class IntegrityError(ValueError):
     bad_cover / bad_payload: the slices whose cover / payload checksum failed.  tiles: when the
     encoding carried a tile table, {slice: bool ndarray [nty, ntx]} of the tiles of each
     bad_cover slice whose restored pixels differ ({} when no cover failed), else None.
-    tile: the table's (th, tw), or None."""
+    tile: the table's (th, tw), or None.
+    keyed: True when a keyed embedding's Poly1305 tag failed (decode(key=)); slices then names the
+    slices whose tag differs (their plaintext was zeroed on the device)."""
 
-    def __init__(self, message="", *, bad_cover=(), bad_payload=(), tiles=None, tile=None):
+    def __init__(self, message="", *, bad_cover=(), bad_payload=(), tiles=None, tile=None, slices=(), keyed=False,
+                 stream=False):
         super().__init__(message)
+        self.slices = [int(b) for b in slices]
+        self.keyed = bool(keyed)
+        self.stream = bool(stream)   # a keyed volume: the stream's tag failed
         self.bad_cover = [int(b) for b in bad_cover]
         self.bad_payload = [int(b) for b in bad_payload]
         self.tiles = tiles

@@ -486,7 +486,8 @@ def _as_batch(covers):
 
 def encode(covers, payloads: Sequence, *, method: str = "lsb", beta: float = 0.4, block: int = 16,
            align: bool = False, mode: str = "hybrid", nbits: Optional[int] = None, T=2, tmax: int = 16,
-           maxval: Optional[int] = None, scheme: int = 1, tmin: int = 1, gate=None, roi=None):
+           maxval: Optional[int] = None, scheme: int = 1, tmin: int = 1, gate=None, roi=None, key=None, nonce=None,
+           index0: int = 0):
     """Embed one payload per slice.
 
     method="lsb" (default): the reference's bit-plane scheme, bit-exact with src/codec.py;
@@ -504,9 +505,12 @@ def encode(covers, payloads: Sequence, *, method: str = "lsb", beta: float = 0.4
     decode() takes either result."""
     if method == "pee":
         from . import pee
-        return pee.encode(covers, payloads, T=T, tmax=tmax, maxval=maxval, scheme=scheme, tmin=tmin, gate=gate, roi=roi)
+        return pee.encode(covers, payloads, T=T, tmax=tmax, maxval=maxval, scheme=scheme, tmin=tmin, gate=gate, roi=roi,
+                          key=key, nonce=nonce, index0=index0)
     if method != "lsb":
         raise ValueError("method must be 'lsb' or 'pee'")
+    if key is not None or nonce is not None or index0 != 0:
+        raise ValueError("key / nonce / index0 are method='pee''s (keyed MED-PEE)")
     if gate is not None:
         raise ValueError("gate is method='pee''s")
     if roi is not None:
@@ -520,13 +524,15 @@ def encode(covers, payloads: Sequence, *, method: str = "lsb", beta: float = 0.4
     return codec.encode(covers, payloads)
 
 
-def decode(enc, *, restore: bool = True):
+def decode(enc, *, restore: bool = True, key=None):
     """True extraction.  Returns (payload_bit_lists, cover) where payload_bit_lists[b] is a
     numpy 0/1 vector of the embedded bits in message order and cover the restored [B,H,W]
     (LSB: positional recovery; MED-PEE: the exact inverse)."""
     from . import pee
     if isinstance(enc, pee.PeeEncoded):
-        return pee.decode(enc, restore=restore)
+        return pee.decode(enc, restore=restore, key=key)
+    if key is not None:
+        raise ValueError("key is a keyed MED-PEE embedding's (encode(..., method='pee', key=))")
     _require_gpu()
     c = _codec_for(tuple(enc.stego.shape), _in_dtype_name(enc), **_codec_kw(enc))
     # the records are read anyway (total_used frames the bits): read them first and check them,

@@ -277,12 +277,44 @@ def _pee_tile_fields(ext: bytes, width: int, height: int) -> Dict:
     return {"tile": (th, tw), "tile_crc32": table}
 
 
+_PEE_AEAD_TAG = b"A1"
+_PEE_AEAD_NONCE, _PEE_AEAD_MAC = 8, 16
+
+
+def pee_aead_extension(nonce: bytes, tag: bytes) -> bytes:
+    """The header extension of a keyed MED-PEE file: b"A1" + the 8-byte nonce + the
+    16-byte Poly1305 tag, appended after whichever of the b"C1" / b"T1" extensions are present, or
+    directly after the fixed fields.  Readers that do not know it ignore it (and read ciphertext)."""
+    if not isinstance(nonce, (bytes, bytearray)) or len(nonce) != _PEE_AEAD_NONCE:
+        raise ValueError(f"the nonce of the keyed extension has {_PEE_AEAD_NONCE} bytes")
+    if not isinstance(tag, (bytes, bytearray)) or len(tag) != _PEE_AEAD_MAC:
+        raise ValueError(f"the tag of the keyed extension has {_PEE_AEAD_MAC} bytes")
+    return _PEE_AEAD_TAG + bytes(nonce) + bytes(tag)
+
+
+def _pee_aead_fields(ext: bytes) -> Dict:
+    """{'aead_nonce', 'aead_tag'} of the header bytes after the other extensions ({} when they do
+    not start the keyed extension); ValueError for a header cut inside it."""
+    if not ext or ext[:2] != _PEE_AEAD_TAG[:len(ext[:2])]:
+        return {}
+    n = len(_PEE_AEAD_TAG) + _PEE_AEAD_NONCE + _PEE_AEAD_MAC
+    if len(ext) < n:
+        raise ValueError(f"truncated MED-PEE header: a keyed extension of {len(ext)} bytes, {n} needed")
+    return {"aead_nonce": bytes(ext[2:2 + _PEE_AEAD_NONCE]), "aead_tag": bytes(ext[2 + _PEE_AEAD_NONCE:n])}
+
+
 def _pee_ext_fields(ext: bytes, width: int, height: int) -> Dict:
-    """The fields of a header's extensions: the checksum extension's, and the tile extension's
-    when it follows."""
+    """The fields of a header's extensions: the checksum extension's, the tile extension's when
+    it follows, and the keyed extension's after whichever of them are present."""
     md = _pee_crc_fields(ext)
+    rest = ext
     if md:
-        md.update(_pee_tile_fields(ext[len(_PEE_CRC_TAG) + struct.calcsize(_PEE_CRC_FMT):], width, height))
+        rest = ext[len(_PEE_CRC_TAG) + struct.calcsize(_PEE_CRC_FMT):]
+        tiles = _pee_tile_fields(rest, width, height)
+        if tiles:
+            md.update(tiles)
+            rest = rest[len(_PEE_TILE_TAG) + struct.calcsize(_PEE_TILE_FMT) + 4 * tiles["tile_crc32"].size:]
+    md.update(_pee_aead_fields(rest))
     return md
 
 

@@ -24,6 +24,11 @@ embed_volume(..., gate="auto") (or an integer gate; include/codec_tcc_gvol.h) th
 Regions of interest (scheme 1; include/codec_tcc_roi.h, roi.py): codec.embed(..., roi=) takes a
 per-slice pixel rectangle that the stego leaves bit-identical to the cover; the records carry
 it, decode() needs no configuration.
+
+Keyed embedding (include/codec_tcc_aead.h, aead.py): codec.embed(..., key=, nonce=)
+encrypts the payload rows with ChaCha20 and tags (cover, ciphertext) with Poly1305 per slice;
+codec.decode(enc, key=) authenticates the restored cover and the extracted rows on the device
+before any plaintext leaves it.
 """
 from __future__ import annotations
 
@@ -34,7 +39,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _lib, checksum as _ck, framing, roi as _roi
+from . import _lib, aead as _aead, checksum as _ck, framing, roi as _roi
 from .codec import _elem_bytes, _require_gpu, _stream, _torch
 
 
@@ -203,6 +208,9 @@ class PeeEncoded:
     payload_crc: Optional[List[int]] = None      # CRC-32 of each slice's payload bits (checksum.payload_crc32)
     cover_tile_crc: object = None                # torch.int32 [B, nty, ntx] (device): CRC-32 per tile (checksum="tiles")
     tile: Optional[Tuple[int, int]] = None       # the table's (th, tw)
+    tag: object = None                           # torch.int32 [B, 4] (device): Poly1305 tag per slice (embed(key=))
+    nonce: Optional[bytes] = None                # the 8-byte nonce of a keyed embedding
+    index0: int = 0                              # global index of slice 0 (the nonce's first word is index0 + b)
 
     def records(self) -> List[_lib.PeeMeta]:
         """Scheme 1: one record per slice.  Scheme 2: 4 * B records, pass-major."""
@@ -326,6 +334,7 @@ class PeeVolume:
     payload_crc: Optional[int] = None   # CRC-32 of the whole stream (checksum.payload_crc32)
     embedded_bits: Optional[int] = None  # info.total, once read back (check=True): < total_bits when truncated
     gate: object = None               # embed_volume's gate= (None: an ungated volume)
+    tag: object = None                # torch.int32 [1, 4] (device): the stream's Poly1305 tag (embed_volume(key=))
 
     def plan_host(self) -> dict:
         """n, t, off (numpy) and the info record's fields: one read-back.  A gated volume adds
@@ -551,7 +560,7 @@ class PeeCodec:
         return caps
 
     def embed(self, covers, payloads, *, stego=None, lm=None, meta=None, packed=None, check: bool = True,
-              checksum=False, tile=_TILE_UNSET, roi=None) -> PeeEncoded:
+              checksum=False, tile=_TILE_UNSET, roi=None, key=None, nonce=None, index0: int = 0) -> PeeEncoded:
         """cover -> stego + location map + per-slice meta.  check=True (default) reads the
         per-slice status back (one sync) and raises RuntimeError if an in-place look-back
         gave up (CODEC_PEE_ELOOKBACK: the slice is not a valid stego); check=False keeps
@@ -573,8 +582,23 @@ class PeeCodec:
         the cover's); checksum="tiles" does with an explicit tile=.
         tile: the default is a private "not given" marker that stands for checksum.TILE_DEFAULT (64),
         exactly as before; it exists so that a call with roi= and checksum="tiles" can tell whether
-        the tile was chosen by the caller."""
+        the tile was chosen by the caller.
+        key (32 bytes; include/codec_tcc_aead.h): the payload rows are encrypted with
+        ChaCha20 into a buffer of the codec's (caller-packed `packed=` rows are not modified) and
+        enc.tag = the Poly1305 tag of (cover, ciphertext) per slice, queued BEFORE the embed (so an
+        in-place embed authenticates the cover, not the stego); the embed then runs unchanged on the
+        encrypted rows.  nonce: 8 bytes, fresh from os.urandom when None -- never reuse one under
+        a key; index0: the global index of slice 0 (a rank of a sharded stack passes its first
+        slice's), slices index0 .. index0 + B - 1 all < 2^31.  enc.payload_crc is None (the tag
+        covers the payload).  A slice truncated by capacity (record status 1) is reported as
+        today and its tag will not verify.  key=None: nothing of this runs."""
         torch = _torch()
+        if key is not None:   # judged before anything is queued
+            key = _aead.check_key(key)
+            nonce = _aead.fresh_nonce() if nonce is None else _aead.check_nonce(nonce)
+            index0 = _aead.check_index(index0, self.B)
+        elif nonce is not None or index0 != 0:
+            raise ValueError("nonce= and index0= go with key=")
         checksum, tiled = _ck.checksum_mode(checksum)
         tile_given = tile is not _TILE_UNSET
         if not tile_given:
@@ -595,7 +619,7 @@ class PeeCodec:
             cover_crc = _ck.crc32_slices(covers)   # queued first: the host work below runs beside it
             if tiled:
                 tile_crc = _ck.crc32_tiles(covers, tile)
-            if packed is None:   # pack here (what _embed would do) and checksum the packed rows
+            if packed is None and key is None:   # pack here (what _embed would do) and checksum the packed rows
                 bits = [framing.to_bits(p) for p in payloads]
                 if len(bits) != self.B:
                     raise ValueError("one payload per slice is required")
@@ -603,7 +627,16 @@ class PeeCodec:
                 payload_crc = [_ck.payload_crc32_packed(rows[b], lengths[b]) for b in range(self.B)]
                 packed = (torch.from_numpy(rows).to(self.device), lengths,
                           torch.tensor(lengths, dtype=torch.int32, device=self.device))
+        tag = None
+        if key is not None:
+            words, lengths, lens_t = packed if packed is not None else self.pack_payloads(payloads)
+            ctx = _aead.upload_ctx(key, nonce, self.device)
+            ct = _aead.chacha20_rows(ctx, words, lens_t, index0)
+            tag = _aead.poly1305_tags(ctx, covers, ct, lens_t, index0)
+            packed = (ct, lengths, lens_t)
         enc = self._embed(covers, payloads, stego, lm, meta, packed, check, roi)
+        if tag is not None:
+            enc.tag, enc.nonce, enc.index0 = tag, nonce, index0
         enc.cover_crc, enc.payload_crc = cover_crc, payload_crc
         enc.cover_tile_crc, enc.tile = tile_crc, tile
         return enc
@@ -786,7 +819,7 @@ class PeeCodec:
         if mode is None:
             return
         have_c, have_p = enc.cover_crc is not None, enc.payload_crc is not None
-        if mode == "require" and not (have_c and have_p):
+        if mode == "require" and not (have_c and have_p) and getattr(enc, "tag", None) is None:
             missing = [n for n, h in (("cover", have_c), ("payload", have_p)) if not h]
             raise _ck.IntegrityError(f"MED-PEE decode: verify='require' and the embedding carries no "
                                      f"{' / '.join(missing)} checksum")
@@ -823,23 +856,69 @@ class PeeCodec:
         maps = _ck.tile_mismatch_maps(cover, enc.cover_tile_crc, enc.tile, range(self.B))
         return np.stack([maps[b] for b in range(self.B)])
 
-    def decode(self, enc: PeeEncoded, verify=True):
+    def _keyed_check(self, enc: PeeEncoded, key):
+        """decode's key= against the encoding, before any launch; the checked key or None."""
+        keyed = getattr(enc, "tag", None) is not None
+        if keyed and key is None:
+            raise ValueError("the embedding is keyed (enc.tag): decode it with key=")
+        if not keyed and key is not None:
+            raise ValueError("key= given for an embedding that is not keyed (no enc.tag)")
+        if not keyed:
+            return None
+        key = _aead.check_key(key)
+        _aead.check_nonce(enc.nonce)
+        _aead.check_index(enc.index0, self.B)
+        _aead._check_tags(enc.tag, self.B, self.device, "enc.tag")
+        return key
+
+    def _keyed_rows(self, enc: PeeEncoded, key, verify: bool, words, cover):
+        """The extracted (encrypted) rows of a keyed embedding -> the plaintext rows on the host.
+        verify: tags over the restored cover and the extracted rows, then the release (rows of a
+        slice whose tag differs are zeroed on the device), and ONE read-back of rows and ok;
+        returns (host rows, [slices whose tag failed]).  Not verify: decrypt only."""
+        torch = _torch()
+        lens_t = torch.tensor([int(n) for n in enc.lengths], dtype=torch.int32, device=self.device)
+        ctx = _aead.upload_ctx(key, enc.nonce, self.device)
+        if not verify:
+            return _aead.chacha20_rows(ctx, words, lens_t, enc.index0).cpu().numpy(), []
+        got = _aead.poly1305_tags(ctx, cover, words, lens_t, enc.index0)
+        pt, ok = _aead.release(ctx, got, enc.tag, words, lens_t, enc.index0)
+        host = torch.cat([pt.reshape(-1), ok.to(torch.int64)]).cpu().numpy()
+        return host[:-self.B].reshape(self.B, -1), [b for b in range(self.B) if not host[-self.B + b]]
+
+    def _raise_keyed(self, enc: PeeEncoded, cover, bad):
+        if bad:
+            tiles = self._tile_maps(enc, cover, bad)
+            raise _ck.IntegrityError(
+                f"MED-PEE decode: authentication failed in slices {bad} (Poly1305 tag mismatch: wrong key or nonce, "
+                f"or cover / payload / tag altered)" + _ck.tiles_text(tiles, enc.tile, (self.H, self.W)),
+                slices=bad, keyed=True, tiles=tiles, tile=enc.tile)
+
+    def decode(self, enc: PeeEncoded, verify=True, key=None):
         """(list of 0/1 bit vectors, restored cover tensor); raises if a slice overflowed, and
         ValueError for records that are not an embed's (check_records).
         verify=True: the checksums enc carries (embed(..., checksum=True)) are compared with the
         restored cover's (one crc32_slices launch behind the extract) and the payloads';
         IntegrityError names the slices and which of cover / payload failed.  verify=False
-        skips it; verify='require' also raises when a checksum is absent."""
+        skips it; verify='require' also raises when a checksum is absent.
+        key: required for a keyed embedding (embed(key=); ValueError before any launch when it is
+        missing, or given for an unkeyed one).  Order: extract, Poly1305 over the restored cover
+        and the extracted rows, the release (tags compared on the device), then the one read-back,
+        which also brings ok.  IntegrityError (.keyed = True, .slices) names the slices whose tag
+        failed; their plaintext never reaches the host.  verify=False decrypts without the tag
+        pass.  verify='require' is satisfied by the tag, which covers cover and payload."""
         mode = _ck.verify_mode(verify)
-        if mode == "require" and (enc.cover_crc is None or enc.payload_crc is None):
+        key = self._keyed_check(enc, key)
+        if mode == "require" and key is None and (enc.cover_crc is None or enc.payload_crc is None):
             self._verify(enc, mode, None, None)
-        bits, cover = self._decode(enc, mode is not None and enc.cover_crc is not None)
+        bits, cover = self._decode(enc, mode is not None and enc.cover_crc is not None, key, mode is not None)
         self._verify(enc, mode, cover, self._payload_rows)
         return bits, cover
 
-    def _decode(self, enc: PeeEncoded, crc: bool):
+    def _decode(self, enc: PeeEncoded, crc: bool, key=None, auth: bool = True):
         """decode() without the comparison; crc: queue crc32_slices(restored cover) behind the
-        extract, before the payload read-back (self._cover_crc)."""
+        extract, before the payload read-back (self._cover_crc).  key: a keyed embedding's
+        (_keyed_rows; auth: with the tag pass)."""
         if enc.scheme != self.scheme:
             raise ValueError(f"a scheme-{enc.scheme} embedding given to a scheme-{self.scheme} codec")
         self._check_buffers(stego=enc.stego, lm=enc.lm, meta=enc.meta)   # before the records' read-back
@@ -852,7 +931,12 @@ class PeeCodec:
             self._check(enc, prs, enc.lengths)
             words, cover = self.extract(enc.stego, enc.meta, enc.lm, payload_words=enc.payload_words)
             self._cover_crc = _ck.crc32_slices(cover) if crc else None
-            host = self._payload_rows = words.cpu().numpy()   # the extract passes have no look-back (tile or slice-serial)
+            if key is not None:
+                host, bad = self._keyed_rows(enc, key, auth, words, cover)
+                self._payload_rows = host
+                self._raise_keyed(enc, cover, bad)
+            else:
+                host = self._payload_rows = words.cpu().numpy()   # the extract passes have no look-back (tile or slice-serial)
             return [framing.unpack_bits(host[i], enc.lengths[i]) for i in range(self.B)], cover
         recs = enc.records()
         _raise_lookback(recs)
@@ -863,11 +947,17 @@ class PeeCodec:
                                     gated=any(int(r.reserved[1]) != 0 for r in recs),
                                     roi=any(int(r.reserved[2]) != 0 for r in recs))
         self._cover_crc = _ck.crc32_slices(cover) if crc else None
-        host = self._payload_rows = words.cpu().numpy()
+        bad = []
+        if key is not None:
+            host, bad = self._keyed_rows(enc, key, auth, words, cover)
+            self._payload_rows = host
+        else:
+            host = self._payload_rows = words.cpu().numpy()
         if self.lookback_failed(enc.payload_words):
             self.reset()
             raise RuntimeError("codec_pee_extract: in-place cursor look-back timed out; the recovered "
                                "payload is invalid (the restored cover is exact)")
+        self._raise_keyed(enc, cover, bad)
         return [framing.unpack_bits(host[i], enc.lengths[i]) for i in range(self.B)], cover
 
     # ---- volume payloads: one bitstream across the stack (include/codec_tcc_vol.h)
@@ -929,7 +1019,7 @@ class PeeCodec:
 
     def embed_volume(self, covers, payload, *, policy: str = "even", stego=None, check: bool = True,
                      checksum=False, buffers=None, packed=None, gate=None, tile=_ck.TILE_DEFAULT,
-                     roi=None) -> "PeeVolume":
+                     roi=None, key=None, nonce=None, index0: int = 0) -> "PeeVolume":
         """One payload (str / bytes / 0-1 vector, framing.to_bits) embedded across the whole
         stack: the device plans how many bits each slice takes and at which T (the rule of
         include/codec_tcc_vol.h: policy "even" spreads the bits in proportion to the slices'
@@ -957,8 +1047,20 @@ class PeeCodec:
         CRC is then absent, as with embed's packed=).
         checksum="tiles": checksum=True plus enc.cover_tile_crc / enc.tile as embed records them;
         decode_volume then names the tiles of a cover that fails its check.
-        roi: must be None -- volume payloads take no region of interest."""
+        roi: must be None -- volume payloads take no region of interest.
+        key / nonce / index0: the whole stream is encrypted as one row at the reserved
+        index 0x80000000 into a buffer of the codec's, every cover gets a tag with an empty
+        ciphertext at index0 + b (enc.tag, queued before the embed), and after the embed the
+        stream is tagged (vol.tag, empty associated data) over its first info.total bits, the
+        length read on the device -- a truncated volume authenticates exactly the prefix it
+        embedded.  The payload CRC is then absent (the tag covers the payload)."""
         torch = _torch()
+        if key is not None:   # judged before anything is queued
+            key = _aead.check_key(key)
+            nonce = _aead.fresh_nonce() if nonce is None else _aead.check_nonce(nonce)
+            index0 = _aead.check_index(index0, self.B)
+        elif nonce is not None or index0 != 0:
+            raise ValueError("nonce= and index0= go with key=")
         if roi is not None:
             raise ValueError("volume payloads take no region of interest: the plan's capacities are the whole "
                              "slices' (DESIGN §3i); embed per slice with embed(..., roi=)")
@@ -988,6 +1090,12 @@ class PeeCodec:
             torch.from_numpy(framing.pack_bits([bits])[0].reshape(-1)).to(self.device)
         cover_crc = _ck.crc32_slices(covers) if checksum else None   # before an in-place embed
         tile_crc = _ck.crc32_tiles(covers, tile) if tiled else None
+        ctx = cover_tag = None
+        if key is not None:   # the stream encrypted into a new buffer, the covers tagged before the embed
+            ctx = _aead.upload_ctx(key, nonce, self.device)
+            words = _aead.chacha20_rows(ctx, words.reshape(1, -1), torch.tensor([N], dtype=torch.int32, device=self.device),
+                                        _aead.STREAM_INDEX).reshape(-1)
+            cover_tag = _aead.poly1305_tags(ctx, covers, index0=index0)
         if stego is None:
             stego = torch.empty_like(covers)
         if buffers is None:
@@ -1017,7 +1125,10 @@ class PeeCodec:
         enc = PeeEncoded(stego=stego, lm=lm, meta=meta, lengths=[0] * self.B, payload_words=pw,
                          config=config, cover_crc=cover_crc, cover_tile_crc=tile_crc, tile=tile)
         vol = PeeVolume(enc=enc, total_bits=N, policy=policy, plan=plan, info=info, gate=config.get("gate"),
-                        payload_crc=_ck.payload_crc32(bits) if checksum and bits is not None else None)
+                        payload_crc=_ck.payload_crc32(bits) if checksum and bits is not None and key is None else None)
+        if key is not None:   # the stream's tag over info.total (word 2 of either info record), read on the device
+            vol.tag = _aead.poly1305_tags(ctx, None, words.reshape(1, -1), info[2:3], _aead.STREAM_INDEX)
+            enc.tag, enc.nonce, enc.index0 = cover_tag, nonce, index0
         if check:
             host = side.cpu().numpy()   # records, plan and info: one read-back
             raw = host[:nm].tobytes()
@@ -1028,23 +1139,33 @@ class PeeCodec:
             p = _plan_dict(host[nm:nm + npl], host[nm + npl:], self.B, gated)
             enc.lengths = [int(v) for v in p["n"]]
             vol.embedded_bits = p["total"]
-            if checksum and bits is not None and p["total"] < N:
+            if checksum and bits is not None and key is None and p["total"] < N:
                 vol.payload_crc = _ck.payload_crc32(bits[:p["total"]])
         return vol
 
-    def decode_volume(self, vol: "PeeVolume", verify=True):
+    def decode_volume(self, vol: "PeeVolume", verify=True, key=None):
         """(bits, covers): the stream's embedded bits as one 0/1 vector (the first
         embedded_bits of a truncated volume) and the restored stack.  The records are read back
         and judged by check_records first; extract and the stream's reassembly are launches on
         the current stream, then one read-back of the stream.  verify as decode(): the cover
-        CRCs per slice and the one payload CRC embed_volume(checksum=True) recorded."""
+        CRCs per slice and the one payload CRC embed_volume(checksum=True) recorded.
+        key: required for a keyed volume (embed_volume(key=)); ValueError before any launch when
+        it is missing, or given for an unkeyed one.  The stream is tagged and released over the
+        embedded total (read on the device) and every restored cover's tag is compared, all on
+        the device; IntegrityError (.keyed; .slices = covers that failed, .stream = the stream
+        failed, whose plaintext then never reaches the host).  verify=False decrypts only."""
         torch = _torch()
         mode = _ck.verify_mode(verify)
         enc = vol.enc
         if enc.scheme != 1 or self.scheme != 1:
             raise ValueError("volume payloads are scheme 1's")
+        if (vol.tag is None) != (enc.tag is None):
+            raise ValueError("a keyed volume carries both the stream's tag (vol.tag) and the covers' (enc.tag)")
+        key = self._keyed_check(enc, key)
+        if key is not None:
+            _aead._check_tags(vol.tag, 1, self.device, "vol.tag")
         have_c, have_p = enc.cover_crc is not None, vol.payload_crc is not None
-        if mode == "require" and not (have_c and have_p):
+        if mode == "require" and key is None and not (have_c and have_p):
             missing = [n for n, h in (("cover", have_c), ("payload", have_p)) if not h]
             raise _ck.IntegrityError(f"MED-PEE decode: verify='require' and the volume carries no "
                                      f"{' / '.join(missing)} checksum")
@@ -1070,12 +1191,38 @@ class PeeCodec:
             sw, out.data_ptr() + 8 * sw, self.workspace.data_ptr(), self.workspace.numel(), vws.data_ptr(),
             vws.numel(), _stream()), what))
         self._cover_crc = _ck.crc32_slices(cover) if (mode is not None and have_c) else None
-        host = out.cpu().numpy()
+        bad_k, bad_stream = [], False
+        if key is not None:   # tags and release over the embedded total, then the one read-back (with ok)
+            ctx = _aead.upload_ctx(key, enc.nonce, self.device)
+            rows, total_t = out[:sw].reshape(1, sw), out[sw:].view(torch.int32)[:1]
+            if mode is None:
+                pt = _aead.chacha20_rows(ctx, rows, total_t, _aead.STREAM_INDEX)
+                host = torch.cat([pt.reshape(-1), out[sw:]]).cpu().numpy()
+            else:
+                stag = _aead.poly1305_tags(ctx, None, rows, total_t, _aead.STREAM_INDEX)
+                ctag = _aead.poly1305_tags(ctx, cover, index0=enc.index0)
+                pt, ok_s = _aead.release(ctx, stag, vol.tag, rows, total_t, _aead.STREAM_INDEX)
+                none = torch.zeros((self.B, 1), dtype=torch.int64, device=self.device)   # the covers' tags: an empty CT
+                _z, ok_c = _aead.release(ctx, ctag, enc.tag, none, torch.zeros(self.B, dtype=torch.int32, device=self.device),
+                                         enc.index0)
+                host = torch.cat([pt.reshape(-1), out[sw:], ok_s.to(torch.int64), ok_c.to(torch.int64)]).cpu().numpy()
+                bad_stream = not host[sw + 1]
+                bad_k = [b for b in range(self.B) if not host[sw + 2 + b]]
+            self._payload_rows = host[:sw]
+        else:
+            host = out.cpu().numpy()
         if self.lookback_failed(enc.payload_words):
             self.reset()
             raise RuntimeError("codec_pee_extract: in-place cursor look-back timed out; the recovered "
                                "payload is invalid (the restored cover is exact)")
-        total = min(int(host[sw:].view(np.int32)[0]), int(vol.total_bits))
+        if bad_k or bad_stream:
+            tiles = self._tile_maps(enc, cover, bad_k)
+            what = ([f"the covers of slices {bad_k}"] if bad_k else []) + (["the stream"] if bad_stream else [])
+            raise _ck.IntegrityError(
+                f"MED-PEE decode: authentication failed for {' and '.join(what)} (Poly1305 tag mismatch: wrong key or "
+                f"nonce, or cover / payload / tag altered)" + _ck.tiles_text(tiles, enc.tile, (self.H, self.W)),
+                slices=bad_k, keyed=True, stream=bad_stream, tiles=tiles, tile=enc.tile)
+        total = min(int(host[sw:sw + 1].view(np.int32)[0]), int(vol.total_bits))
         bits = framing.unpack_bits(host[:sw], total)
         if mode is not None:
             bad_c = self._cover_mismatches(enc) if have_c else []
@@ -1349,7 +1496,8 @@ def _config_from_records(enc: "PeeEncoded") -> dict:
 
 
 def encode(covers, payloads: Sequence, *, T=2, tmax: int = 16, maxval: Optional[int] = None,
-           scheme: int = 1, tmin: int = 1, checksum=False, gate=None, tile=_TILE_UNSET, roi=None) -> PeeEncoded:
+           scheme: int = 1, tmin: int = 1, checksum=False, gate=None, tile=_TILE_UNSET, roi=None, key=None, nonce=None,
+           index0: int = 0) -> PeeEncoded:
     """MED-PEE embed of one payload per slice (the package's `encode(..., method="pee")`).
     covers: [B,H,W] / [H,W] uint8/uint16 torch tensor or numpy array; T: expansion threshold
     or "auto" (smallest T <= tmax whose capacity holds each slice's payload); maxval: the
@@ -1362,7 +1510,12 @@ def encode(covers, payloads: Sequence, *, T=2, tmax: int = 16, maxval: Optional[
     roi (scheme 1): a rectangle (y0, x0, y1, x1) for every slice or [B, 4] of them that the stego leaves
     untouched (PeeCodec.embed); decode() reads it from the records.
     tile: not given = checksum.TILE_DEFAULT (64), as before (PeeCodec.embed explains the marker).
+    key / nonce / index0: a keyed embedding (PeeCodec.embed; ChaCha20-Poly1305); decode(enc, key=).
     Raises ValueError when a payload exceeds its slice's capacity."""
+    if key is not None:   # before the GPU is touched
+        _aead.check_key(key)
+        if nonce is not None:
+            _aead.check_nonce(nonce)
     shape = tuple(covers.shape)
     check_gate_args(gate, T, tmax, (int(shape[-2]) // 2) * (int(shape[-1]) // 2) if len(shape) >= 2 else 0, scheme)
     if roi is not None:   # every rule but the values', which need the batch shape (PeeCodec.embed)
@@ -1376,7 +1529,7 @@ def encode(covers, payloads: Sequence, *, T=2, tmax: int = 16, maxval: Optional[
         payloads = [payloads]
     dt = "uint16" if _elem_bytes(covers) == 2 else "uint8"
     codec = _codec_for(tuple(covers.shape), dt, T=T, tmax=tmax, maxval=maxval, scheme=scheme, tmin=tmin, gate=gate)
-    enc = codec.embed(covers, payloads, checksum=checksum, tile=tile, roi=roi)
+    enc = codec.embed(covers, payloads, checksum=checksum, tile=tile, roi=roi, key=key, nonce=nonce, index0=index0)
     if scheme == 2:
         short = [i for i, (g, n) in enumerate(zip(enc.embedded(), enc.lengths)) if g < n]
         if short:
@@ -1386,22 +1539,24 @@ def encode(covers, payloads: Sequence, *, T=2, tmax: int = 16, maxval: Optional[
     return enc
 
 
-def decode(enc: PeeEncoded, verify=True, *, restore: bool = True):
+def decode(enc: PeeEncoded, verify=True, *, restore: bool = True, key=None):
     """Exact extraction: (payload_bit_lists, cover) like the LSB decode() -- payload_bit_lists[b]
     is a numpy 0/1 vector of slice b's embedded bits, cover the restored [B,H,W] tensor
     (None with restore=False).  verify: PeeCodec.decode's (True checks the checksums the
-    encoding carries, False skips, 'require' insists on them; IntegrityError on a mismatch)."""
+    encoding carries, False skips, 'require' insists on them; IntegrityError on a mismatch).
+    key: a keyed embedding's (PeeCodec.decode)."""
     _require_gpu()
     cfg = enc.config or _config_from_records(enc)
     codec = _codec_for(tuple(enc.stego.shape), cfg.get("dtype", "uint16"), T=cfg.get("T", 2),
                        tmax=cfg.get("tmax", 16), maxval=cfg.get("maxval"), scheme=int(getattr(enc, "scheme", 1)),
                        tmin=cfg.get("tmin", 1))
-    bits, cover = codec.decode(enc, verify)
+    bits, cover = codec.decode(enc, verify, key=key)
     return bits, (cover if restore else None)
 
 
 def encode_volume(covers, payload, *, policy: str = "even", tmax: int = 16, maxval: Optional[int] = None,
-                  checksum=False, scheme: int = 1, gate=None, tile=_ck.TILE_DEFAULT) -> PeeVolume:
+                  checksum=False, scheme: int = 1, gate=None, tile=_ck.TILE_DEFAULT, key=None, nonce=None,
+                  index0: int = 0) -> PeeVolume:
     """MED-PEE embed of ONE payload across a [B,H,W] stack (PeeCodec.embed_volume): the bits are
     spread over the slices on the device (policy "even": in proportion to capacity; "fill": in
     slice order), each slice at the smallest T <= tmax that holds its share.  gate: a smoothness
@@ -1409,7 +1564,11 @@ def encode_volume(covers, payload, *, policy: str = "even", tmax: int = 16, maxv
     decode_volume() reads the gates from the records.  Raises ValueError
     when the volume cannot hold the payload at tmax, as encode() does per slice; argument errors
     (policy, scheme 2, more than 2^31 - 1 bits or candidates, a shape that is no stack) are
-    ValueError before the GPU is touched."""
+    ValueError before the GPU is touched.  key / nonce / index0: a keyed volume (PeeCodec.embed_volume)."""
+    if key is not None:
+        _aead.check_key(key)
+        if nonce is not None:
+            _aead.check_nonce(nonce)
     shape = tuple(covers.shape)
     bits = framing.to_bits(payload)
     check_volume_args(shape if len(shape) != 2 else (1,) + shape, bits.size, policy, scheme)
@@ -1420,14 +1579,15 @@ def encode_volume(covers, payload, *, policy: str = "even", tmax: int = 16, maxv
     covers = _as_gpu_batch(covers)
     dt = "uint16" if _elem_bytes(covers) == 2 else "uint8"
     codec = _codec_for(tuple(covers.shape), dt, T="auto", tmax=tmax, maxval=maxval)
-    vol = codec.embed_volume(covers, bits, policy=policy, checksum=checksum, gate=gate, tile=tile)
+    vol = codec.embed_volume(covers, bits, policy=policy, checksum=checksum, gate=gate, tile=tile, key=key, nonce=nonce,
+                             index0=index0)
     if vol.embedded_bits < vol.total_bits:
         raise ValueError(f"payload of {vol.total_bits} bits exceeds the volume's PEE capacity "
                          f"{vol.embedded_bits} (tmax={tmax})")
     return vol
 
 
-def decode_volume(vol: PeeVolume, verify=True, *, restore: bool = True):
+def decode_volume(vol: PeeVolume, verify=True, *, restore: bool = True, key=None):
     """(bits, covers) of an encode_volume / embed_volume result: the payload as one 0/1 vector and
     the restored [B,H,W] stack (None with restore=False).  verify: as decode()."""
     _require_gpu()
@@ -1435,7 +1595,7 @@ def decode_volume(vol: PeeVolume, verify=True, *, restore: bool = True):
     cfg = enc.config or _config_from_records(enc)
     codec = _codec_for(tuple(enc.stego.shape), cfg.get("dtype", "uint16"), T="auto", tmax=cfg.get("tmax", 16),
                        maxval=cfg.get("maxval"))
-    bits, cover = codec.decode_volume(vol, verify)
+    bits, cover = codec.decode_volume(vol, verify, key=key)
     return bits, (cover if restore else None)
 
 

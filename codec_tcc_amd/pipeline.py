@@ -140,7 +140,7 @@ def decode_bin_exact(filepath: str, search_block_size: Optional[int] = None) -> 
 # ------------------------------------------------------------------ MED-PEE files
 def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxval: Optional[int] = None,
                     codec: str = "raw", scheme: int = 1, tmin: int = 1, checksum=False, gate=None, tile=64,
-                    roi=None) -> Dict:
+                    roi=None, key=None, nonce=None) -> Dict:
     """MED-PEE embed of one slice into a version-16 STGC file.  `image` is an array or a
     DICOM path; maxval defaults to the DICOM's full scale 2**BitsStored - 1 (4095 for the
     reference's 12-bit pe.dcm), else the dtype maximum.  T = 'auto' picks the smallest
@@ -160,8 +160,20 @@ def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxva
     roi (scheme 1): a rectangle (y0, x0, y1, x1) the stego leaves bit-identical to the cover
     (PeeCodec.embed): the file then carries scheme byte 4 -- byte 3's fields (the gate
     65535 when none was asked for) and the rectangle ('roi' in the result).  An empty rectangle is
-    no rectangle: the file is what it is without roi=.  Without roi the file's bytes are unchanged."""
+    no rectangle: the file is what it is without roi=.  Without roi the file's bytes are unchanged.
+    key (32 bytes) / nonce (8 bytes, fresh when None): a keyed file (PeeCodec.embed(key=), DESIGN
+    §3j): the stego carries the ChaCha20 ciphertext and the header ends with the keyed extension
+    (container.pee_aead_extension: nonce and Poly1305 tag; 'nonce' / 'tag' in the result), after
+    the checksum extensions when those are asked for -- their payload field is then 0 and not
+    verified (the tag covers the payload; a CRC of the plaintext would tell about it).  A payload
+    truncated by capacity does not authenticate.  Without key the file's bytes are unchanged."""
+    from . import aead as _aead
     from . import checksum as _ck
+    if key is not None:   # before the GPU is touched
+        key = _aead.check_key(key)
+        nonce = _aead.fresh_nonce() if nonce is None else _aead.check_nonce(nonce)
+    elif nonce is not None:
+        raise ValueError("nonce= goes with key=")
     from .pee import PeeCodec, check_gate_args, check_roi_args, lm_bits
     checksum, tiled = _ck.checksum_mode(checksum)
     tile = _ck.check_tile_args(tile) if tiled else None
@@ -186,17 +198,22 @@ def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxva
     pc = PeeCodec(1, h, w, dtype=str(img.dtype), T=T, tmin=tmin, tmax=tmax, maxval=maxval, scheme=scheme, gate=gate)
     enc = pc.embed(torch.from_numpy(np.ascontiguousarray(img)[None]).cuda(), [bits],
                    checksum="tiles" if tiled else checksum, **({"tile": tile} if tiled else {}),
-                   **({"roi": roi} if roi is not None else {}))
+                   **({"roi": roi} if roi is not None else {}),
+                   **({"key": key, "nonce": nonce} if key is not None else {}))
 
     def ext(embedded: int) -> Tuple[bytes, Dict]:
-        if not checksum:
-            return b"", {}
-        crcs = {"cover_crc32": _ck.crc_list(enc.cover_crc)[0], "payload_crc32": _ck.payload_crc32(bits[:embedded])}
-        xb = container.pee_crc_extension(crcs["cover_crc32"], crcs["payload_crc32"])
-        if tiled:
-            crcs["tile"] = tile
-            crcs["tile_crc32"] = enc.cover_tile_crc[0].cpu().numpy().view(np.uint32)
-            xb += container.pee_tile_extension(tile[0], tile[1], crcs["tile_crc32"])
+        xb, crcs = b"", {}
+        if checksum:
+            crcs = {"cover_crc32": _ck.crc_list(enc.cover_crc)[0],
+                    "payload_crc32": _ck.payload_crc32(bits[:embedded]) if key is None else 0}
+            xb = container.pee_crc_extension(crcs["cover_crc32"], crcs["payload_crc32"])
+            if tiled:
+                crcs["tile"] = tile
+                crcs["tile_crc32"] = enc.cover_tile_crc[0].cpu().numpy().view(np.uint32)
+                xb += container.pee_tile_extension(tile[0], tile[1], crcs["tile_crc32"])
+        if key is not None:
+            crcs.update(nonce=nonce, tag=_aead.tag_bytes(enc.tag)[0])
+            xb += container.pee_aead_extension(nonce, crcs["tag"])
         return xb, crcs
     if scheme == 2:
         prs = [pr[0] for pr in enc.pass_records()]
@@ -291,23 +308,36 @@ def read_pee_bytes(raw: bytes) -> PeeFile:
     return PeeFile(md=md, scheme=scheme, records=records, lm=lm, stego=stego, payload_words=pw, lm_words=lm_words)
 
 
-def decode_bin_pee(filepath: str, verify=True) -> Tuple[np.ndarray, np.ndarray]:
+def decode_bin_pee(filepath: str, verify=True, key=None) -> Tuple[np.ndarray, np.ndarray]:
     """(payload bits as a 0/1 uint8 vector, restored cover) from a version-16 STGC file
     (either scheme): read_pee_bytes on the host, then one extract launch.
     verify=True: a file with the checksum extension is checked -- the restored cover's CRC-32
     (one GPU pass behind the extract) and the payload's against the header's; IntegrityError
     names what failed, and for a file with the tile extension its `tiles` attribute maps the tiles
-    of the cover that differ.  False skips it; 'require' also raises for a file without checksums."""
+    of the cover that differ.  False skips it; 'require' also raises for a file without checksums.
+    key: required for a file with the keyed extension (encode_file_pee(key=)); a keyed file without
+    key=, or key= for a file without the extension, is a ValueError before the GPU is touched.  The
+    restored cover and the extracted rows are tagged and compared on the device; IntegrityError
+    (.keyed, .slices == [0]) when the tag fails, and no plaintext reaches the host.  verify=False
+    decrypts without the tag pass."""
+    from . import aead as _aead
     from . import checksum as _ck
     from .pee import PeeCodec
     mode = _ck.verify_mode(verify)
     with open(filepath, "rb") as f:
         pf = read_pee_bytes(f.read())
+    keyed = "aead_tag" in pf.md
+    if keyed and key is None:
+        raise ValueError("the file is keyed (its header carries the A1 extension): decode it with key=")
+    if not keyed and key is not None:
+        raise ValueError("key= given for a file that is not keyed (no A1 extension)")
+    if keyed:
+        key = _aead.check_key(key)
     _require_gpu()
     torch = _torch()
     md, h, w = pf.md, pf.stego.shape[0], pf.stego.shape[1]
     have = "cover_crc32" in md
-    if mode == "require" and not have:
+    if mode == "require" and not have and not keyed:
         raise _ck.IntegrityError("MED-PEE file: verify='require' and the header carries no checksums")
     pc = PeeCodec(1, h, w, dtype=str(pf.stego.dtype), T=md["T"], maxval=md["maxval"], scheme=pf.scheme)
     metas = b"".join(bytes(r) for pr in pf.records for r in pr)
@@ -319,10 +349,31 @@ def decode_bin_pee(filepath: str, verify=True) -> Tuple[np.ndarray, np.ndarray]:
                               payload_words=pf.payload_words, **({"gated": True} if "gate" in md else {}),
                               **({"roi": True} if "roi" in md else {}))
     crc = _ck.crc32_slices(cover) if (mode and have) else None
-    bits = framing.unpack_bits(words.cpu().numpy()[0], md["L"])
+    if keyed:   # tag the restored cover and the extracted rows, release, one read-back with ok
+        ctx = _aead.upload_ctx(key, md["aead_nonce"], words.device)
+        lens = torch.tensor([md["L"]], dtype=torch.int32, device=words.device)
+        if mode is None:
+            host = _aead.chacha20_rows(ctx, words, lens, 0).cpu().numpy()[0]
+        else:
+            want = torch.from_numpy(np.frombuffer(md["aead_tag"], dtype="<i4").reshape(1, 4).copy()).to(words.device)
+            pt, ok = _aead.release(ctx, _aead.poly1305_tags(ctx, cover, words, lens, 0), want, words, lens, 0)
+            both = torch.cat([pt.reshape(-1), ok.to(torch.int64)]).cpu().numpy()
+            host = both[:-1]
+            if not both[-1]:
+                tiles = None
+                if "tile_crc32" in md:
+                    table = torch.from_numpy(md["tile_crc32"].view(np.int32)[None].copy()).cuda()
+                    tiles = _ck.tile_mismatch_maps(cover, table, md["tile"], [0])
+                raise _ck.IntegrityError("MED-PEE file: authentication failed (Poly1305 tag mismatch: wrong key, or the "
+                                         "file's pixels, records, nonce or tag altered)"
+                                         + _ck.tiles_text(tiles, md.get("tile"), (h, w)),
+                                         slices=[0], keyed=True, tiles=tiles, tile=md.get("tile"))
+        bits = framing.unpack_bits(host, md["L"])
+    else:
+        bits = framing.unpack_bits(words.cpu().numpy()[0], md["L"])
     if crc is not None:
         bad_c = [0] if _ck.crc_list(crc)[0] != md["cover_crc32"] else []
-        bad_p = [0] if _ck.payload_crc32(bits) != md["payload_crc32"] else []
+        bad_p = [0] if not keyed and _ck.payload_crc32(bits) != md["payload_crc32"] else []
         tiles = None
         if (bad_c or bad_p) and "tile_crc32" in md:   # the tile pass runs only for a cover that failed
             table = torch.from_numpy(md["tile_crc32"].view(np.int32)[None].copy()).cuda()
