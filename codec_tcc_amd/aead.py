@@ -58,6 +58,20 @@ def check_index(index0, B: int = 1) -> int:
     return index0
 
 
+def check_call(key, nonce, index0=0, B: int = 1, *, fresh: bool = True,
+               lone: Optional[str] = "nonce= and index0= go with key="):
+    """(key, nonce, index0) of a call's key= / nonce= / index0=, judged before anything is queued.
+    key=None: the other two must be absent (ValueError `lone`; lone=None leaves that to a later
+    check).  fresh: a missing nonce is drawn from os.urandom."""
+    if key is None:
+        if lone and (nonce is not None or index0 != 0):
+            raise ValueError(lone)
+        return None, nonce, index0
+    key = check_key(key)
+    nonce = (fresh_nonce() if fresh else None) if nonce is None else check_nonce(nonce)
+    return key, nonce, check_index(index0, B)
+
+
 def ctx_bytes(key, nonce) -> bytes:
     """The 48-byte codec_aead_ctx of (key, nonce) (pure host)."""
     return check_key(key) + check_nonce(nonce) + bytes(8)

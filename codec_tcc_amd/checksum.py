@@ -34,11 +34,15 @@ class IntegrityError(ValueError):
     bad_cover slice whose restored pixels differ ({} when no cover failed), else None.
     tile: the table's (th, tw), or None.
     keyed: True when a keyed embedding's Poly1305 tag failed (decode(key=)); slices then names the
-    slices whose tag differs (their plaintext was zeroed on the device)."""
+    slices whose tag differs (their plaintext was zeroed on the device).
+    rows: the payload rows exactly as the decode's one read-back brought them to the host (a
+    volume: the stream's words; the failed slices of a keyed failure: the zeros the device
+    released), None when the error was raised before any read-back."""
 
     def __init__(self, message="", *, bad_cover=(), bad_payload=(), tiles=None, tile=None, slices=(), keyed=False,
-                 stream=False):
+                 stream=False, rows=None):
         super().__init__(message)
+        self.rows = rows
         self.slices = [int(b) for b in slices]
         self.keyed = bool(keyed)
         self.stream = bool(stream)   # a keyed volume: the stream's tag failed
@@ -142,20 +146,24 @@ def verify_mode(verify) -> Optional[str]:
     raise ValueError("verify must be True, False or 'require'")
 
 
-def raise_mismatch(bad_cover, bad_payload, what: str = "MED-PEE decode", *, tiles=None, tile=None, shape=None):
+def raise_mismatch(bad_cover, bad_payload, what: str = "MED-PEE decode", *, tiles=None, tile=None, shape=None,
+                   stream: bool = False, rows=None):
     """IntegrityError naming the slices whose cover / payload checksum failed (none: returns).
     tiles / tile: the differing-tile maps of the bad covers and their tile size (IntegrityError's
-    attributes); shape = (H, W) lets the message give the tiles' pixel boxes."""
-    if not bad_cover and not bad_payload:
+    attributes); shape = (H, W) lets the message give the tiles' pixel boxes.  stream: a volume's
+    one payload checksum failed; rows: IntegrityError.rows."""
+    if not bad_cover and not bad_payload and not stream:
         return
     parts = []
     if bad_cover:
         parts.append(f"cover checksum mismatch in slices {list(bad_cover)}")
     if bad_payload:
         parts.append(f"payload checksum mismatch in slices {list(bad_payload)}")
+    if stream:
+        parts.append("the volume's payload checksum does not match")
     raise IntegrityError(f"{what}: {'; '.join(parts)} (CRC-32: this is not what was embedded)"
                          + tiles_text(tiles, tile, shape),
-                         bad_cover=bad_cover, bad_payload=bad_payload, tiles=tiles, tile=tile)
+                         bad_cover=bad_cover, bad_payload=bad_payload, tiles=tiles, tile=tile, rows=rows)
 
 
 # ------------------------------------------------------------------ tile checksums

@@ -169,11 +169,7 @@ def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxva
     truncated by capacity does not authenticate.  Without key the file's bytes are unchanged."""
     from . import aead as _aead
     from . import checksum as _ck
-    if key is not None:   # before the GPU is touched
-        key = _aead.check_key(key)
-        nonce = _aead.fresh_nonce() if nonce is None else _aead.check_nonce(nonce)
-    elif nonce is not None:
-        raise ValueError("nonce= goes with key=")
+    key, nonce, _index0 = _aead.check_call(key, nonce, lone="nonce= goes with key=")   # before the GPU is touched
     from .pee import PeeCodec, check_gate_args, check_roi_args, lm_bits
     checksum, tiled = _ck.checksum_mode(checksum)
     tile = _ck.check_tile_args(tile) if tiled else None
@@ -319,64 +315,39 @@ def decode_bin_pee(filepath: str, verify=True, key=None) -> Tuple[np.ndarray, np
     key=, or key= for a file without the extension, is a ValueError before the GPU is touched.  The
     restored cover and the extracted rows are tagged and compared on the device; IntegrityError
     (.keyed, .slices == [0]) when the tag fails, and no plaintext reaches the host.  verify=False
-    decrypts without the tag pass."""
-    from . import aead as _aead
-    from . import checksum as _ck
-    from .pee import PeeCodec
+    decrypts without the tag pass.  What follows the extract is pee_verify.after_extract, as for
+    PeeCodec.decode: a scheme-1 extract whose look-back gave up raises decode()'s RuntimeError."""
+    from . import checksum as _ck, pee_verify as _pv
+    from .pee import PeeCodec, PeeEncoded
     mode = _ck.verify_mode(verify)
     with open(filepath, "rb") as f:
         pf = read_pee_bytes(f.read())
-    keyed = "aead_tag" in pf.md
-    if keyed and key is None:
-        raise ValueError("the file is keyed (its header carries the A1 extension): decode it with key=")
-    if not keyed and key is not None:
-        raise ValueError("key= given for a file that is not keyed (no A1 extension)")
-    if keyed:
-        key = _aead.check_key(key)
+    md, (h, w) = pf.md, pf.stego.shape
+    keyed = "aead_tag" in md
+    key = _pv.check_key(keyed, key, "file", "its header carries the A1 extension", "A1 extension")
     _require_gpu()
     torch = _torch()
-    md, h, w = pf.md, pf.stego.shape[0], pf.stego.shape[1]
     have = "cover_crc32" in md
-    if mode == "require" and not have and not keyed:
-        raise _ck.IntegrityError("MED-PEE file: verify='require' and the header carries no checksums")
+    _pv.check_require(mode, keyed, have, have, "MED-PEE file", "the header", named=False)
     pc = PeeCodec(1, h, w, dtype=str(pf.stego.dtype), T=md["T"], maxval=md["maxval"], scheme=pf.scheme)
     metas = b"".join(bytes(r) for pr in pf.records for r in pr)
     meta_t = torch.frombuffer(bytearray(metas), dtype=torch.uint8).view(len(pf.records), 1, -1).cuda()
     lm_t = torch.from_numpy(np.packbits(pf.lm, axis=-1, bitorder="little").view(np.int64).copy()).cuda()
     if pf.scheme == 1:
         meta_t, lm_t = meta_t[0], lm_t[0]
-    words, cover = pc.extract(torch.from_numpy(np.ascontiguousarray(pf.stego)[None]).cuda(), meta_t, lm_t,
-                              payload_words=pf.payload_words, **({"gated": True} if "gate" in md else {}),
-                              **({"roi": True} if "roi" in md else {}))
-    crc = _ck.crc32_slices(cover) if (mode and have) else None
-    if keyed:   # tag the restored cover and the extracted rows, release, one read-back with ok
-        ctx = _aead.upload_ctx(key, md["aead_nonce"], words.device)
-        lens = torch.tensor([md["L"]], dtype=torch.int32, device=words.device)
-        if mode is None:
-            host = _aead.chacha20_rows(ctx, words, lens, 0).cpu().numpy()[0]
-        else:
-            want = torch.from_numpy(np.frombuffer(md["aead_tag"], dtype="<i4").reshape(1, 4).copy()).to(words.device)
-            pt, ok = _aead.release(ctx, _aead.poly1305_tags(ctx, cover, words, lens, 0), want, words, lens, 0)
-            both = torch.cat([pt.reshape(-1), ok.to(torch.int64)]).cpu().numpy()
-            host = both[:-1]
-            if not both[-1]:
-                tiles = None
-                if "tile_crc32" in md:
-                    table = torch.from_numpy(md["tile_crc32"].view(np.int32)[None].copy()).cuda()
-                    tiles = _ck.tile_mismatch_maps(cover, table, md["tile"], [0])
-                raise _ck.IntegrityError("MED-PEE file: authentication failed (Poly1305 tag mismatch: wrong key, or the "
-                                         "file's pixels, records, nonce or tag altered)"
-                                         + _ck.tiles_text(tiles, md.get("tile"), (h, w)),
-                                         slices=[0], keyed=True, tiles=tiles, tile=md.get("tile"))
-        bits = framing.unpack_bits(host, md["L"])
-    else:
-        bits = framing.unpack_bits(words.cpu().numpy()[0], md["L"])
-    if crc is not None:
-        bad_c = [0] if _ck.crc_list(crc)[0] != md["cover_crc32"] else []
-        bad_p = [0] if not keyed and _ck.payload_crc32(bits) != md["payload_crc32"] else []
-        tiles = None
-        if (bad_c or bad_p) and "tile_crc32" in md:   # the tile pass runs only for a cover that failed
-            table = torch.from_numpy(md["tile_crc32"].view(np.int32)[None].copy()).cuda()
-            tiles = _ck.tile_mismatch_maps(cover, table, md["tile"], bad_c) if bad_c else {}
-        _ck.raise_mismatch(bad_c, bad_p, "MED-PEE file", tiles=tiles, tile=md.get("tile"), shape=(h, w))
-    return bits, cover.cpu().numpy()[0]
+    # what the header states, as an embedding: the records were judged on the host (read_pee_bytes) and
+    # are not read back; the tile table stays on the host until a cover fails; a keyed file's payload
+    # CRC field is not verified (the tag covers the payload)
+    enc = PeeEncoded(stego=torch.from_numpy(np.ascontiguousarray(pf.stego)[None]).cuda(), lm=lm_t, meta=meta_t,
+                     lengths=[md["L"]], payload_words=pf.payload_words, scheme=pf.scheme,
+                     cover_crc=[md["cover_crc32"]] if have else None,
+                     payload_crc=[md["payload_crc32"]] if have and not keyed else None,
+                     cover_tile_crc=md["tile_crc32"].view(np.int32)[None].copy() if "tile_crc32" in md else None,
+                     tile=md.get("tile"), nonce=md.get("aead_nonce"))
+    if keyed and mode is not None:
+        enc.tag = torch.from_numpy(np.frombuffer(md["aead_tag"], dtype="<i4").reshape(1, 4).copy()).cuda()
+    words, cover = pc.extract(enc.stego, meta_t, lm_t, payload_words=pf.payload_words,
+                              **({"gated": True} if "gate" in md else {}), **({"roi": True} if "roi" in md else {}))
+    # scheme 1's B = 1 out-of-place extract takes the flat look-back route: its flag is read (as decode() does)
+    rows, _total = _pv.after_extract(pc, enc, cover, words, mode, key, what="MED-PEE file", lookback=pf.scheme == 1)
+    return framing.unpack_bits(rows[0], md["L"]), cover.cpu().numpy()[0]

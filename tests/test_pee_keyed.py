@@ -114,7 +114,7 @@ def _fails(codec, enc, key, slices):
     with pytest.raises(IntegrityError) as e:
         codec.decode(enc, key=key)
     assert e.value.keyed is True and e.value.slices == slices
-    rows = codec._payload_rows                       # what the one read-back brought
+    rows = e.value.rows                              # what the one read-back brought
     for b in range(B):
         assert (not rows[b].any()) == (b in slices), b
 

@@ -82,12 +82,12 @@ def test_keyed_volume_refuses_what_was_not_embedded(covers):
     vol, cov, bits = _check_volume(codec, covers, 600, "even")
     with pytest.raises(IntegrityError) as e:
         codec.decode_volume(vol, key=bytes(32))                                # a wrong key
-    assert e.value.keyed and e.value.stream and e.value.slices == [0, 1, 2, 3] and not codec._payload_rows.any()
+    assert e.value.keyed and e.value.stream and e.value.slices == [0, 1, 2, 3] and not e.value.rows.any()
     other = dataclasses.replace(vol, tag=vol.tag.clone())
     other.tag[0, 2] ^= 1 << 30                                                 # one bit of the stream's tag
     with pytest.raises(IntegrityError) as e:
         codec.decode_volume(other, key=KEY)
-    assert e.value.keyed and e.value.stream and e.value.slices == [] and not codec._payload_rows.any()
+    assert e.value.keyed and e.value.stream and e.value.slices == [] and not e.value.rows.any()
     enc = copy.copy(vol.enc)
     enc.stego = vol.enc.stego.clone()
     enc.stego.view(torch.int16)[2, 40, 40] ^= 1                                # one pixel of slice 2 (a context pixel)
