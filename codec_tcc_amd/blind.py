@@ -1,0 +1,314 @@
+"""Blind MED-PEE (include/codec_tcc_blind.h): the stego alone carries its location map
+and record, so that it decodes with nothing beside it.
+
+    stego, info = codec.embed_blind(covers, payloads, checksum=True)
+    bits, cover = codec.decode_blind(stego)              # T and maxval come from each header
+
+Scheme 1, fixed T, out of place, per slice.  A slice carries n_side = 192 + 32 E side bits in the
+LSBs of its last pixels (side bit i = bit 0 of the pixel with flat index H W - 1 - i): six header
+words, then the E location-map entries.  Those pixels lie in a region the ROI embed
+(include/codec_tcc_roi.h) neither modifies nor reads as context, and the LSBs they displace lead
+the PEE payload.  The plan -- which rows the payload needs, hence E and the region -- is computed
+on the device from the cover alone (tests/pee_blind_spec.py is the specification).
+
+parse_header, check_args and the geometry helpers are pure host code: no GPU, no library load.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Tuple
+
+import numpy as np
+
+from . import _lib
+
+MAGIC = _lib.BLIND_MAGIC
+HDR_WORDS = _lib.BLIND_HDR_WORDS
+HDR_BITS = 32 * HDR_WORDS
+NO_ENTRY = 0xFFFFFFFF
+FLAG_CRC = _lib.BLIND_FLAG_CRC
+MAX_ENTRIES = _lib.BLIND_MAX_ENTRIES
+MAX_DIM = _lib.ROI_MAX_DIM
+INFO_FIELDS = ("status", "n_user", "E", "n_side", "end", "region_row")
+STATUS_TEXT = {1: "the payload and its side bits exceed the slice's capacity",
+               2: "more location-map entries than max_entries"}
+
+
+def side_bits(E: int) -> int:
+    return HDR_BITS + 32 * int(E)
+
+
+def region(H: int, W: int, n_side: int) -> Tuple[int, Tuple[int, int, int, int]]:
+    """(r, rectangle): the candidate rows and the pixel rectangle reserved for n_side side bits."""
+    r = -(-int(n_side) // (2 * int(W)))
+    return r, (2 * (int(H) // 2 - r), 0, int(H), int(W))
+
+
+def row_words(n_user: int, max_entries: int) -> int:
+    """uint64 words of the PEE payload row: CODEC_PEE_BLIND_ROW_WORDS."""
+    return (int(n_user) + HDR_BITS + 32 * int(max_entries) + 63) // 64
+
+
+def check_args(*, scheme: int, T, gate, H: int, W: int, maxval: int, max_entries: int = 256, roi=None, key=None,
+               in_place: bool = False) -> None:
+    """The argument rules of the blind calls, as ValueError before anything is queued, in this
+    order: scheme, T, gate, roi / key, the shape, maxval, max_entries, in place."""
+    if int(scheme) != 1:
+        raise ValueError("blind MED-PEE is scheme 1's: scheme 2's later passes modify the pixels that hold the side bits "
+                         "(DESIGN §3k)")
+    if isinstance(T, str):
+        raise ValueError("blind MED-PEE takes a fixed T: the plan needs one row table per T (DESIGN §3k)")
+    if not 1 <= int(T) <= 64:
+        raise ValueError(f"blind MED-PEE takes T in 1..64, got {T}")
+    if gate is not None:
+        raise ValueError("blind MED-PEE takes no smoothness gate: the plan counts every candidate (DESIGN §3k)")
+    if roi is not None:
+        raise ValueError("blind MED-PEE takes no roi=: the reserved region is the slice's one rectangle (DESIGN §3k)")
+    if key is not None:
+        raise ValueError("blind MED-PEE takes no key=: the header has no room for the tag (DESIGN §3k)")
+    if int(H) > MAX_DIM or int(W) > MAX_DIM:
+        raise ValueError(f"blind MED-PEE takes H, W <= {MAX_DIM} (the ROI record words), got {int(H)} x {int(W)}")
+    if int(H) * int(W) < HDR_BITS:
+        raise ValueError(f"a {int(H)} x {int(W)} slice cannot hold the {HDR_BITS} header bits")
+    if not 1 <= int(maxval) <= 65535:
+        raise ValueError(f"the header holds maxval in 1..65535, got {maxval}")
+    if isinstance(max_entries, bool) or int(max_entries) != max_entries or not 0 <= int(max_entries) <= MAX_ENTRIES:
+        raise ValueError(f"max_entries must be an integer in 0..{MAX_ENTRIES}, got {max_entries!r}")
+    if in_place:
+        raise ValueError("blind MED-PEE embeds out of place only: pass a stego buffer other than the covers")
+
+
+def parse_header(words, H: int, W: int, vmax: int) -> Dict:
+    """One slice's six header words -> {T, flags, maxval, n_user, E, end, crc, n_side, rect, L};
+    ValueError naming the field for anything that is no header of an H x W slice."""
+    w = [int(v) & 0xFFFFFFFF for v in list(words)[:HDR_WORDS]]
+    H, W = int(H), int(W)
+    hc, wc = H // 2, W // 2
+    nc = hc * wc
+    if w[0] != MAGIC:
+        raise ValueError(f"magic = {w[0]:#010x} (a blind MED-PEE header starts with {MAGIC:#010x})")
+    T, flags, maxval = w[1] & 0xFF, (w[1] >> 8) & 0xFF, w[1] >> 16
+    if not 1 <= T <= 64:
+        raise ValueError(f"T = {T} (1..64)")
+    if flags & ~FLAG_CRC:
+        raise ValueError(f"flags = {flags:#x} (bit 0 alone is defined)")
+    if not 1 <= maxval <= vmax:
+        raise ValueError(f"maxval = {maxval} (1..{vmax})")
+    n_user, E = w[2], w[3]
+    end = -1 if w[4] == NO_ENTRY else w[4]
+    if end >= nc:
+        raise ValueError(f"end = {end} (the slice has {nc} candidates)")
+    n_side = side_bits(E)
+    if E > nc or n_side > H * W:
+        raise ValueError(f"E = {E} (the slice cannot hold {n_side} side bits)")
+    r, rect = region(H, W, n_side)
+    if r > hc:
+        raise ValueError(f"n_side = {n_side} (more than the slice's {hc} candidate rows hold)")
+    if end >= (hc - r) * wc:
+        raise ValueError(f"end = {end} (inside the reserved region, which starts at candidate row {hc - r})")
+    L = n_side + n_user
+    if L > end + 1:
+        raise ValueError(f"n_user = {n_user} ({L} bits cannot lie in candidates 0..{end})")
+    return {"T": T, "flags": flags, "maxval": maxval, "n_user": n_user, "E": E, "end": end, "crc": w[5],
+            "n_side": n_side, "rect": rect, "L": L}
+
+
+def parse_headers(hdr: np.ndarray, H: int, W: int, nbytes: int) -> Dict[str, np.ndarray]:
+    """Every slice's header (hdr: uint32 [B, >= 6] as codec_pee_blind_headers gathers them) as int64
+    arrays [B] under parse_header's names ("rect": [B, 4]): parse_header's rules applied to all
+    slices at once.  ValueError naming the slices that carry no header, each with parse_header's
+    reason."""
+    H, W = int(H), int(W)
+    hc, wc = H // 2, W // 2
+    nc = hc * wc
+    vmax = 65535 if int(nbytes) == 2 else 255
+    w = np.asarray(hdr)[:, :HDR_WORDS].astype(np.int64) & 0xFFFFFFFF
+    T, flags, maxval = w[:, 1] & 0xFF, (w[:, 1] >> 8) & 0xFF, w[:, 1] >> 16
+    n_user, E = w[:, 2], w[:, 3]
+    end = np.where(w[:, 4] == NO_ENTRY, -1, w[:, 4])
+    n_side = HDR_BITS + 32 * E
+    r = -(-n_side // (2 * W))
+    L = n_side + n_user
+    ok = ((w[:, 0] == MAGIC) & (T >= 1) & (T <= 64) & ((flags & ~FLAG_CRC) == 0) & (maxval >= 1) & (maxval <= vmax)
+          & (end < nc) & (E <= nc) & (n_side <= H * W) & (r <= hc) & (end < (hc - r) * wc) & (L <= end + 1))
+    if not ok.all():
+        bad = []
+        for b in np.flatnonzero(~ok):
+            try:
+                parse_header(w[b], H, W, vmax)
+                bad.append((int(b), "inconsistent header"))   # (the two statements of the rules disagree)
+            except ValueError as e:
+                bad.append((int(b), str(e)))
+        raise ValueError(f"no valid blind MED-PEE header in slices {[b for b, _ in bad]}: "
+                         + "; ".join(f"slice {b}: {why}" for b, why in bad[:4]))
+    rect = np.stack([2 * (hc - r), np.zeros_like(r), np.full_like(r, H), np.full_like(r, W)], axis=1)
+    return {"T": T, "flags": flags, "maxval": maxval, "n_user": n_user, "E": E, "end": end, "crc": w[:, 5],
+            "n_side": n_side, "rect": rect, "L": L}
+
+
+def records_bytes(heads: Dict[str, np.ndarray], H: int, W: int) -> bytes:
+    """The codec_pee_meta records of checked headers, as pee_checks.make_record(..., status=0, roi=rect)
+    writes them (B records of 16 int32 words), built for all slices at once."""
+    B = heads["T"].shape[0]
+    nc = (int(H) // 2) * (int(W) // 2)
+    m = np.zeros((B, _lib.PEE_META_BYTES // 4), dtype=np.int64)
+    end, rect = heads["end"], heads["rect"]
+    m[:, 0], m[:, 1], m[:, 2], m[:, 3] = heads["T"], heads["maxval"], heads["L"], end
+    m[:, 4], m[:, 5] = nc, (nc + 1023) // 1024
+    m[:, 6] = np.where(end >= 0, end // 1024, -1)
+    m[:, 8], m[:, 10], m[:, 11] = heads["L"], int(H), int(W)
+    m[:, 13] = (rect[:, 0] << 16) | rect[:, 1]
+    m[:, 14] = _lib.GATE_MAX + 1
+    m[:, 15] = (rect[:, 2] << 16) | rect[:, 3]
+    return (m & 0xFFFFFFFF).astype("<u4").tobytes()
+
+
+def raise_status(status, what: str = "embed_blind") -> None:
+    """ValueError naming the slices an embed refused (info's status column, on the host)."""
+    bad: Dict[int, List[int]] = {}
+    for b, s in enumerate(status):
+        if int(s) != 0:
+            bad.setdefault(int(s), []).append(b)
+    if bad:
+        raise ValueError(f"{what}: " + "; ".join(f"{STATUS_TEXT.get(s, 'status %d' % s)} in slices {v}"
+                                                 for s, v in sorted(bad.items())))
+
+
+# ---------------------------------------------------------------- the device side (PeeCodec's methods call these)
+def _workspace(codec, pw: int, max_entries: int):
+    """The blind workspace for rows of pw words: a codec_pee workspace with the plan's arrays, a
+    map and the rows behind it, zeroed once (codec_pee_reset) and kept (the last few)."""
+    from collections import OrderedDict
+    from .codec import _stream, _torch
+    cache = codec.__dict__.setdefault("_ws_blind", OrderedDict())
+    key = (int(pw), int(max_entries))
+    if key not in cache:
+        P = codec._params(pw)
+        n = int(_lib.load().codec_pee_blind_workspace_bytes(C.byref(P), int(max_entries)))
+        if n == 0:
+            _lib.check(-1, "codec_pee_blind_workspace_bytes")
+        ws = _torch().empty(n, dtype=_torch().uint8, device=codec.device)
+        _lib.check(_lib.load().codec_pee_reset(C.byref(P), ws.data_ptr(), ws.numel(), _stream()), "codec_pee_reset")
+        cache[key] = ws
+        while len(cache) > 4:
+            cache.popitem(last=False)
+    cache.move_to_end(key)
+    return cache[key]
+
+
+def _guarded(codec, ws, pw: int, fn):
+    """Run one call on a blind workspace; on any exception re-zero that workspace, then re-raise."""
+    from .codec import _stream
+    try:
+        return fn()
+    except BaseException:
+        try:
+            _lib.load().codec_pee_reset(C.byref(codec._params(pw)), ws.data_ptr(), ws.numel(), _stream())
+        except Exception:   # the original error is the one to report
+            pass
+        raise
+
+
+def _codec_args(codec, max_entries: int = 256, in_place: bool = False):
+    check_args(scheme=codec.scheme, T="auto" if codec.auto else codec.T, gate=codec.gate, H=codec.H, W=codec.W,
+               maxval=codec.maxval, max_entries=max_entries, in_place=in_place)
+
+
+def embed(codec, covers, payloads, *, stego=None, packed=None, checksum=False, max_entries: int = 256,
+          check: bool = True):
+    from . import checksum as _ck
+    from .codec import _stream, _torch
+    from .pee_checks import check_buffers
+    torch = _torch()
+    if checksum not in (False, True):
+        raise ValueError("embed_blind takes checksum=True or False (the header holds the cover's CRC-32 alone)")
+    _codec_args(codec, max_entries)
+    check_buffers(codec.device, codec.B, codec.H, codec.W, codec.bytes, lm_words=codec.lm_words, scheme=1,
+                  covers=covers, stego=stego, packed=packed)
+    _codec_args(codec, max_entries, in_place=stego is not None and stego.data_ptr() == covers.data_ptr())
+    words, lengths, lens_t = packed if packed is not None else codec.pack_payloads(payloads)
+    n_max = max([int(n) for n in lengths] + [0])
+    if n_max > 64 * int(words.shape[1]):
+        raise ValueError(f"a payload of {n_max} bits does not fit the packed rows' {64 * int(words.shape[1])}")
+    pw = row_words(n_max, max_entries)
+    crc = _ck.crc32_slices(covers) if checksum else None   # queued first, as embed(checksum=True) does
+    if stego is None:
+        stego = torch.empty_like(covers)
+    ws = _workspace(codec, pw, max_entries)
+    info = torch.empty((codec.B, _lib.BLIND_INFO_WORDS), dtype=torch.int32, device=codec.device)
+    lm = torch.empty((codec.B, codec.lm_words), dtype=torch.int64, device=codec.device)
+    meta = torch.empty((codec.B, _lib.PEE_META_BYTES), dtype=torch.uint8, device=codec.device)
+    P = codec._params(pw)
+    _guarded(codec, ws, pw, lambda: _lib.check(_lib.load().codec_pee_blind_embed(
+        C.byref(P), covers.data_ptr(), stego.data_ptr(), words.data_ptr(), int(words.shape[1]), lens_t.data_ptr(),
+        None if crc is None else crc.data_ptr(), int(max_entries), info.data_ptr(), meta.data_ptr(), lm.data_ptr(),
+        ws.data_ptr(), ws.numel(), _stream()), "codec_pee_blind_embed"))
+    out = info[:, :len(INFO_FIELDS)]
+    if check:
+        raise_status(out[:, 0].cpu().tolist())   # one read-back
+    return stego, out
+
+
+def capacity(codec, covers, max_entries: int = 256):
+    from .codec import _stream, _torch
+    torch = _torch()
+    _codec_args(codec, max_entries)
+    codec._check_buffers(covers=covers)
+    pw = row_words(0, max_entries)
+    ws = _workspace(codec, pw, max_entries)
+    info = torch.empty((codec.B, _lib.BLIND_INFO_WORDS), dtype=torch.int32, device=codec.device)
+    _guarded(codec, ws, pw, lambda: _lib.check(_lib.load().codec_pee_blind_plan(
+        C.byref(codec._params(pw)), covers.data_ptr(), None, int(max_entries), info.data_ptr(), ws.data_ptr(), ws.numel(),
+        _stream()), "codec_pee_blind_plan"))
+    return info[:, _lib.BLIND_INFO_WORDS - 1].contiguous()
+
+
+def decode(codec, stego, *, cover=None, verify=True):
+    from . import checksum as _ck, framing, pee_verify as _pv
+    from .codec import _stream, _torch
+    from .pee_checks import check_buffers, check_records
+    torch = _torch()
+    mode = _ck.verify_mode(verify)
+    if codec.scheme != 1:
+        raise ValueError("blind MED-PEE is scheme 1's")
+    if codec.H > MAX_DIM or codec.W > MAX_DIM or codec.H * codec.W < HDR_BITS:
+        raise ValueError(f"a {codec.H} x {codec.W} slice carries no blind MED-PEE header")
+    check_buffers(codec.device, codec.B, codec.H, codec.W, codec.bytes, lm_words=codec.lm_words, scheme=1,
+                  stego=stego, cover=cover)
+    if cover is not None and cover.data_ptr() == stego.data_ptr():
+        raise ValueError("blind MED-PEE decodes out of place only: pass a cover buffer other than the stego")
+    lib = _lib.load()
+    hdr = torch.empty((codec.B, 8), dtype=torch.int32, device=codec.device)
+    _lib.check(lib.codec_pee_blind_headers(C.byref(codec._params(1)), stego.data_ptr(), hdr.data_ptr(), _stream()),
+               "codec_pee_blind_headers")
+    heads = parse_headers(hdr.cpu().numpy().view(np.uint32), codec.H, codec.W, codec.bytes)   # the one read-back before the extract
+    pw = max(HDR_BITS // 64, int((heads["L"].max() + 63) // 64))
+    uw = max(1, int((heads["n_user"].max() + 63) // 64))
+    raw = records_bytes(heads, codec.H, codec.W)
+    check_records([_lib.PeeMeta.from_buffer_copy(raw, b * _lib.PEE_META_BYTES) for b in range(codec.B)], codec.H, codec.W,
+                  scheme=1, payload_words=pw, lm_words=codec.lm_words, bytes=codec.bytes)
+    has_crc = (heads["flags"] & FLAG_CRC) != 0
+    if mode == "require" and not has_crc.all():
+        raise _ck.IntegrityError("blind MED-PEE decode: verify='require' and slices "
+                                 f"{np.flatnonzero(~has_crc).tolist()} carry no cover checksum")
+    meta = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy().reshape(codec.B, _lib.PEE_META_BYTES)).to(codec.device)
+    if cover is None:
+        cover = torch.empty_like(stego)
+    words = torch.empty((codec.B, uw), dtype=torch.int64, device=codec.device)
+    ws = _workspace(codec, pw, 0)
+    _guarded(codec, ws, pw, lambda: _lib.check(lib.codec_pee_blind_extract(
+        C.byref(codec._params(pw)), stego.data_ptr(), hdr.data_ptr(), meta.data_ptr(), cover.data_ptr(), words.data_ptr(),
+        uw, ws.data_ptr(), ws.numel(), _stream()), "codec_pee_blind_extract"))
+    flagged = np.flatnonzero(has_crc).tolist()
+    got = _ck.crc32_slices(cover) if mode is not None and flagged else None
+    host = words.cpu().numpy()
+    # small batches take the flat look-back route out of place too: its flag, as decode() reads it
+    off = int(lib.codec_pee_extract_flag_offset(C.byref(codec._params(pw))))
+    if off and int(ws[off:off + 4].view(torch.int32).item()) != 0:
+        _lib.check(lib.codec_pee_reset(C.byref(codec._params(pw)), ws.data_ptr(), ws.numel(), _stream()), "codec_pee_reset")
+        raise RuntimeError(_pv.LOOKBACK_TIMEOUT)
+    if got is not None:
+        bad = set(_pv.cover_mismatches(got, heads["crc"].tolist(), codec.B))
+        _ck.raise_mismatch([b for b in flagged if b in bad], [], "blind MED-PEE decode", rows=host)
+    n_user = heads["n_user"].tolist()
+    return [framing.unpack_bits(host[b], n_user[b]) for b in range(codec.B)], cover

@@ -27,7 +27,7 @@ SRCS = [os.path.join(HERE, "csrc", "codec_hip.hip"), os.path.join(HERE, "csrc", 
         os.path.join(HERE, "csrc", "codec_crc.hip"), os.path.join(HERE, "csrc", "codec_vol.hip"),
         os.path.join(HERE, "csrc", "codec_gate.hip"), os.path.join(HERE, "csrc", "codec_gvol.hip"),
         os.path.join(HERE, "csrc", "codec_tile.hip"), os.path.join(HERE, "csrc", "codec_roi.hip"),
-        os.path.join(HERE, "csrc", "codec_aead.hip")]
+        os.path.join(HERE, "csrc", "codec_aead.hip"), os.path.join(HERE, "csrc", "codec_blind.hip")]
 HDRS = [os.path.join(HERE, "csrc", "codec_common.h"), os.path.join(HERE, "csrc", "codec_crc_gf2.h")]
 OUT = os.path.join(HERE, "libcodec_hip.so")
 INC = os.path.join(REPO, "include")
@@ -58,7 +58,7 @@ def _common_deps():
                    os.path.join(INC, "codec_tcc_crc.h"), os.path.join(INC, "codec_tcc_vol.h"),
                    os.path.join(INC, "codec_tcc_gate.h"), os.path.join(INC, "codec_tcc_gvol.h"),
                    os.path.join(INC, "codec_tcc_tile.h"), os.path.join(INC, "codec_tcc_roi.h"),
-                   os.path.join(INC, "codec_tcc_aead.h")]
+                   os.path.join(INC, "codec_tcc_aead.h"), os.path.join(INC, "codec_tcc_blind.h")]
 
 
 def _digest(paths, flags) -> str:

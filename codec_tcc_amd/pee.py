@@ -39,7 +39,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _lib, aead as _aead, checksum as _ck, framing, pee_verify as _pv, roi as _roi
+from . import _lib, aead as _aead, blind as _blind, checksum as _ck, framing, pee_verify as _pv, roi as _roi
 from .codec import _elem_bytes, _require_gpu, _stream, _torch
 from .pee_checks import (VOLUME_NMAX, _bad_device, _bad_overlap, _bad_pixels, _bad_side,  # noqa: F401 (re-exported)
                          _check_multi_args, _dense, _on_device, _pix_dtypes, check_buffers, check_gate_args,
@@ -639,6 +639,38 @@ class PeeCodec:
         host, _total = _pv.after_extract(self, enc, cover, words, mode, key, lookback=self.scheme == 1)
         return [framing.unpack_bits(host[i], enc.lengths[i]) for i in range(self.B)], cover
 
+    # ---- blind MED-PEE: the stego alone carries its map and record (include/codec_tcc_blind.h, blind.py)
+    def embed_blind(self, covers, payloads, *, stego=None, packed=None, checksum=False, max_entries: int = 256,
+                    check: bool = True):
+        """(stego, info): every slice's stego carries its own header and location map in the LSBs
+        of its last rows, so decode_blind(stego) needs nothing else.  info: int32
+        [B, 6] on the device, per slice (status, n_user, E, n_side, end, region row); status 1: the
+        payload and its 192 + 32 E side bits do not fit, 2: E > max_entries -- such a slice is
+        copied through unchanged and carries no header.  Scheme 1 with a fixed T and no gate, out
+        of place; row table, plan, splice, ROI embed and pack are queued on the current stream
+        with no host round trip (capturable with packed= and check=False).
+        checksum=True: crc32_slices(covers), queued first, goes into the header and decode_blind
+        verifies it.  max_entries: the most location-map entries a slice may need (it sizes the
+        payload rows).  check=True reads the statuses back (one sync) and raises ValueError naming
+        the refused slices; check=False leaves them in info."""
+        return _blind.embed(self, covers, payloads, stego=stego, packed=packed, checksum=checksum,
+                            max_entries=max_entries, check=check)
+
+    def decode_blind(self, stego, *, cover=None, verify=True):
+        """(bits per slice, cover) of embed_blind's stegos, from the pixels alone: T, maxval, the
+        lengths, the region and the map come from each slice's header, whatever this codec was
+        built with (its shape and dtype are the stego's).  The headers are gathered and read back
+        once; anything that is no header of such a slice is a ValueError naming the slices, before
+        the extract is launched, and the rebuilt records pass check_records.  verify (True, False,
+        'require'): a slice whose header carries the cover's CRC-32 and whose restored cover has
+        another raises IntegrityError (.bad_cover), as decode(verify=True) does."""
+        return _blind.decode(self, stego, cover=cover, verify=verify)
+
+    def blind_capacity(self, covers, max_entries: int = 256):
+        """int32 [B] device tensor: the most user bits embed_blind takes per slice at this codec's T
+        (the plan rule of DESIGN §3k), -1 where not even the header fits."""
+        return _blind.capacity(self, covers, max_entries)
+
     # ---- volume payloads: one bitstream across the stack (include/codec_tcc_vol.h)
     def _cached_workspace(self, fn: str, payload_words: int, tmax: int):
         """A workspace sized by the library's `fn` for this row pitch; the last few are kept, so a
@@ -990,6 +1022,39 @@ def decode(enc: PeeEncoded, verify=True, *, restore: bool = True, key=None):
                        tmax=cfg.get("tmax", 16), maxval=cfg.get("maxval"), scheme=int(getattr(enc, "scheme", 1)),
                        tmin=cfg.get("tmin", 1))
     bits, cover = codec.decode(enc, verify, key=key)
+    return bits, (cover if restore else None)
+
+
+def encode_blind(covers, payloads: Sequence, *, T: int = 2, maxval: Optional[int] = None, checksum=False,
+                 max_entries: int = 256, scheme: int = 1, gate=None, roi=None, key=None):
+    """Blind MED-PEE embed of one payload per slice (PeeCodec.embed_blind): (stego, info), where the
+    stego decodes with nothing beside it (decode_blind).  covers: [B,H,W] / [H,W] uint8 / uint16
+    torch tensor or numpy array.  Raises ValueError naming the slices whose payload (with its side
+    bits) does not fit; scheme=2, T="auto", gate=, roi= and key= are ValueError before the GPU is
+    touched."""
+    shape = tuple(covers.shape)
+    if len(shape) < 2:
+        raise ValueError(f"covers must be [B, H, W] or [H, W], got shape {shape}")
+    mv = maxval if maxval is not None else (255 if "8" in str(covers.dtype) and "16" not in str(covers.dtype) else 65535)
+    _blind.check_args(scheme=scheme, T=T, gate=gate, H=int(shape[-2]), W=int(shape[-1]), maxval=mv,
+                      max_entries=max_entries, roi=roi, key=key)
+    _require_gpu()
+    covers = _as_gpu_batch(covers)
+    if isinstance(payloads, (str, bytes, bytearray)):
+        payloads = [payloads]
+    dt = "uint16" if _elem_bytes(covers) == 2 else "uint8"
+    codec = _codec_for(tuple(covers.shape), dt, T=int(T), tmax=16, maxval=maxval)
+    return codec.embed_blind(covers, payloads, checksum=checksum, max_entries=max_entries)
+
+
+def decode_blind(stego, verify=True, *, restore: bool = True):
+    """(payload_bit_lists, cover) of a blind stego ([B,H,W] / [H,W] tensor or numpy array), from
+    its pixels alone (PeeCodec.decode_blind); cover is None with restore=False."""
+    _require_gpu()
+    stego = _as_gpu_batch(stego)
+    dt = "uint16" if _elem_bytes(stego) == 2 else "uint8"
+    codec = _codec_for(tuple(stego.shape), dt, T=2, tmax=16, maxval=None)
+    bits, cover = codec.decode_blind(stego, verify=verify)
     return bits, (cover if restore else None)
 
 

@@ -248,6 +248,53 @@ def encode_file_pee(image, payload, out_path: str, *, T=2, tmax: int = 16, maxva
             "status": r.status, "lm_count": r.lm_count, "stego": stego, **gated, **crcs}
 
 
+def encode_dicom_pee(image_or_path, payload, out_path: str, T: int = 2, checksum: bool = True,
+                     maxval: Optional[int] = None, max_entries: int = 256) -> Dict:
+    """Blind MED-PEE (PeeCodec.embed_blind) of `payload` (str / bytes / 0-1 vector, as
+    encode_file_pee takes it) into a plain DICOM: the file's pixel data is the stego
+    (dicom.save_dicom), which carries its own header and location map, so decode_dicom_pee needs
+    the file alone and any DICOM store keeps it like every other image.  maxval: the DICOM's
+    BitsStored when the image is one, else the dtype's maximum.  checksum=True: the header holds
+    the cover's CRC-32.  ValueError when the payload and its side bits do not fit."""
+    from .pee import PeeCodec
+    _require_gpu()
+    torch = _torch()
+    if isinstance(image_or_path, np.ndarray):
+        img = image_or_path
+    else:
+        img, attrs = dicom.read_dicom(image_or_path)
+        if maxval is None and attrs.get("bits_stored"):
+            maxval = (1 << int(attrs["bits_stored"])) - 1
+    if img.ndim != 2 or img.dtype not in (np.uint8, np.uint16):
+        raise ValueError("A imagem deve ser 2D uint8 ou uint16.")
+    h, w = img.shape
+    bits = framing.to_bits(payload)
+    pc = PeeCodec(1, h, w, dtype=str(img.dtype), T=T, maxval=maxval)
+    stego, info = pc.embed_blind(torch.from_numpy(np.ascontiguousarray(img)[None]).cuda(), [bits], checksum=bool(checksum),
+                                 max_entries=max_entries)
+    out = stego.cpu().numpy()[0]
+    size = dicom.save_dicom(out, out_path)
+    row = [int(v) for v in info.cpu().tolist()[0]]
+    return {"path": out_path, "bytes": size, "T": int(T), "maxval": pc.maxval, "stego": out,
+            **dict(zip(("status", "L", "E", "n_side", "end", "region_row"), row))}
+
+
+def decode_dicom_pee(path, verify=True) -> Tuple[np.ndarray, np.ndarray]:
+    """(payload bits as a 0/1 uint8 vector, restored cover) from a DICOM written by
+    encode_dicom_pee (a path or the file's bytes): PeeCodec.decode_blind on its pixels.  ValueError
+    for an image that carries no blind MED-PEE header, IntegrityError when the restored cover
+    fails the CRC-32 its header carries (verify as decode_blind's)."""
+    from .pee import PeeCodec
+    img, _attrs = dicom.read_dicom(path)
+    if img.ndim != 2 or img.dtype not in (np.uint8, np.uint16):
+        raise ValueError("A imagem deve ser 2D uint8 ou uint16.")
+    _require_gpu()
+    h, w = img.shape
+    pc = PeeCodec(1, h, w, dtype=str(img.dtype), T=1)
+    bits, cover = pc.decode_blind(_torch().from_numpy(np.ascontiguousarray(img)[None]).cuda(), verify=verify)
+    return bits[0], cover.cpu().numpy()[0]
+
+
 @dataclass
 class PeeFile:
     """The host half of a MED-PEE file decode (read_pee_bytes): everything the launch needs."""

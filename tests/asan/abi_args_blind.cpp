@@ -1,0 +1,227 @@
+// Host sanitizer check of the argument validation of include/codec_tcc_blind.h's entries, as
+// abi_args_roi.cpp is for codec_tcc_roi.h: linked against the host-only
+// -fsanitize=address,undefined build of the library and tests/asan/hip_stubs.cpp
+// (tests/test_asan_abi_blind.py builds and runs it).  Every bad call must return its negative
+// status (0 for the size function) with an error text and no device operation; every call with
+// good arguments must get past the checks, i.e. reach its first device operation (which the
+// stubs refuse and count).
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include "codec_tcc_blind.h"
+
+static int g_fail = 0, g_n = 0;
+extern "C" int hip_stub_device_ops(void);   // tests/asan/hip_stubs.cpp
+
+#define EXPECT_NEG(expr)                                                                           \
+    do {                                                                                           \
+        ++g_n;                                                                                     \
+        const long long r_ = (long long)(expr);                                                    \
+        if (r_ >= 0) {                                                                             \
+            fprintf(stderr, "FAIL line %d: %s returned %lld (want < 0)\n", __LINE__, #expr, r_);   \
+            ++g_fail;                                                                              \
+        } else if (!codec_last_error() || !codec_last_error()[0]) {                                \
+            fprintf(stderr, "FAIL line %d: %s gave no error message\n", __LINE__, #expr);          \
+            ++g_fail;                                                                              \
+        }                                                                                          \
+    } while (0)
+
+#define EXPECT_EQ(expr, want)                                                                      \
+    do {                                                                                           \
+        ++g_n;                                                                                     \
+        const unsigned long long r_ = (unsigned long long)(expr), w_ = (unsigned long long)(want); \
+        if (r_ != w_) {                                                                            \
+            fprintf(stderr, "FAIL line %d: %s = %llu (want %llu)\n", __LINE__, #expr, r_, w_);     \
+            ++g_fail;                                                                              \
+        }                                                                                          \
+    } while (0)
+
+#define ME 8   // max_entries of the good calls: rows of (192 + 32 * 8 + 64 * 4 + 63) / 64 = 11 words
+
+static codec_pee_params good() {
+    codec_pee_params P;
+    memset(&P, 0, sizeof(P));
+    P.B = 5; P.H = 64; P.W = 96; P.bytes = 2; P.T = 2; P.maxval = 4095;
+    P.payload_words = (int32_t)CODEC_PEE_BLIND_ROW_WORDS(256, ME); P.lm_words = 24;   // (64 / 2) * (96 / 2) = 1536 candidates
+    return P;
+}
+
+// the parameter sets every entry must refuse
+static int bad_params(codec_pee_params* out) {
+    int k = 0;
+    codec_pee_params P;
+    P = good(); P.B = 0; out[k++] = P;
+    P = good(); P.B = -3; out[k++] = P;
+    P = good(); P.B = INT32_MIN; out[k++] = P;
+    P = good(); P.H = 0; out[k++] = P;
+    P = good(); P.W = -1; out[k++] = P;
+    P = good(); P.H = 65536; P.W = 65536; P.lm_words = 1 << 24; out[k++] = P;      // H * W past 2^31
+    P = good(); P.bytes = 0; out[k++] = P;
+    P = good(); P.bytes = 4; out[k++] = P;
+    P = good(); P.T = 0; out[k++] = P;
+    P = good(); P.T = 65; out[k++] = P;                                            // the blind entries' own bound
+    P = good(); P.maxval = 0; out[k++] = P;
+    P = good(); P.maxval = 65536; out[k++] = P;
+    P = good(); P.bytes = 1; P.maxval = 256; out[k++] = P;
+    P = good(); P.payload_words = 0; out[k++] = P;
+    P = good(); P.payload_words = -1; out[k++] = P;
+    P = good(); P.lm_words = 0; out[k++] = P;
+    P = good(); P.lm_words = 23; out[k++] = P;                                     // 1472 < 1536 candidates
+    P = good(); P.H = 8; P.W = 16; P.lm_words = 1; out[k++] = P;                   // 128 pixels: no room for 192 header bits
+    return k;
+}
+
+int main() {
+    alignas(64) static unsigned char buf[1 << 16];
+    void* p = buf;
+    void* q = buf + 32768;
+    int32_t* i32 = reinterpret_cast<int32_t*>(buf);
+    uint32_t* u32 = reinterpret_cast<uint32_t*>(buf);
+    uint64_t* u64p = reinterpret_cast<uint64_t*>(buf);
+    codec_pee_meta* meta = reinterpret_cast<codec_pee_meta*>(buf);
+    const size_t big = (size_t)1 << 40;
+
+    if (codec_abi_version() != 1) { fprintf(stderr, "FAIL abi version\n"); return 2; }
+
+    codec_pee_params G = good();
+    const size_t pws = codec_pee_workspace_bytes(&G);
+    const size_t bws = codec_pee_blind_workspace_bytes(&G, ME);
+    if (!pws || bws <= pws) {
+        fprintf(stderr, "FAIL workspace sizes of good arguments: %zu / %zu\n", pws, bws);
+        ++g_fail;
+    }
+    EXPECT_EQ(CODEC_PEE_BLIND_ROW_WORDS(0, 0), 3);
+    EXPECT_EQ(CODEC_PEE_BLIND_ROW_WORDS(1, 0), 4);
+    EXPECT_EQ(CODEC_PEE_BLIND_ROW_WORDS(1000, 256), (1000 + 192 + 8192 + 63) / 64);
+
+#define WSB(P, me) codec_pee_blind_workspace_bytes(P, me)
+#define PLAN(P, cover, len, me, info, ws, wsb) codec_pee_blind_plan(P, cover, len, me, info, ws, wsb, nullptr)
+#define EMB(P, cover, stego, pay, uw, len, crc, me, info, m, lm, ws, wsb) \
+    codec_pee_blind_embed(P, cover, stego, pay, uw, len, crc, me, info, m, lm, ws, wsb, nullptr)
+#define HDR(P, stego, out) codec_pee_blind_headers(P, stego, out, nullptr)
+#define EXT(P, stego, hdr, m, cover, pay, uw, ws, wsb) codec_pee_blind_extract(P, stego, hdr, m, cover, pay, uw, ws, wsb, nullptr)
+
+    // ---- bad parameter sets: every entry
+    codec_pee_params bad[32];
+    const int nbad = bad_params(bad);
+    for (int k = 0; k < nbad; ++k) {
+        const codec_pee_params* B = &bad[k];
+        EXPECT_EQ(WSB(B, ME), 0);
+        EXPECT_NEG(PLAN(B, p, i32, ME, i32, p, big));
+        EXPECT_NEG(PLAN(B, p, nullptr, ME, i32, p, big));
+        EXPECT_NEG(EMB(B, p, q, u64p, 4, i32, u32, ME, i32, meta, u64p, p, big));
+        EXPECT_NEG(EMB(B, p, q, u64p, 4, i32, nullptr, ME, i32, meta, u64p, p, big));
+        EXPECT_NEG(HDR(B, p, u32));
+        EXPECT_NEG(EXT(B, p, u32, meta, q, u64p, 4, p, big));
+    }
+    EXPECT_EQ(WSB(nullptr, ME), 0);
+    EXPECT_NEG(PLAN(nullptr, p, i32, ME, i32, p, big));
+    EXPECT_NEG(EMB(nullptr, p, q, u64p, 4, i32, u32, ME, i32, meta, u64p, p, big));
+    EXPECT_NEG(HDR(nullptr, p, u32));
+    EXPECT_NEG(EXT(nullptr, p, u32, meta, q, u64p, 4, p, big));
+    // H or W above 65535: the reserved rectangle travels in the ROI record words
+    for (int k = 0; k < 2; ++k) {
+        codec_pee_params P = good();
+        P.B = 1;
+        if (k == 0) { P.H = 65536; P.W = 8; } else { P.H = 8; P.W = 65536; }
+        P.lm_words = (4 * 32768 + 63) / 64;
+        if (!codec_pee_workspace_bytes(&P)) { fprintf(stderr, "FAIL: the tall / wide shape is not a codec_pee one\n"); ++g_fail; }
+        EXPECT_EQ(WSB(&P, ME), 0);
+        EXPECT_NEG(PLAN(&P, p, i32, ME, i32, p, big));
+        EXPECT_NEG(EMB(&P, p, q, u64p, 4, i32, u32, ME, i32, meta, u64p, p, big));
+        EXPECT_NEG(HDR(&P, p, u32));
+        EXPECT_NEG(EXT(&P, p, u32, meta, q, u64p, 4, p, big));
+    }
+    // max_entries out of range, and rows narrower than its side bits
+    for (int32_t me : {-1, INT32_MIN, CODEC_PEE_BLIND_MAX_ENTRIES + 1, INT32_MAX}) {
+        EXPECT_EQ(WSB(&G, me), 0);
+        EXPECT_NEG(PLAN(&G, p, i32, me, i32, p, big));
+        EXPECT_NEG(EMB(&G, p, q, u64p, 4, i32, u32, me, i32, meta, u64p, p, big));
+    }
+    {
+        codec_pee_params P = good();
+        P.payload_words = (int32_t)CODEC_PEE_BLIND_ROW_WORDS(0, ME) - 1;
+        EXPECT_EQ(WSB(&P, ME), 0);
+        EXPECT_NEG(PLAN(&P, p, i32, ME, i32, p, big));
+        EXPECT_NEG(EMB(&P, p, q, u64p, 4, i32, u32, ME, i32, meta, u64p, p, big));
+        P.payload_words = 2;   // below the 192 header bits
+        EXPECT_NEG(EXT(&P, p, u32, meta, q, u64p, 4, p, big));
+    }
+
+    // ---- codec_pee_blind_plan
+    EXPECT_NEG(PLAN(&G, nullptr, i32, ME, i32, p, bws));
+    EXPECT_NEG(PLAN(&G, p, i32, ME, nullptr, p, bws));
+    EXPECT_NEG(PLAN(&G, p, i32, ME, i32, nullptr, bws));
+    EXPECT_NEG(PLAN(&G, p, i32, ME, i32, p, bws - 1));
+    EXPECT_NEG(PLAN(&G, p, i32, ME, i32, p, pws));
+    EXPECT_NEG(PLAN(&G, p, nullptr, ME, i32, p, 0));
+
+    // ---- codec_pee_blind_embed
+    EXPECT_NEG(EMB(&G, nullptr, q, u64p, 4, i32, u32, ME, i32, meta, u64p, p, bws));
+    EXPECT_NEG(EMB(&G, p, nullptr, u64p, 4, i32, u32, ME, i32, meta, u64p, p, bws));
+    EXPECT_NEG(EMB(&G, p, q, nullptr, 4, i32, u32, ME, i32, meta, u64p, p, bws));
+    EXPECT_NEG(EMB(&G, p, q, u64p, 4, nullptr, u32, ME, i32, meta, u64p, p, bws));
+    EXPECT_NEG(EMB(&G, p, q, u64p, 4, i32, u32, ME, nullptr, meta, u64p, p, bws));
+    EXPECT_NEG(EMB(&G, p, q, u64p, 4, i32, u32, ME, i32, nullptr, u64p, p, bws));
+    EXPECT_NEG(EMB(&G, p, q, u64p, 4, i32, u32, ME, i32, meta, nullptr, p, bws));
+    EXPECT_NEG(EMB(&G, p, q, u64p, 4, i32, u32, ME, i32, meta, u64p, nullptr, bws));
+    EXPECT_NEG(EMB(&G, p, p, u64p, 4, i32, u32, ME, i32, meta, u64p, p, bws));            // in place
+    EXPECT_NEG(EMB(&G, p, q, u64p, 0, i32, u32, ME, i32, meta, u64p, p, bws));
+    EXPECT_NEG(EMB(&G, p, q, u64p, -1, i32, u32, ME, i32, meta, u64p, p, bws));
+    EXPECT_NEG(EMB(&G, p, q, u64p, INT32_MAX, i32, u32, ME, i32, meta, u64p, p, bws));
+    EXPECT_NEG(EMB(&G, p, q, u64p, 4, i32, u32, ME, i32, meta, u64p, p, bws - 1));
+    EXPECT_NEG(EMB(&G, p, q, u64p, 4, i32, nullptr, ME, i32, meta, u64p, p, pws));
+    EXPECT_NEG(EMB(&G, p, q, u64p, 4, i32, nullptr, ME, i32, meta, u64p, p, 0));
+
+    // ---- codec_pee_blind_headers
+    EXPECT_NEG(HDR(&G, nullptr, u32));
+    EXPECT_NEG(HDR(&G, p, nullptr));
+
+    // ---- codec_pee_blind_extract
+    const size_t xws = codec_pee_blind_workspace_bytes(&G, 0);
+    EXPECT_NEG(EXT(&G, nullptr, u32, meta, q, u64p, 4, p, xws));
+    EXPECT_NEG(EXT(&G, p, nullptr, meta, q, u64p, 4, p, xws));
+    EXPECT_NEG(EXT(&G, p, u32, nullptr, q, u64p, 4, p, xws));
+    EXPECT_NEG(EXT(&G, p, u32, meta, nullptr, u64p, 4, p, xws));
+    EXPECT_NEG(EXT(&G, p, u32, meta, q, nullptr, 4, p, xws));
+    EXPECT_NEG(EXT(&G, p, u32, meta, q, u64p, 4, nullptr, xws));
+    EXPECT_NEG(EXT(&G, p, u32, meta, p, u64p, 4, p, xws));                               // in place
+    EXPECT_NEG(EXT(&G, p, u32, meta, q, u64p, 0, p, xws));
+    EXPECT_NEG(EXT(&G, p, u32, meta, q, u64p, INT32_MIN, p, xws));
+    EXPECT_NEG(EXT(&G, p, u32, meta, q, u64p, 4, p, xws - 1));
+    EXPECT_NEG(EXT(&G, p, u32, meta, q, u64p, 4, p, 0));
+
+    if (hip_stub_device_ops() != 0) {
+        fprintf(stderr, "FAIL: %d device operations were attempted by argument-error calls\n", hip_stub_device_ops());
+        ++g_fail;
+    }
+
+    // ---- good arguments: each entry gets past its checks and reaches a device operation, which
+    // the stubs refuse and count.  The buffer stands in for device memory:
+    // nothing dereferences it on the host.
+    {
+        static unsigned char ws[1 << 22];
+        if (bws > sizeof(ws)) { fprintf(stderr, "FAIL: workspace of the good shape is %zu bytes\n", bws); return 2; }
+        int ops = hip_stub_device_ops();
+#define EXPECT_REACHED(expr)                                                                           \
+    do {                                                                                               \
+        ++g_n;                                                                                         \
+        (void)(expr);   /* whatever the refused launches make of it */                                 \
+        if (hip_stub_device_ops() <= ops) {                                                            \
+            fprintf(stderr, "FAIL line %d: %s stopped before any device operation: %s\n", __LINE__, #expr, codec_last_error()); \
+            ++g_fail;                                                                                  \
+        }                                                                                              \
+        ops = hip_stub_device_ops();                                                                   \
+    } while (0)
+        EXPECT_REACHED(HDR(&G, p, u32));
+        EXPECT_REACHED(HDR(&G, buf + 2, u32));                                           // an offset view
+        EXPECT_REACHED(PLAN(&G, p, i32, ME, i32, ws, bws));
+        EXPECT_REACHED(PLAN(&G, p, nullptr, 0, i32, ws, bws));
+        EXPECT_REACHED(EMB(&G, p, q, u64p, 4, i32, u32, ME, i32, meta, u64p, ws, bws));
+        EXPECT_REACHED(EMB(&G, buf + 2, q, u64p, 1, i32, nullptr, 0, i32, meta, u64p, ws, bws));
+        EXPECT_REACHED(EXT(&G, p, u32, meta, q, u64p, 4, ws, bws));
+    }
+    printf("abi_args_blind: %d calls, %d failures\n", g_n, g_fail);
+    return g_fail ? 1 : 0;
+}
