@@ -28,7 +28,8 @@ SRCS = [os.path.join(HERE, "csrc", "codec_hip.hip"), os.path.join(HERE, "csrc", 
         os.path.join(HERE, "csrc", "codec_gate.hip"), os.path.join(HERE, "csrc", "codec_gvol.hip"),
         os.path.join(HERE, "csrc", "codec_tile.hip"), os.path.join(HERE, "csrc", "codec_roi.hip"),
         os.path.join(HERE, "csrc", "codec_aead.hip"), os.path.join(HERE, "csrc", "codec_blind.hip")]
-HDRS = [os.path.join(HERE, "csrc", "codec_common.h"), os.path.join(HERE, "csrc", "codec_crc_gf2.h")]
+HDRS = [os.path.join(HERE, "csrc", "codec_common.h"), os.path.join(HERE, "csrc", "codec_crc_gf2.h"),
+        os.path.join(HERE, "csrc", "codec_vol_checks.h")]
 OUT = os.path.join(HERE, "libcodec_hip.so")
 INC = os.path.join(REPO, "include")
 ARCH = os.environ.get("CODEC_OFFLOAD_ARCH", "gfx950")

@@ -385,14 +385,14 @@ static int blind_plan(const codec_pee_params* P, const BlWs& L, const void* cove
     const int hc = P->H / 2;
     if (hc > 0) {
         ProfScope prof(st, CODEC_K_BLIND_ROWS);
-        const size_t va = P->bytes == 2 ? 16 : 8;
-        const bool vec = (P->W % 8) == 0 && ((uintptr_t)cover % va) == 0;
         dim3 grid((unsigned)((hc + BL_ROWS_PER_WG - 1) / BL_ROWS_PER_WG), (unsigned)P->B);
-#define BLR(TT, VV) hipLaunchKernelGGL((k_blind_rows<TT, VV>), grid, dim3(256), 0, st, static_cast<const TT*>(cover), P->H, \
-                                       P->W, P->maxval, P->T, rows)
-        if (P->bytes == 2) { if (vec) BLR(uint16_t, true); else BLR(uint16_t, false); }
-        else { if (vec) BLR(uint8_t, true); else BLR(uint8_t, false); }
-#undef BLR
+        pee_pixel(P->bytes, [&](auto px) {
+            using TT = decltype(px);
+            auto go = [&](auto kern) {
+                hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, static_cast<const TT*>(cover), P->H, P->W, P->maxval, P->T, rows);
+            };
+            pee_flag(pee_vec_route(P, cover), [&](auto v) { go(k_blind_rows<TT, v()>); });
+        });
         LAUNCH_CHECK("k_blind_rows");
     }
     hipLaunchKernelGGL(k_blind_plan, dim3((unsigned)P->B), dim3(256), 0, st, rows, lengths, user_bits, P->H, P->W, P->T,
@@ -448,12 +448,11 @@ int codec_pee_blind_embed(const codec_pee_params* P, const void* cover, void* st
     const long long npx = (long long)P->H * P->W;
     {
         dim3 grid((unsigned)((P->payload_words + 255) / 256), (unsigned)P->B);
-        if (P->bytes == 2)
-            hipLaunchKernelGGL(k_blind_splice<uint16_t>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(cover), npx,
+        pee_pixel(P->bytes, [&](auto px) {
+            using TT = decltype(px);
+            hipLaunchKernelGGL(k_blind_splice<TT>, grid, dim3(256), 0, st, static_cast<const TT*>(cover), npx,
                                reinterpret_cast<const u64*>(payload), (int)user_words, info, rows, P->payload_words);
-        else
-            hipLaunchKernelGGL(k_blind_splice<uint8_t>, grid, dim3(256), 0, st, static_cast<const uint8_t*>(cover), npx,
-                               reinterpret_cast<const u64*>(payload), (int)user_words, info, rows, P->payload_words);
+        });
         LAUNCH_CHECK("k_blind_splice");
     }
     rc = codec_pee_roi_embed(P, cover, stego, reinterpret_cast<const uint64_t*>(rows),
@@ -462,12 +461,11 @@ int codec_pee_blind_embed(const codec_pee_params* P, const void* cover, void* st
                              lm, workspace, workspace_bytes, stream);
     if (rc) return rc;
     const int nc = (P->H / 2) * (P->W / 2);
-    if (P->bytes == 2)
-        hipLaunchKernelGGL(k_blind_pack<uint16_t>, dim3((unsigned)P->B), dim3(256), 0, st, static_cast<uint16_t*>(stego), npx,
-                           nc, P->T, P->maxval, meta, reinterpret_cast<const u64*>(lm), P->lm_words, crc, info);
-    else
-        hipLaunchKernelGGL(k_blind_pack<uint8_t>, dim3((unsigned)P->B), dim3(256), 0, st, static_cast<uint8_t*>(stego), npx,
-                           nc, P->T, P->maxval, meta, reinterpret_cast<const u64*>(lm), P->lm_words, crc, info);
+    pee_pixel(P->bytes, [&](auto px) {
+        using TT = decltype(px);
+        hipLaunchKernelGGL(k_blind_pack<TT>, dim3((unsigned)P->B), dim3(256), 0, st, static_cast<TT*>(stego), npx, nc, P->T,
+                           P->maxval, meta, reinterpret_cast<const u64*>(lm), P->lm_words, crc, info);
+    });
     LAUNCH_CHECK("k_blind_pack");
     return 0;
 }
@@ -480,10 +478,10 @@ int codec_pee_blind_headers(const codec_pee_params* P, const void* stego, uint32
     hipStream_t st = as_stream(stream);
     const long long npx = (long long)P->H * P->W;
     const dim3 grid((unsigned)((8LL * P->B + 255) / 256));
-    if (P->bytes == 2)
-        hipLaunchKernelGGL(k_blind_headers<uint16_t>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(stego), npx, P->B, hdr_out);
-    else
-        hipLaunchKernelGGL(k_blind_headers<uint8_t>, grid, dim3(256), 0, st, static_cast<const uint8_t*>(stego), npx, P->B, hdr_out);
+    pee_pixel(P->bytes, [&](auto px) {
+        using TT = decltype(px);
+        hipLaunchKernelGGL(k_blind_headers<TT>, grid, dim3(256), 0, st, static_cast<const TT*>(stego), npx, P->B, hdr_out);
+    });
     LAUNCH_CHECK("k_blind_headers");
     return 0;
 }
@@ -513,12 +511,11 @@ int codec_pee_blind_extract(const codec_pee_params* P, const void* stego, const 
     const long long ebound = (row_bits - BL_HDR_BITS) / 32;   // >= 0 by the row check
     if (ebound > 0) {
         dim3 grid((unsigned)((ebound + 255) / 256), (unsigned)P->B);
-        if (P->bytes == 2)
-            hipLaunchKernelGGL(k_blind_scatter<uint16_t>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(stego), npx, nc,
-                               row_bits, hdr, lm, P->lm_words);
-        else
-            hipLaunchKernelGGL(k_blind_scatter<uint8_t>, grid, dim3(256), 0, st, static_cast<const uint8_t*>(stego), npx, nc,
-                               row_bits, hdr, lm, P->lm_words);
+        pee_pixel(P->bytes, [&](auto px) {
+            using TT = decltype(px);
+            hipLaunchKernelGGL(k_blind_scatter<TT>, grid, dim3(256), 0, st, static_cast<const TT*>(stego), npx, nc, row_bits,
+                               hdr, lm, P->lm_words);
+        });
         LAUNCH_CHECK("k_blind_scatter");
     }
     rc = codec_pee_roi_extract(P, stego, meta, reinterpret_cast<const uint64_t*>(lm), cover_out,
@@ -527,12 +524,11 @@ int codec_pee_blind_extract(const codec_pee_params* P, const void* stego, const 
     {
         const long long n = std::max(row_bits, (long long)user_words);
         dim3 grid((unsigned)((n + 255) / 256), (unsigned)P->B);
-        if (P->bytes == 2)
-            hipLaunchKernelGGL(k_blind_restore<uint16_t>, grid, dim3(256), 0, st, static_cast<uint16_t*>(cover_out), npx, nc,
-                               row_bits, hdr, rows, P->payload_words, reinterpret_cast<u64*>(payload_out), (int)user_words);
-        else
-            hipLaunchKernelGGL(k_blind_restore<uint8_t>, grid, dim3(256), 0, st, static_cast<uint8_t*>(cover_out), npx, nc,
-                               row_bits, hdr, rows, P->payload_words, reinterpret_cast<u64*>(payload_out), (int)user_words);
+        pee_pixel(P->bytes, [&](auto px) {
+            using TT = decltype(px);
+            hipLaunchKernelGGL(k_blind_restore<TT>, grid, dim3(256), 0, st, static_cast<TT*>(cover_out), npx, nc, row_bits, hdr,
+                               rows, P->payload_words, reinterpret_cast<u64*>(payload_out), (int)user_words);
+        });
         LAUNCH_CHECK("k_blind_restore");
     }
     return 0;

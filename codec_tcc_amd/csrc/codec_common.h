@@ -9,6 +9,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 
 #include "codec_tcc.h"
 
@@ -426,6 +427,31 @@ static long long debug_knob(const char* name, long long dflt) {
 }
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// ---- launch dispatch.  Every launch route of the MED-PEE units writes its kernel argument list
+// once, in a lambda `go(kern)`; the template arguments are chosen around it.  pee_pixel hands the
+// pixel type of P->bytes to a generic lambda (`[&](auto px) { using TT = decltype(px); ... }`) and
+// pee_flag up to three run-time flags as std::bool_constant values (`ip()` is a constant
+// expression).  The kernels instantiated are exactly those named in a go(...): a route that
+// exists for uint16_t only sits under `if constexpr (std::is_same_v<TT, uint16_t>)`.
+template <class F> static inline auto pee_pixel(int bytes, F&& f) { return bytes == 2 ? f(uint16_t{}) : f(uint8_t{}); }
+template <class F> static inline void pee_flag(bool a, F&& f) {
+    if (a) f(std::true_type{}); else f(std::false_type{});
+}
+template <class F> static inline void pee_flag(bool a, bool b, F&& f) {
+    pee_flag(a, [&](auto A) { pee_flag(b, [&](auto B) { f(A, B); }); });
+}
+template <class F> static inline void pee_flag(bool a, bool b, bool c, F&& f) {
+    pee_flag(a, b, [&](auto A, auto B) { pee_flag(c, [&](auto C) { f(A, B, C); }); });
+}
+template <int N> using pee_int = std::integral_constant<int, N>;
+
+// the 8-pixel vector kernels apply: W % 8 == 0 and the image (both images) aligned to `align`
+// bytes; 0: one 8-pixel vector of P->bytes, 16 or 8
+static inline bool pee_vec_route(const codec_pee_params* P, const void* a, const void* b = nullptr, size_t align = 0) {
+    if (!align) align = P->bytes == 2 ? 16 : 8;
+    return (P->W % 8) == 0 && ((uintptr_t)a % align) == 0 && ((uintptr_t)b % align) == 0;
+}
 
 // codec_pee.hip: the PEE workspace registry (include/codec_tcc.h, codec_pee_workspace_bytes) for
 // workspace-taking entries of other translation units.  P has passed the entry's checks and the

@@ -315,22 +315,21 @@ static int gate_capacity(const codec_pee_params* P, const void* cover, int32_t t
         hipLaunchKernelGGL(k_pee_gate_zero, dim3((unsigned)std::min<size_t>(1024, (nz + 255) / 256)), dim3(256), 0, st, gbins, nz);
         LAUNCH_CHECK("k_pee_gate_zero");
     }
-    const size_t va = P->bytes == 2 ? 16 : 8;
-    const bool vec = (P->W % 8) == 0 && ((uintptr_t)cover % va) == 0;
+    const bool vec = pee_vec_route(P, cover);
     const long long units = vec ? (long long)(P->H / 2) * (P->W / 8) : (long long)(P->H / 2) * (P->W / 2);
     ProfScope prof(st, CODEC_K_PEE_GATE_TABLE);
     dim3 grid((unsigned)std::max(1LL, (units + GT_PER_WG - 1) / GT_PER_WG), (unsigned)P->B);
-#define PGT(TT, VV, ...) hipLaunchKernelGGL((k_pee_gate_table<TT, VV, ##__VA_ARGS__>), grid, dim3(256), 0, st, \
-                                            static_cast<const TT*>(cover), P->H, P->W, P->maxval, (int)tmax, (int)t_fixed, \
-                                            (int)g_fixed, gbins, arrivals, lengths, n, hs, t_out, g_out, k_out
-    if (rps) {
-        if (P->bytes == 2) { if (vec) PGT(uint16_t, true, const int32_t*), rps); else PGT(uint16_t, false, const int32_t*), rps); }
-        else { if (vec) PGT(uint8_t, true, const int32_t*), rps); else PGT(uint8_t, false, const int32_t*), rps); }
-    } else {
-        if (P->bytes == 2) { if (vec) PGT(uint16_t, true)); else PGT(uint16_t, false)); }
-        else { if (vec) PGT(uint8_t, true)); else PGT(uint8_t, false)); }
-    }
-#undef PGT
+    auto go = [&](auto... roi) {   // roi: the rectangles, for the ROI instantiations
+        pee_pixel(P->bytes, [&](auto px) {
+            using TT = decltype(px);
+            pee_flag(vec, [&](auto v) {
+                hipLaunchKernelGGL((k_pee_gate_table<TT, v(), decltype(roi)...>), grid, dim3(256), 0, st,
+                                   static_cast<const TT*>(cover), P->H, P->W, P->maxval, (int)tmax, (int)t_fixed, (int)g_fixed,
+                                   gbins, arrivals, lengths, n, hs, t_out, g_out, k_out, roi...);
+            });
+        });
+    };
+    if (rps) go(rps); else go();
     LAUNCH_CHECK("k_pee_gate_table");
     return 0;
 }

@@ -21,7 +21,7 @@
 // three per class; the tie-break is explicit (smaller T, then smaller j) and the tests pin the
 // two to the same answers.  Table values are clamped to (H/2)(W/2) as they are read.
 // The decode side needs no kernel of its own: k_vol_plan<1> scans the records' L.
-#include "codec_common.h"
+#include "codec_vol_checks.h"
 #include "codec_tcc_gvol.h"
 
 #define GV_NT 1024
@@ -268,60 +268,18 @@ __global__ __launch_bounds__(GV_NT) void k_gvol_plan(const uint32_t* __restrict_
 }
 
 // ====================================================================== host side
-struct GvolWs {
-    size_t off, rows, ntab, hstab, total;
+// the checks are codec_vol_checks.h's, with the gate's bound on a slice's candidates
+static int gvol_check(const codec_pee_params* P, const char* who) { return vol_check(P, who, CODEC_PEE_GATE_MAX_NC); }
+
+// the workspace: the volume head (codec_pee_volume_gather takes this workspace as it is), then
+// the tables n [B][16] and hs [B][tmax][16]
+struct GvolWs : VolWsHead {
+    size_t ntab, hstab, total;
 };
-
-static long long gvol_nc(const codec_pee_params* P) { return (long long)(P->H / 2) * (P->W / 2); }
-
-// the checks every entry shares: codec_pee's own, the volume bounds and the gate's
-static int gvol_check(const codec_pee_params* P, const char* who) {
-    if (!P) return set_err(CODEC_EINVAL, "%s: params is NULL", who);
-    if (P->B < 1 || P->H < 1 || P->W < 1 || (long long)P->H * P->W > 0x7FFFFFFFLL)
-        return set_err(CODEC_EINVAL, "%s: bad shape B=%d H=%d W=%d", who, P->B, P->H, P->W);
-    if (P->bytes != 1 && P->bytes != 2) return set_err(CODEC_EINVAL, "%s: bytes must be 1 or 2", who);
-    if (P->T < 1) return set_err(CODEC_EINVAL, "%s: T must be >= 1", who);
-    const int vmax = P->bytes == 2 ? 65535 : 255;
-    if (P->maxval < 1 || P->maxval > vmax) return set_err(CODEC_EINVAL, "%s: maxval out of range", who);
-    if (P->payload_words < 1 || P->lm_words < 1)
-        return set_err(CODEC_EINVAL, "%s: payload_words/lm_words must be >= 1", who);
-    const long long nc = gvol_nc(P);
-    if ((long long)P->lm_words * 64 < nc) return set_err(CODEC_EINVAL, "%s: lm_words must cover every candidate", who);
-    if (nc > CODEC_PEE_GATE_MAX_NC) return set_err(CODEC_EINVAL, "%s: more than 2^26 candidates per slice", who);
-    if ((long long)P->B * nc > 0x7FFFFFFFLL)
-        return set_err(CODEC_EINVAL, "%s: B * (H/2) * (W/2) = %lld exceeds 2^31 - 1", who, (long long)P->B * nc);
-    if ((long long)P->B * P->payload_words > 0x7FFFFFFFLL)
-        return set_err(CODEC_EINVAL, "%s: B * payload_words exceeds 2^31 - 1", who);
-    return 0;
-}
-
-static int gvol_check_tmax(int32_t tmax, const char* who) {
-    if (tmax < 1 || tmax > GV_TMAX) return set_err(CODEC_EINVAL, "%s: tmax must be in 1..16", who);
-    return 0;
-}
-
-static int gvol_check_plan(const codec_pee_params* P, int32_t tmax, int64_t nbits, int32_t policy, int32_t g_fixed,
-                           const char* who) {
-    int rc = gvol_check_tmax(tmax, who);
-    if (rc) return rc;
-    if (nbits < 0 || nbits > 0x7FFFFFFFLL) return set_err(CODEC_EINVAL, "%s: nbits must be in 0..2^31 - 1", who);
-    if (policy != CODEC_VOL_EVEN && policy != CODEC_VOL_FILL)
-        return set_err(CODEC_EINVAL, "%s: policy must be CODEC_VOL_EVEN or CODEC_VOL_FILL", who);
-    if (g_fixed < -1 || g_fixed > CODEC_PEE_GATE_MAX)
-        return set_err(CODEC_EINVAL, "%s: g_fixed must be -1 or in 0..65535", who);
-    if (64ll * P->payload_words < std::min<long long>(nbits, gvol_nc(P)))
-        return set_err(CODEC_EINVAL, "%s: payload_words = %d cannot hold a slice's share of %lld bits", who,
-                       P->payload_words, (long long)nbits);
-    return 0;
-}
-
-// head: the layout of codec_vol.hip's workspace for tmax = 1 (offsets, then the rows), so that
-// codec_pee_volume_gather takes this workspace as it is
 static GvolWs gvol_ws(const codec_pee_params* P, int32_t tmax) {
     GvolWs L;
-    L.off = 0;
-    L.rows = align_up(((size_t)P->B + 1) * 4, 256);
-    L.ntab = align_up(L.rows + (size_t)P->B * P->payload_words * 8, 256);
+    static_cast<VolWsHead&>(L) = vol_ws_head(P);
+    L.ntab = L.end;
     L.hstab = align_up(L.ntab + (size_t)P->B * GV_CLASSES * 4, 256);
     L.total = align_up(L.hstab + (size_t)P->B * tmax * GV_CLASSES * 4, 256);
     return L;
@@ -331,7 +289,7 @@ static int gvol_launch_plan(const codec_pee_params* P, const uint32_t* n, const 
                             int64_t nbits, int32_t policy, int32_t g_fixed, int32_t* n_out, int32_t* t_out,
                             int32_t* g_out, int32_t* off_out, codec_pee_gvol_info* info, hipStream_t st) {
     ProfScope prof(st, CODEC_K_GVOL_PLAN);
-    hipLaunchKernelGGL(k_gvol_plan, dim3(1), dim3(GV_NT), 0, st, n, hs, (int)P->B, (int)tmax, (uint32_t)gvol_nc(P),
+    hipLaunchKernelGGL(k_gvol_plan, dim3(1), dim3(GV_NT), 0, st, n, hs, (int)P->B, (int)tmax, (uint32_t)vol_nc(P),
                        (u64)nbits, (int)policy, (int)g_fixed, n_out, t_out, g_out, off_out, info);
     LAUNCH_CHECK("k_gvol_plan");
     return 0;
@@ -341,7 +299,7 @@ extern "C" {
 
 size_t codec_pee_gvol_workspace_bytes(const codec_pee_params* P, int32_t tmax) {
     if (gvol_check(P, "codec_pee_gvol_workspace_bytes")) return 0;
-    if (gvol_check_tmax(tmax, "codec_pee_gvol_workspace_bytes")) return 0;
+    if (vol_check_tmax(tmax, GV_TMAX, "codec_pee_gvol_workspace_bytes")) return 0;
     return gvol_ws(P, tmax).total;
 }
 
@@ -350,7 +308,7 @@ int codec_pee_gvol_plan(const codec_pee_params* P, const uint32_t* n, const uint
                         int32_t* off_out, codec_pee_gvol_info* info, void* stream) {
     int rc = gvol_check(P, "codec_pee_gvol_plan");
     if (rc) return rc;
-    if ((rc = gvol_check_plan(P, tmax, nbits, policy, g_fixed, "codec_pee_gvol_plan"))) return rc;
+    if ((rc = vol_check_plan(P, tmax, GV_TMAX, nbits, policy, g_fixed, "codec_pee_gvol_plan"))) return rc;
     if (!n || !hs || !n_out || !t_out || !g_out || !off_out || !info)
         return set_err(CODEC_EINVAL, "codec_pee_gvol_plan: NULL pointer argument");
     return gvol_launch_plan(P, n, hs, tmax, nbits, policy, g_fixed, n_out, t_out, g_out, off_out, info,
@@ -364,14 +322,11 @@ int codec_pee_gvol_embed(const codec_pee_params* P, const void* cover, void* ste
                          size_t table_workspace_bytes, void* gvol_workspace, size_t gvol_workspace_bytes, void* stream) {
     int rc = gvol_check(P, "codec_pee_gvol_embed");
     if (rc) return rc;
-    if ((rc = gvol_check_plan(P, tmax, nbits, policy, g_fixed, "codec_pee_gvol_embed"))) return rc;
+    if ((rc = vol_check_plan(P, tmax, GV_TMAX, nbits, policy, g_fixed, "codec_pee_gvol_embed"))) return rc;
     if (!cover || !stego || !n_out || !t_out || !g_out || !off_out || !info || !meta || !lm || !pee_workspace ||
         !table_workspace || !gvol_workspace || (!bitstream && nbits > 0))
         return set_err(CODEC_EINVAL, "codec_pee_gvol_embed: NULL pointer argument");
-    const size_t need_pee = codec_pee_workspace_bytes(P);
-    if (!need_pee || pee_workspace_bytes < need_pee)
-        return set_err(CODEC_EINVAL, "codec_pee_gvol_embed: PEE workspace too small (%zu < %zu)", pee_workspace_bytes,
-                       need_pee);
+    if ((rc = vol_check_pee_ws(P, pee_workspace_bytes, "codec_pee_gvol_embed"))) return rc;
     const size_t need_tab = codec_pee_gate_workspace_bytes(P, tmax);
     if (!need_tab || table_workspace_bytes < need_tab)
         return set_err(CODEC_EINVAL, "codec_pee_gvol_embed: table workspace too small (%zu < %zu)",
@@ -401,16 +356,11 @@ int codec_pee_gvol_extract(const codec_pee_params* P, const void* stego, const c
                            size_t gvol_workspace_bytes, void* stream) {
     int rc = gvol_check(P, "codec_pee_gvol_extract");
     if (rc) return rc;
-    // one thread per word in blocks of 256; a stream never holds more than 2^31 - 1 bits
-    if (stream_words < 0 || stream_words > (1ll << 25))
-        return set_err(CODEC_EINVAL, "codec_pee_gvol_extract: stream_words must be in 0..2^25");
+    if ((rc = vol_check_stream_words(stream_words, "codec_pee_gvol_extract"))) return rc;
     if (!stego || !meta || !lm || !cover_out || !total_out || !pee_workspace || !gvol_workspace ||
         (!bitstream && stream_words > 0))
         return set_err(CODEC_EINVAL, "codec_pee_gvol_extract: NULL pointer argument");
-    const size_t need_pee = codec_pee_workspace_bytes(P);
-    if (!need_pee || pee_workspace_bytes < need_pee)
-        return set_err(CODEC_EINVAL, "codec_pee_gvol_extract: PEE workspace too small (%zu < %zu)",
-                       pee_workspace_bytes, need_pee);
+    if ((rc = vol_check_pee_ws(P, pee_workspace_bytes, "codec_pee_gvol_extract"))) return rc;
     const GvolWs L = gvol_ws(P, 1);
     if (gvol_workspace_bytes < L.total)
         return set_err(CODEC_EINVAL, "codec_pee_gvol_extract: gated volume workspace too small (%zu < %zu)",

@@ -3457,23 +3457,8 @@ static int pee_multi_check(const codec_pee_params* P, int pass) {
     return 0;
 }
 
-// ---- launch dispatch.  Every launch route below writes its kernel argument list once, in a
-// lambda `go(kern)`; the template arguments are chosen around it.  pee_pixel hands the pixel
-// type of P->bytes to a generic lambda (`[&](auto px) { using TT = decltype(px); ... }`) and
-// pee_flag up to three run-time flags as std::bool_constant values (`ip()` is a constant
-// expression).  The kernels instantiated are exactly those named in a go(...): a route that
-// exists for uint16_t only sits under `if constexpr (std::is_same_v<TT, uint16_t>)`.
-template <class F> static inline auto pee_pixel(int bytes, F&& f) { return bytes == 2 ? f(uint16_t{}) : f(uint8_t{}); }
-template <class F> static inline void pee_flag(bool a, F&& f) {
-    if (a) f(std::true_type{}); else f(std::false_type{});
-}
-template <class F> static inline void pee_flag(bool a, bool b, F&& f) {
-    pee_flag(a, [&](auto A) { pee_flag(b, [&](auto B) { f(A, B); }); });
-}
-template <class F> static inline void pee_flag(bool a, bool b, bool c, F&& f) {
-    pee_flag(a, b, [&](auto A, auto B) { pee_flag(c, [&](auto C) { f(A, B, C); }); });
-}
-template <int N> using pee_int = std::integral_constant<int, N>;
+// ---- launch dispatch: every launch route below writes its kernel argument list once, in a
+// lambda `go(kern)`, with pee_pixel / pee_flag / pee_int (codec_common.h) around it.
 
 // ---- the entry sequence of the workspace-taking calls, in the order their errors are
 // reported: the params (`checked` = what pee_check / pee_multi_check returned: the call site
@@ -3505,8 +3490,8 @@ int pee_workspace_enter(const codec_pee_params* P, void* workspace, void* stream
     return 0;
 }
 
-// ---- what the scheme-1 routes are chosen by.  vec: the 8-pixel vector kernels apply (W % 8
-// == 0 and both images aligned to `align` bytes; 0: one 8-pixel vector of P->bytes, 16 or 8);
+// ---- what the scheme-1 routes are chosen by.  vec: the 8-pixel vector kernels apply
+// (pee_vec_route, both images aligned to `align` bytes);
 // items: 8-pixel row-pair chunks per slice; onepass: CODEC_PEE_ONEPASS (0 forces the two-pass
 // path); flat: B <= CODEC_PEE_FLAT_MAXB (7) out of place, see pee_embed_t
 struct PeeRoute {
@@ -3514,9 +3499,8 @@ struct PeeRoute {
     long long items, onepass;
 };
 static PeeRoute pee_route(const codec_pee_params* P, const void* src, const void* dst, size_t align = 0) {
-    if (!align) align = P->bytes == 2 ? 16 : 8;
     PeeRoute R;
-    R.vec = (P->W % 8) == 0 && ((uintptr_t)src % align) == 0 && ((uintptr_t)dst % align) == 0;
+    R.vec = pee_vec_route(P, src, dst, align);
     R.inplace = src == dst;
     R.items = (long long)(P->H / 2) * (P->W / 8);
     R.onepass = knob("CODEC_PEE_ONEPASS", -1);
@@ -3616,8 +3600,7 @@ int codec_pee_capacity(const codec_pee_params* P, const void* cover, int32_t tma
     uint32_t* hist = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + L.hist);
     // no memset: bins and arrival counters are zero on entry (zeroed workspace; each slice's
     // last workgroup clears them)
-    const size_t va = P->bytes == 2 ? 16 : 8;
-    const bool vec = (P->W % 8) == 0 && ((uintptr_t)cover % va) == 0;
+    const bool vec = pee_vec_route(P, cover);
     const long long units = vec ? (long long)(P->H / 2) * (P->W / 8) : (long long)(P->H / 2) * (P->W / 2);
     ProfScope prof(st, CODEC_K_PEE_CAPACITY);
     {   // launched even when there is nothing to count: the last workgroup writes caps / t_out

@@ -147,8 +147,7 @@ int codec_roi_bbox(const codec_pee_params* P, const void* image, int32_t level, 
                    void* stream) {
     if (!P) return set_err(CODEC_EINVAL, "codec_roi_bbox: params is NULL");
     if (!codec_pee_workspace_bytes(P)) return CODEC_EINVAL;   // checks P and sets the text
-    if (P->H > CODEC_PEE_ROI_MAX_DIM || P->W > CODEC_PEE_ROI_MAX_DIM)
-        return set_err(CODEC_EINVAL, "codec_roi_bbox: H and W must be <= 65535");
+    if (int rc = pee_roi_dim_check(P, "codec_roi_bbox")) return rc;
     if (!image || !roi_out) return set_err(CODEC_EINVAL, "codec_roi_bbox: NULL pointer argument");
     if (level < 0 || level > 65535) return set_err(CODEC_EINVAL, "codec_roi_bbox: level must be in 0..65535");
     if (margin < 0 || margin > 65535) return set_err(CODEC_EINVAL, "codec_roi_bbox: margin must be in 0..65535");
@@ -163,11 +162,11 @@ int codec_roi_bbox(const codec_pee_params* P, const void* image, int32_t level, 
         const long long npx = (long long)P->H * P->W;
         const long long units = vec ? (npx / vl + RB_VEC_PER_WG - 1) / RB_VEC_PER_WG : (npx + RB_PX_PER_WG - 1) / RB_PX_PER_WG;
         dim3 grid((unsigned)units, (unsigned)P->B);   // >= 1: H, W >= 1
-#define RBB(TT, VV) hipLaunchKernelGGL((k_roi_bbox<TT, VV>), grid, dim3(256), 0, st, static_cast<const TT*>(image), P->H, \
-                                       P->W, (uint32_t)level, roi_out)
-        if (P->bytes == 2) { if (vec) RBB(uint16_t, true); else RBB(uint16_t, false); }
-        else { if (vec) RBB(uint8_t, true); else RBB(uint8_t, false); }
-#undef RBB
+        pee_pixel(P->bytes, [&](auto px) {
+            const auto* img = static_cast<const decltype(px)*>(image);
+            auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, img, P->H, P->W, (uint32_t)level, roi_out); };
+            pee_flag(vec, [&](auto v) { go(k_roi_bbox<decltype(px), v()>); });
+        });
         LAUNCH_CHECK("k_roi_bbox");
     }
     hipLaunchKernelGGL(k_roi_finish, dim3(gb), dim3(256), 0, st, roi_out, P->B, P->H, P->W, (int)margin);

@@ -15,8 +15,7 @@
 //   k_vol_gather   one thread per stream word: a binary search in off for the first slice that
 //                  contributes, then a walk over slices (runs of empty ones included) until the
 //                  word's 64 bits are filled.  Each word is written once.
-#include "codec_common.h"
-#include "codec_tcc_vol.h"
+#include "codec_vol_checks.h"
 
 #define VOL_NT 1024
 #define VOL_TMAX 64
@@ -188,48 +187,14 @@ __global__ __launch_bounds__(256) void k_vol_gather(const u64* __restrict__ rows
 }
 
 // ====================================================================== host side
-struct VolWs {
-    size_t off, rows, caps, total;
+// the checks are codec_vol_checks.h's; the workspace: its head, then the capacities [B][tmax]
+struct VolWs : VolWsHead {
+    size_t caps, total;
 };
-
-static long long vol_nc(const codec_pee_params* P) { return (long long)(P->H / 2) * (P->W / 2); }
-
-// the checks every entry shares (codec_pee's own, and the volume bounds)
-static int vol_check(const codec_pee_params* P, const char* who) {
-    if (!P) return set_err(CODEC_EINVAL, "%s: params is NULL", who);
-    if (P->B < 1 || P->H < 1 || P->W < 1 || (long long)P->H * P->W > 0x7FFFFFFFLL)
-        return set_err(CODEC_EINVAL, "%s: bad shape B=%d H=%d W=%d", who, P->B, P->H, P->W);
-    if (P->bytes != 1 && P->bytes != 2) return set_err(CODEC_EINVAL, "%s: bytes must be 1 or 2", who);
-    if (P->T < 1) return set_err(CODEC_EINVAL, "%s: T must be >= 1", who);
-    const int vmax = P->bytes == 2 ? 65535 : 255;
-    if (P->maxval < 1 || P->maxval > vmax) return set_err(CODEC_EINVAL, "%s: maxval out of range", who);
-    if (P->payload_words < 1 || P->lm_words < 1)
-        return set_err(CODEC_EINVAL, "%s: payload_words/lm_words must be >= 1", who);
-    const long long nc = vol_nc(P);
-    if ((long long)P->lm_words * 64 < nc) return set_err(CODEC_EINVAL, "%s: lm_words must cover every candidate", who);
-    if ((long long)P->B * nc > 0x7FFFFFFFLL)
-        return set_err(CODEC_EINVAL, "%s: B * (H/2) * (W/2) = %lld exceeds 2^31 - 1", who, (long long)P->B * nc);
-    if ((long long)P->B * P->payload_words > 0x7FFFFFFFLL)
-        return set_err(CODEC_EINVAL, "%s: B * payload_words exceeds 2^31 - 1", who);
-    return 0;
-}
-
-static int vol_check_plan(const codec_pee_params* P, int32_t tmax, int64_t nbits, int32_t policy, const char* who) {
-    if (tmax < 1 || tmax > VOL_TMAX) return set_err(CODEC_EINVAL, "%s: tmax must be in 1..64", who);
-    if (nbits < 0 || nbits > 0x7FFFFFFFLL) return set_err(CODEC_EINVAL, "%s: nbits must be in 0..2^31 - 1", who);
-    if (policy != CODEC_VOL_EVEN && policy != CODEC_VOL_FILL)
-        return set_err(CODEC_EINVAL, "%s: policy must be CODEC_VOL_EVEN or CODEC_VOL_FILL", who);
-    if (64ll * P->payload_words < std::min<long long>(nbits, vol_nc(P)))
-        return set_err(CODEC_EINVAL, "%s: payload_words = %d cannot hold a slice's share of %lld bits", who,
-                       P->payload_words, (long long)nbits);
-    return 0;
-}
-
 static VolWs vol_ws(const codec_pee_params* P, int32_t tmax) {
     VolWs L;
-    L.off = 0;
-    L.rows = align_up(((size_t)P->B + 1) * 4, 256);
-    L.caps = align_up(L.rows + (size_t)P->B * P->payload_words * 8, 256);
+    static_cast<VolWsHead&>(L) = vol_ws_head(P);
+    L.caps = L.end;
     L.total = align_up(L.caps + (size_t)P->B * tmax * 4, 256);
     return L;
 }
@@ -280,21 +245,11 @@ static int vol_launch_gather(const codec_pee_params* P, const codec_pee_meta* me
     return 0;
 }
 
-static int vol_check_stream_words(int64_t stream_words, const char* who) {
-    // one thread per word in blocks of 256; a stream never holds more than 2^31 - 1 bits
-    if (stream_words < 0 || stream_words > (1ll << 25))
-        return set_err(CODEC_EINVAL, "%s: stream_words must be in 0..2^25", who);
-    return 0;
-}
-
 extern "C" {
 
 size_t codec_pee_volume_workspace_bytes(const codec_pee_params* P, int32_t tmax) {
     if (vol_check(P, "codec_pee_volume_workspace_bytes")) return 0;
-    if (tmax < 1 || tmax > VOL_TMAX) {
-        set_err(CODEC_EINVAL, "codec_pee_volume_workspace_bytes: tmax must be in 1..64");
-        return 0;
-    }
+    if (vol_check_tmax(tmax, VOL_TMAX, "codec_pee_volume_workspace_bytes")) return 0;
     return vol_ws(P, tmax).total;
 }
 
@@ -303,7 +258,7 @@ int codec_pee_volume_plan(const codec_pee_params* P, const int32_t* caps, int32_
                           void* stream) {
     int rc = vol_check(P, "codec_pee_volume_plan");
     if (rc) return rc;
-    if ((rc = vol_check_plan(P, tmax, nbits, policy, "codec_pee_volume_plan"))) return rc;
+    if ((rc = vol_check_plan(P, tmax, VOL_TMAX, nbits, policy, -1, "codec_pee_volume_plan"))) return rc;
     if (!caps || !n_out || !t_out || !off_out || !info)
         return set_err(CODEC_EINVAL, "codec_pee_volume_plan: NULL pointer argument");
     return vol_launch_plan(P, caps, tmax, nbits, policy, n_out, t_out, off_out, info, as_stream(stream));
@@ -342,14 +297,11 @@ int codec_pee_volume_embed(const codec_pee_params* P, const void* cover, void* s
                            size_t vol_workspace_bytes, void* stream) {
     int rc = vol_check(P, "codec_pee_volume_embed");
     if (rc) return rc;
-    if ((rc = vol_check_plan(P, tmax, nbits, policy, "codec_pee_volume_embed"))) return rc;
+    if ((rc = vol_check_plan(P, tmax, VOL_TMAX, nbits, policy, -1, "codec_pee_volume_embed"))) return rc;
     if (!cover || !stego || !n_out || !t_out || !off_out || !info || !meta || !lm || !pee_workspace || !vol_workspace ||
         (!bitstream && nbits > 0))
         return set_err(CODEC_EINVAL, "codec_pee_volume_embed: NULL pointer argument");
-    const size_t need_pee = codec_pee_workspace_bytes(P);
-    if (!need_pee || pee_workspace_bytes < need_pee)
-        return set_err(CODEC_EINVAL, "codec_pee_volume_embed: PEE workspace too small (%zu < %zu)", pee_workspace_bytes,
-                       need_pee);
+    if ((rc = vol_check_pee_ws(P, pee_workspace_bytes, "codec_pee_volume_embed"))) return rc;
     const VolWs L = vol_ws(P, tmax);
     if (vol_workspace_bytes < L.total)
         return set_err(CODEC_EINVAL, "codec_pee_volume_embed: volume workspace too small (%zu < %zu)",
@@ -375,10 +327,7 @@ int codec_pee_volume_extract(const codec_pee_params* P, const void* stego, const
     if (!stego || !meta || !lm || !cover_out || !total_out || !pee_workspace || !vol_workspace ||
         (!bitstream && stream_words > 0))
         return set_err(CODEC_EINVAL, "codec_pee_volume_extract: NULL pointer argument");
-    const size_t need_pee = codec_pee_workspace_bytes(P);
-    if (!need_pee || pee_workspace_bytes < need_pee)
-        return set_err(CODEC_EINVAL, "codec_pee_volume_extract: PEE workspace too small (%zu < %zu)",
-                       pee_workspace_bytes, need_pee);
+    if ((rc = vol_check_pee_ws(P, pee_workspace_bytes, "codec_pee_volume_extract"))) return rc;
     const VolWs L = vol_ws(P, 1);
     if (vol_workspace_bytes < L.total)
         return set_err(CODEC_EINVAL, "codec_pee_volume_extract: volume workspace too small (%zu < %zu)",

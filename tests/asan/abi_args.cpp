@@ -12,30 +12,7 @@
 
 #include "codec_tcc.h"
 
-static int g_fail = 0, g_n = 0;
-extern "C" int hip_stub_device_ops(void);   // tests/asan/hip_stubs.cpp
-
-#define EXPECT_NEG(expr)                                                                           \
-    do {                                                                                           \
-        ++g_n;                                                                                     \
-        const long long r_ = (long long)(expr);                                                    \
-        if (r_ >= 0) {                                                                             \
-            fprintf(stderr, "FAIL line %d: %s returned %lld (want < 0)\n", __LINE__, #expr, r_);   \
-            ++g_fail;                                                                              \
-        } else if (!codec_last_error() || !codec_last_error()[0]) {                                \
-            fprintf(stderr, "FAIL line %d: %s gave no error message\n", __LINE__, #expr);          \
-            ++g_fail;                                                                              \
-        }                                                                                          \
-    } while (0)
-#define EXPECT_ZERO(expr)                                                                          \
-    do {                                                                                           \
-        ++g_n;                                                                                     \
-        const long long r_ = (long long)(expr);                                                    \
-        if (r_ != 0) {                                                                             \
-            fprintf(stderr, "FAIL line %d: %s returned %lld (want 0)\n", __LINE__, #expr, r_);     \
-            ++g_fail;                                                                              \
-        }                                                                                          \
-    } while (0)
+#include "abi_expect.h"
 
 static codec_params good_params() {
     codec_params P;
@@ -331,10 +308,6 @@ int main() {
     EXPECT_NEG(codec_debug_res_trace(reinterpret_cast<unsigned long long*>(buf), -1));
 
     if (!codec_build_digest()) { fprintf(stderr, "FAIL build digest NULL\n"); ++g_fail; }
-    if (hip_stub_device_ops() != 0) {
-        fprintf(stderr, "FAIL %d launches / memory operations reached the runtime\n", hip_stub_device_ops());
-        ++g_fail;
-    }
-    printf("abi_args: %d calls, %d failures\n", g_n, g_fail);
-    return g_fail ? 1 : 0;
+    expect_no_device_ops();
+    return abi_report("abi_args");
 }

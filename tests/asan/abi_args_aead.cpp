@@ -1,7 +1,7 @@
 // Host sanitizer check of the argument validation of include/codec_tcc_aead.h's entries, as
 // abi_args_crc.cpp is for codec_tcc_crc.h: linked against the host-only
 // -fsanitize=address,undefined build of the library and tests/asan/hip_stubs.cpp
-// (tests/test_asan_abi_aead.py builds and runs it).  Every bad call must return its negative
+// (tests/test_asan_abi.py builds and runs it).  Every bad call must return its negative
 // status (0 for the size queries) with an error text and no device operation.
 #include <stdint.h>
 #include <stdio.h>
@@ -9,31 +9,7 @@
 
 #include "codec_tcc_aead.h"
 
-static int g_fail = 0, g_n = 0;
-extern "C" int hip_stub_device_ops(void);   // tests/asan/hip_stubs.cpp
-
-#define EXPECT_NEG(expr)                                                                           \
-    do {                                                                                           \
-        ++g_n;                                                                                     \
-        const long long r_ = (long long)(expr);                                                    \
-        if (r_ >= 0) {                                                                             \
-            fprintf(stderr, "FAIL line %d: %s returned %lld (want < 0)\n", __LINE__, #expr, r_);   \
-            ++g_fail;                                                                              \
-        } else if (!codec_last_error() || !codec_last_error()[0]) {                                \
-            fprintf(stderr, "FAIL line %d: %s gave no error message\n", __LINE__, #expr);          \
-            ++g_fail;                                                                              \
-        }                                                                                          \
-    } while (0)
-
-#define EXPECT_EQ(expr, want)                                                                      \
-    do {                                                                                           \
-        ++g_n;                                                                                     \
-        const unsigned long long r_ = (unsigned long long)(expr), w_ = (unsigned long long)(want); \
-        if (r_ != w_) {                                                                            \
-            fprintf(stderr, "FAIL line %d: %s = %llu (want %llu)\n", __LINE__, #expr, r_, w_);     \
-            ++g_fail;                                                                              \
-        }                                                                                          \
-    } while (0)
+#include "abi_expect.h"
 
 int main() {
     alignas(64) static unsigned char buf[1 << 16];
@@ -138,10 +114,6 @@ int main() {
     EXPECT_NEG(codec_aead_release(ctx, 2, 0, u32, u32, rows, 4, len, nullptr, len, nullptr));
     EXPECT_NEG(codec_aead_release(ctx, 2, 0, u32, u32, rows, 4, len, rows, nullptr, nullptr));
 
-    if (hip_stub_device_ops() != 0) {
-        fprintf(stderr, "FAIL: %d device operations were attempted by argument-error calls\n", hip_stub_device_ops());
-        ++g_fail;
-    }
-    printf("abi_args_aead: %d calls, %d failures\n", g_n, g_fail);
-    return g_fail ? 1 : 0;
+    expect_no_device_ops();
+    return abi_report("abi_args_aead");
 }

@@ -1,6 +1,6 @@
 // Host sanitizer check of the argument validation of include/codec_tcc_ext.h's entries, as
 // abi_args.cpp is for codec_tcc.h: linked against the host-only -fsanitize=address,undefined
-// build of the library and tests/asan/hip_stubs.cpp (tests/test_asan_abi_ext.py builds and runs
+// build of the library and tests/asan/hip_stubs.cpp (tests/test_asan_abi.py builds and runs
 // it on the CPU box).  Every call has NULL pointers, a bad shape, tmin / tmax out of range,
 // cover == stego or a short workspace, and must return its negative status with an error text.
 // No call here reaches a kernel launch.
@@ -12,21 +12,7 @@
 
 #include "codec_tcc_ext.h"
 
-static int g_fail = 0, g_n = 0;
-extern "C" int hip_stub_device_ops(void);   // tests/asan/hip_stubs.cpp
-
-#define EXPECT_NEG(expr)                                                                           \
-    do {                                                                                           \
-        ++g_n;                                                                                     \
-        const long long r_ = (long long)(expr);                                                    \
-        if (r_ >= 0) {                                                                             \
-            fprintf(stderr, "FAIL line %d: %s returned %lld (want < 0)\n", __LINE__, #expr, r_);   \
-            ++g_fail;                                                                              \
-        } else if (!codec_last_error() || !codec_last_error()[0]) {                                \
-            fprintf(stderr, "FAIL line %d: %s gave no error message\n", __LINE__, #expr);          \
-            ++g_fail;                                                                              \
-        }                                                                                          \
-    } while (0)
+#include "abi_expect.h"
 
 static codec_pee_params good_pee() {
     codec_pee_params P;
@@ -97,10 +83,6 @@ int main() {
         EXPECT_NEG(codec_pee_multi_embed_auto(&P, p, q, w64, i32, 1, 4, i32, pmeta, w64, p, ws - 1, nullptr));
         EXPECT_NEG(codec_pee_multi_embed_auto(&P, p, q, w64, i32, 1, 4, i32, pmeta, w64, p, 0, nullptr));
     }
-    if (hip_stub_device_ops() != 0) {
-        fprintf(stderr, "FAIL: %d device operations were attempted by argument-error calls\n", hip_stub_device_ops());
-        ++g_fail;
-    }
-    printf("abi_args_ext: %d calls, %d failures\n", g_n, g_fail);
-    return g_fail ? 1 : 0;
+    expect_no_device_ops();
+    return abi_report("abi_args_ext");
 }

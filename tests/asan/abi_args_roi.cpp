@@ -1,7 +1,7 @@
 // Host sanitizer check of the argument validation of include/codec_tcc_roi.h's entries, as
 // abi_args_gate.cpp is for codec_tcc_gate.h: linked against the host-only
 // -fsanitize=address,undefined build of the library and tests/asan/hip_stubs.cpp
-// (tests/test_asan_abi_roi.py builds and runs it).  Every bad call must return its negative
+// (tests/test_asan_abi.py builds and runs it).  Every bad call must return its negative
 // status with an error text and no device operation; every call with good arguments must get
 // past the checks, i.e. reach its first device operation (which the stubs refuse and count).
 #include <stdint.h>
@@ -10,31 +10,7 @@
 
 #include "codec_tcc_roi.h"
 
-static int g_fail = 0, g_n = 0;
-extern "C" int hip_stub_device_ops(void);   // tests/asan/hip_stubs.cpp
-
-#define EXPECT_NEG(expr)                                                                           \
-    do {                                                                                           \
-        ++g_n;                                                                                     \
-        const long long r_ = (long long)(expr);                                                    \
-        if (r_ >= 0) {                                                                             \
-            fprintf(stderr, "FAIL line %d: %s returned %lld (want < 0)\n", __LINE__, #expr, r_);   \
-            ++g_fail;                                                                              \
-        } else if (!codec_last_error() || !codec_last_error()[0]) {                                \
-            fprintf(stderr, "FAIL line %d: %s gave no error message\n", __LINE__, #expr);          \
-            ++g_fail;                                                                              \
-        }                                                                                          \
-    } while (0)
-
-#define EXPECT_EQ(expr, want)                                                                      \
-    do {                                                                                           \
-        ++g_n;                                                                                     \
-        const unsigned long long r_ = (unsigned long long)(expr), w_ = (unsigned long long)(want); \
-        if (r_ != w_) {                                                                            \
-            fprintf(stderr, "FAIL line %d: %s = %llu (want %llu)\n", __LINE__, #expr, r_, w_);     \
-            ++g_fail;                                                                              \
-        }                                                                                          \
-    } while (0)
+#include "abi_expect.h"
 
 static codec_pee_params good() {
     codec_pee_params P;
@@ -201,10 +177,7 @@ int main() {
     EXPECT_NEG(BOX(&G, p, 0, 65536, i32));
     EXPECT_NEG(BOX(&G, p, 0, INT32_MAX, i32));
 
-    if (hip_stub_device_ops() != 0) {
-        fprintf(stderr, "FAIL: %d device operations were attempted by argument-error calls\n", hip_stub_device_ops());
-        ++g_fail;
-    }
+    expect_no_device_ops();
 
     // ---- good arguments: each entry gets past its checks and reaches a device operation, which
     // the stubs refuse and count.  The buffer stands in for device memory:
@@ -212,17 +185,7 @@ int main() {
     {
         static unsigned char ws[1 << 22];
         if (gws > sizeof(ws)) { fprintf(stderr, "FAIL: workspace of the good shape is %zu bytes\n", gws); return 2; }
-        int ops = hip_stub_device_ops();
-#define EXPECT_REACHED(expr)                                                                           \
-    do {                                                                                               \
-        ++g_n;                                                                                         \
-        (void)(expr);   /* whatever the refused launches make of it */                                 \
-        if (hip_stub_device_ops() <= ops) {                                                            \
-            fprintf(stderr, "FAIL line %d: %s stopped before any device operation: %s\n", __LINE__, #expr, codec_last_error()); \
-            ++g_fail;                                                                                  \
-        }                                                                                              \
-        ops = hip_stub_device_ops();                                                                   \
-    } while (0)
+        g_ops = hip_stub_device_ops();
         EXPECT_REACHED(BOX(&G, p, 0, 3, i32));
         EXPECT_REACHED(BOX(&G, buf + 2, 65535, 65535, i32));                                    // an offset view
         EXPECT_REACHED(CAP(&G, p, 16, 0, -1, i32, i32, u32, u32, i32, i32, i32, ws, gws));
@@ -232,6 +195,5 @@ int main() {
         EXPECT_REACHED(AUTO(&G, p, p, u64p, i32, 16, 0, -1, i32, i32, i32, meta, u64p, ws, gws));
         EXPECT_REACHED(EXT(&G, p, meta, u64p, p, u64p, ws, pws));
     }
-    printf("abi_args_roi: %d calls, %d failures\n", g_n, g_fail);
-    return g_fail ? 1 : 0;
+    return abi_report("abi_args_roi");
 }

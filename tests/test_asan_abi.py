@@ -1,79 +1,74 @@
 """Host AddressSanitizer + UndefinedBehaviorSanitizer run of the C-ABI argument checking
-(SURVEY §5 "Host ASan on the C-ABI shim").
+(SURVEY §5 "Host ASan on the C-ABI shim"), one row per public header.
 
-The library's translation units are compiled host-only (`--offload-host-only`: no device
-code, so no GPU is needed and the build takes seconds) with -fsanitize=address,undefined,
-linked against tests/asan/hip_stubs.cpp (a stand-in HIP runtime whose device operations fail
-and are counted) and tests/asan/abi_args.cpp, which drives every codec_* entry of include/codec_tcc.h
-with NULL pointers, bad shapes, overflowing sizes and short workspaces.  Every call must
-return its negative status (or 0 bytes) with no sanitizer report.  GPU sanitizers are not
-available on this pool; this covers the host side only."""
+tests/asan_build.py compiles the library's translation units host-only (`--offload-host-only`:
+no device code, so no GPU is needed) with -fsanitize=address,undefined, once for the whole
+module, and links each header's stand-alone driver tests/asan/abi_args*.cpp against them and
+tests/asan/hip_stubs.cpp (a stand-in HIP runtime whose device operations fail and are counted).
+A driver calls every entry of its header with NULL pointers, bad shapes, overflowing sizes and
+short workspaces; every bad call must return its negative status (or 0 bytes) with no device
+operation and no sanitizer report.  GPU sanitizers are not available on this pool; this covers
+the host side only."""
 import os
 import re
 import subprocess
+from collections import namedtuple
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
-SAN = ["-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-fno-sanitize-recover=undefined"]
+import asan_build
+from asan_build import REPO
+
+# driver: tests/asan/<driver>.cpp; header: include/<header>; exports: the _lib list the header's
+# declarations must equal (None: not compared); floor: the least number of calls the driver makes;
+# n_declared: the header's entry count where it is pinned; asan_extra: further ASAN_OPTIONS
+Row = namedtuple("Row", "driver header exports floor n_declared asan_extra", defaults=(None, ""))
+ROWS = [
+    Row("abi_args", "codec_tcc.h", None, 301, asan_extra=":verify_asan_link_order=0"),   # more than 300 calls
+    Row("abi_args_ext", "codec_tcc_ext.h", None, 30),
+    Row("abi_args_crc", "codec_tcc_crc.h", "EXPORTS_CRC", 40),
+    Row("abi_args_vol", "codec_tcc_vol.h", "EXPORTS_VOL", 200),
+    Row("abi_args_gate", "codec_tcc_gate.h", "EXPORTS_GATE", 140),
+    Row("abi_args_gvol", "codec_tcc_gvol.h", "EXPORTS_GVOL", 150),
+    Row("abi_args_tile", "codec_tcc_tile.h", "EXPORTS_TILE", 140),
+    Row("abi_args_roi", "codec_tcc_roi.h", "EXPORTS_ROI", 170),
+    Row("abi_args_aead", "codec_tcc_aead.h", "EXPORTS_AEAD", 70, 6),
+    Row("abi_args_blind", "codec_tcc_blind.h", "EXPORTS_BLIND", 180, 5),
+]
+rows = pytest.mark.parametrize("row", ROWS, ids=[r.header[:-2] for r in ROWS])
 
 
-@pytest.fixture(scope="module")
-def abi_args_binary(tmp_path_factory):
-    if not os.path.exists(HIPCC):
+@rows
+def test_c_abi_rejects_bad_arguments_under_asan(row):
+    if not os.path.exists(asan_build.HIPCC):
         pytest.skip("hipcc not installed")
-    from codec_tcc_amd import build
-    out = tmp_path_factory.mktemp("asan")
-    objs = []
-    jobs = []
-    for src in build.SRCS:
-        obj = str(out / (os.path.basename(src) + ".o"))
-        cmd = [HIPCC, "-O1", "-g", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--offload-host-only", *SAN,
-               f"-I{build.INC}", "-c", src, "-o", obj]
-        jobs.append(subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-        objs.append(obj)
-    for p in jobs:
-        _o, err = p.communicate()
-        assert p.returncode == 0, err[-4000:]
-    # the host-only objects still name their (absent) code objects: give them empty ones
-    nm = subprocess.run(["nm", "-u", *objs], capture_output=True, text=True, check=True).stdout
-    fatbins = sorted(set(re.findall(r"\b(__hip_fatbin_[0-9a-f]+)\b", nm)))
-    dig = out / "digest.cpp"
-    dig.write_text('extern "C" const char* codec_build_digest(void) { return "asan-host-build"; }\n' +
-                   "".join(f'extern "C" {{ char {f}[64]; }}\n' for f in fatbins))
-    for src in (os.path.join(REPO, "tests", "asan", "abi_args.cpp"), os.path.join(REPO, "tests", "asan", "hip_stubs.cpp"),
-                str(dig)):
-        obj = str(out / (os.path.basename(src) + ".o"))
-        r = subprocess.run([HIPCC, "-O1", "-g", "-std=c++17", "--offload-arch=gfx950", "--offload-host-only", *SAN,
-                            f"-I{build.INC}", "-c", src, "-o", obj], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-4000:]
-        objs.append(obj)
-    exe = str(out / "abi_args")
-    # linked with clang++ against the stubs only (no libamdhip64, so no GPU runtime at all)
-    r = subprocess.run(["/opt/rocm/lib/llvm/bin/clang++", *SAN, *objs, "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    return exe
-
-
-def test_c_abi_rejects_bad_arguments_under_asan(abi_args_binary):
+    exe = asan_build.link_driver(row.driver + ".cpp")
     env = dict(os.environ,
-               ASAN_OPTIONS="detect_leaks=0:halt_on_error=1:verify_asan_link_order=0:abort_on_error=0",
+               ASAN_OPTIONS="detect_leaks=0:halt_on_error=1:abort_on_error=0" + row.asan_extra,
                UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1",
                HIP_VISIBLE_DEVICES="")
-    r = subprocess.run([abi_args_binary], capture_output=True, text=True, timeout=300, env=env)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
     report = r.stdout + r.stderr
     assert "AddressSanitizer" not in report and "runtime error" not in report, report[-6000:]
     assert r.returncode == 0, report[-6000:]
-    m = re.search(r"abi_args: (\d+) calls, 0 failures", r.stdout)
-    assert m and int(m.group(1)) > 300, report[-3000:]
+    m = re.search(rf"{row.driver}: (\d+) calls, 0 failures", r.stdout)
+    assert m and int(m.group(1)) >= row.floor, report[-3000:]
 
 
-def test_every_header_entry_is_driven():
-    """abi_args.cpp calls every function include/codec_tcc.h declares."""
-    hdr = open(os.path.join(REPO, "include", "codec_tcc.h")).read()
+@rows
+def test_every_header_entry_is_driven(row):
+    """The driver calls every function its header declares, and the header declares what
+    _lib exports for it."""
+    hdr = open(os.path.join(REPO, "include", row.header)).read()
     declared = set(re.findall(r"^\s*(?:int|size_t|const char\*)\s+(codec_\w+)\s*\(", hdr, re.M))
-    src = open(os.path.join(REPO, "tests", "asan", "abi_args.cpp")).read()
-    called = set(re.findall(r"\b(codec_\w+)\s*\(", src))
-    assert declared <= called, sorted(declared - called)
-
+    called = set(re.findall(r"\b(codec_\w+)\s*\(", open(os.path.join(asan_build.ASAN_DIR, row.driver + ".cpp")).read()))
+    from codec_tcc_amd import _lib
+    if row.exports:
+        assert declared == set(getattr(_lib, row.exports))
+    if row.n_declared:
+        assert len(declared) == row.n_declared
+    assert declared and declared <= called, sorted(declared - called)
+    if row.header == "codec_tcc_aead.h":
+        assert _lib.KERNEL_TAGS[47] == "k_chacha20_rows" and _lib.KERNEL_TAGS[51] == "k_aead_release"
+        assert "#define CODEC_K_CHACHA20_ROWS 47" in hdr and "#define CODEC_K_AEAD_RELEASE 51" in hdr
+        assert _lib.AEAD_CTX_BYTES == 48

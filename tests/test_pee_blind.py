@@ -13,6 +13,8 @@ import pee_covers as PC
 pytestmark = pytest.mark.gpu
 
 CASE = {c[0]: c for c in CS.CASES}
+# uint8 at a width that is no multiple of 8 (the scalar row pass of uint8); E and r are the spec's
+CASE["u8_w100"] = ("u8_w100", 64, 100, "uint8", 2, 2, 60, 2, 2)
 
 
 def _codec(B, H, W, dtype, T, maxval):
@@ -62,10 +64,10 @@ def _run(name, B, checksum=False):
 
 
 @pytest.mark.parametrize("B", [3, 9])
-@pytest.mark.parametrize("name", ["smooth", "planted1", "planted3", "wide_t2", "wide_t4", "odd", "u8"])
+@pytest.mark.parametrize("name", ["smooth", "planted1", "planted3", "wide_t2", "wide_t4", "odd", "u8", "u8_w100"])
 def test_gpu_blind_parity(name, B):
     """Stego and info bit for bit the spec's and the exact round trip, flat slots (B = 3) and lane
-    order (B = 9), both ROI route families (W % 8 == 0 and the odd 37 x 53) and uint8."""
+    order (B = 9), both ROI route families (W % 8 == 0 and the odd 37 x 53) and uint8 on both."""
     _n, _h, _w, _dt, _T, _k, _nu, E, r = CASE[name]
     _codec_, covers, bits, _stego = _run(name, B, checksum=name in ("planted3", "odd", "u8"))
     _st, info, p = BS.embed(covers[0], bits[0], _T, CS.top(_dt))

@@ -258,15 +258,24 @@ def test_gpu_roi_lookback_fallback(slots, monkeypatch):
 
 
 def test_gpu_roi_table_and_selection_match_spec():
+    """The table under rectangles on both routes of both pixel types: W % 8 == 0 (130x512, 64x96,
+    16x24) and not (37x53, 16x20), and every batch again as a view one pixel into its buffer (no
+    vector alignment: the scalar route whatever W is)."""
     torch = pytest.importorskip("torch")
     from codec_tcc_amd.pee import PeeCodec
+    u8 = [np.stack([synth.GENERATORS["u8"](16, w, 440 + i) for i in range(2)]) for w in (24, 20)]
     for covers, maxval in ((_ct12(4, 130, 512, 360), 4095), (_ct12(4, 37, 53, 363), 4095),
-                           (PC.batch(64, 96, "uint16", 4095, 2, 3), 4095)):
+                           (PC.batch(64, 96, "uint16", 4095, 2, 3), 4095), (u8[0], 255), (u8[1], 255)):
         B, H, W = covers.shape
         rects = _rects(covers, [2] * B, [NO_GATE] * B, maxval)
         codec = PeeCodec(B, H, W, dtype=str(covers.dtype), T=2, tmax=16, maxval=maxval)       # no gate: _table_workspace
         cov = torch.from_numpy(covers).cuda()
+        flat = torch.empty(B * H * W + 1, dtype=cov.dtype, device="cuda")
+        off = flat[1:].view(B, H, W)
+        off.copy_(cov)
         n, hs = codec.gate_table(cov, roi=rects)
+        n_off, hs_off = codec.gate_table(off, roi=rects)
+        assert torch.equal(n, n_off) and torch.equal(hs, hs_off)
         n, hs = n.cpu().numpy(), hs.cpu().numpy()
         for b, c in enumerate(covers):
             sn, sh = R.table(c, 16, rects[b], maxval)
