@@ -75,3 +75,107 @@ def case_cover(case) -> np.ndarray:
 
 def payload(n: int, seed: int) -> np.ndarray:
     return np.random.default_rng(4000 + seed).integers(0, 2, n).astype(np.uint8)
+
+
+# ---------------------------------------------------------------------------------------------
+# Shapes at which the kernels' loops run more than once (tests/test_pee_blind_shapes.py on the
+# GPU, tests/test_pee_blind_host.py spec against scalar restatement).  T = 4 for uint16 (maxval
+# 4095) and 2 for uint8 (maxval 255); the flat covers of "narrow" take T = 2 in both.
+def scattered(h: int, w: int, dtype, cells) -> np.ndarray:
+    """A smooth cover with the q-th candidate (i, j) of `cells` planted, alternately low and high."""
+    img = smooth(h, w, dtype)
+    for q, (i, j) in enumerate(cells):
+        plant(img, 2 * i + 1, 2 * j + 1, high=(q % 2 == 1))
+    return img
+
+
+def flat(h: int, w: int, dtype) -> np.ndarray:
+    """Mid-grey everywhere: every candidate is expandable and safe at any T."""
+    return np.full((h, w), (top(dtype) + 1) // 2, dtype=dtype)
+
+
+def many_cells(h: int, w: int, k: int = 300):
+    """k sorted picks (default_rng(11)) among the candidates with odd row and odd column number:
+    no planted cell touches another's context."""
+    L = [(i, j) for i in range(1, h // 2, 2) for j in range(1, w // 2, 2)]
+    return [L[q] for q in sorted(np.random.default_rng(11).choice(len(L), k, replace=False).tolist())]
+
+
+TALL_CELLS = ((5, 3), (260, 5), (300, 2), (520, 7), (530, 1))     # unsafe pixels in all three chunks of 256 rows
+WIDE_CELLS = ((0, 400), (2, 100), (3, 500), (4, 7))
+LONG_CELLS = ((3, 9), (100, 200), (200, 17))
+
+
+def _tall(cap):
+    return (cap, 55 * cap // 100, 0)
+
+
+def _wide(cap):
+    return (cap, cap // 2, 1)
+
+
+def _many(cap):
+    return (cap, cap // 2, 0)
+
+
+def _long(cap):
+    return (cap, 20000)
+
+
+def _edge(cap):
+    return (cap, cap + 1) if cap >= 0 else (0,)
+
+
+# (name, group, h, w, dtype, T, cells (None: the flat cover), lengths(capacity), max_entries, checksum)
+SHAPE_CASES = (
+    ("tall_vec_u16", "tall", 1100, 24, "uint16", 4, TALL_CELLS, _tall, 256, True),
+    ("tall_vec_u8", "tall", 1100, 24, "uint8", 2, TALL_CELLS, _tall, 256, False),
+    ("tall_scalar_u16", "tall", 1101, 22, "uint16", 4, TALL_CELLS, _tall, 256, False),
+    ("tall_scalar_u8", "tall", 1101, 22, "uint8", 2, TALL_CELLS, _tall, 256, True),
+    ("wide_vec_u16", "wide", 12, 1032, "uint16", 4, WIDE_CELLS, _wide, 256, False),
+    ("wide_vec_u8", "wide", 12, 1032, "uint8", 2, WIDE_CELLS, _wide, 256, True),
+    ("wide_scalar_u16", "wide", 13, 1030, "uint16", 4, WIDE_CELLS, _wide, 256, True),
+    ("wide_scalar_u8", "wide", 13, 1030, "uint8", 2, WIDE_CELLS, _wide, 256, False),
+    ("many_u16", "many", 300, 264, "uint16", 4, "many", _many, 65536, True),
+    ("many_u8", "many", 301, 262, "uint8", 2, "many", _many, 65536, False),
+    ("long_u16", "long", 512, 512, "uint16", 4, LONG_CELLS, _long, 256, True),
+    ("long_u8", "long", 512, 512, "uint8", 2, LONG_CELLS, _long, 256, False),
+    ("narrow_600x2", "narrow", 600, 2, "uint16", 2, None, _edge, 256, True),
+    ("narrow_601x3", "narrow", 601, 3, "uint8", 2, None, _edge, 256, False),
+    ("narrow_120x8", "narrow", 120, 8, "uint16", 2, None, _edge, 256, True),
+    ("narrow_121x9", "narrow", 121, 9, "uint8", 2, None, _edge, 256, False),
+    ("narrow_14x14", "narrow", 14, 14, "uint16", 2, None, _edge, 256, True),
+    ("narrow_28x14", "narrow", 28, 14, "uint16", 2, None, _edge, 256, False),
+    ("narrow_2x96", "narrow", 2, 96, "uint16", 2, None, _edge, 256, True),
+)
+SHAPE_CASE = {c[0]: c for c in SHAPE_CASES}
+# capacity at the case's max_entries, as the spec gives it on the recipes above (the issue's figures)
+SHAPE_CAPACITY = {"tall_vec_u16": 2906, "wide_vec_u16": 1914, "wide_scalar_u16": 1932, "many_u16": 1937, "long_u16": 41843,
+                  "narrow_600x2": 60, "narrow_601x3": 76, "narrow_120x8": 0, "narrow_121x9": 4, "narrow_14x14": -1,
+                  "narrow_28x14": -1, "narrow_2x96": -1}
+# (E, r) per embedded payload length, in the order of the case's lengths: the table of DESIGN §3k
+SHAPE_ER = {"tall_vec_u16": ((5, 8), (3, 6), (1, 5)), "tall_vec_u8": ((5, 8), (3, 6), (1, 5)),
+            "tall_scalar_u16": ((5, 8), (3, 7), (1, 6)), "tall_scalar_u8": ((5, 8), (3, 7), (1, 6)),
+            "wide_vec_u16": ((4, 1), (2, 1), (1, 1)), "wide_vec_u8": ((4, 1), (2, 1), (1, 1)),
+            "wide_scalar_u16": ((4, 1), (2, 1), (1, 1)), "wide_scalar_u8": ((4, 1), (2, 1), (1, 1)),
+            "many_u16": ((271, 17), (172, 11), (4, 1)), "many_u8": ((166, 11), (119, 8), (40, 3)),
+            "long_u16": ((19, 1), (18, 1)), "long_u8": ((156, 6), (155, 6)),
+            "narrow_600x2": ((0, 48),), "narrow_601x3": ((0, 32),), "narrow_120x8": ((0, 12),), "narrow_121x9": ((0, 11),),
+            "narrow_14x14": (), "narrow_28x14": (), "narrow_2x96": ()}
+
+_made = {}
+
+
+def shape_case(name: str):
+    """(cover, T, maxval, max_entries, checksum, lengths, capacity) of a SHAPE_CASES entry; the cover
+    is built once and is read-only."""
+    if name not in _made:
+        _n, _g, h, w, dtype, T, cells, lengths, me, checksum = SHAPE_CASE[name]
+        if cells is None:
+            img = flat(h, w, dtype)
+        else:
+            img = scattered(h, w, dtype, many_cells(h, w) if cells == "many" else cells)
+        img.setflags(write=False)
+        cap = BS.capacity(img, T, top(dtype), me)
+        _made[name] = (img, T, top(dtype), me, checksum, tuple(lengths(cap)), cap)
+    return _made[name]

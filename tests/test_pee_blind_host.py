@@ -89,6 +89,41 @@ def test_spec_matches_scalar_restatement(case):
         assert h2 == (hdr["T"], hdr["flags"], hdr["maxval"], hdr["n_user"], hdr["E"], hdr["end"], hdr["crc"])
 
 
+@pytest.mark.parametrize("name", [c[0] for c in CS.SHAPE_CASES])
+def test_spec_matches_scalar_restatement_shapes(name):
+    """The same on every cover and payload length of tests/test_pee_blind_shapes.py (tall, wide,
+    many-entry, long-payload and narrow slices): stego, info and both decodes of the two
+    statements agree, the capacity is the scalar plan's boundary and the figures DESIGN §3k
+    quotes, so the spec is pinned at these shapes without a GPU."""
+    img, T, mv, me, checksum, lengths, cap = CS.shape_case(name)
+    rows = img.astype(np.int64).tolist()
+    if name in CS.SHAPE_CAPACITY:
+        assert cap == CS.SHAPE_CAPACITY[name]
+    assert cap < 0 or SC.plan(rows, cap, T, mv, me)[0] == 0
+    assert SC.plan(rows, cap + 1, T, mv, me)[0] in (1, 2)
+    table = []
+    for q, n in enumerate(lengths):
+        bits = CS.payload(n, q + 1)
+        st, info, p = BS.embed(img, bits, T, mv, checksum, me)
+        assert (info[0] == 0) == (n <= cap)
+        if info[0] == 0:
+            table.append((info[2], p["r"]))
+        s2, i2 = SC.embed(rows, bits.tolist(), T, mv, img.dtype.itemsize, checksum, me)
+        assert tuple(i2) == tuple(info)
+        np.testing.assert_array_equal(np.asarray(s2), st)
+        if info[0]:
+            np.testing.assert_array_equal(st, img)
+            continue
+        assert info[5] == 2 * (img.shape[0] // 2 - p["r"]) and info[3] == 192 + 32 * info[2]
+        g2, c2, h2 = SC.decode(st.astype(np.int64).tolist())
+        got, cov, hdr = BS.decode(st)
+        assert g2 == bits.tolist() == got.tolist()
+        np.testing.assert_array_equal(np.asarray(c2), img)
+        np.testing.assert_array_equal(cov, img)
+        assert h2 == (hdr["T"], hdr["flags"], hdr["maxval"], hdr["n_user"], hdr["E"], hdr["end"], hdr["crc"])
+    assert tuple(table) == CS.SHAPE_ER[name]   # the table of DESIGN §3k
+
+
 @pytest.mark.parametrize("case", CS.CASES, ids=[c[0] for c in CS.CASES])
 def test_capacity_is_the_boundary_of_fits(case):
     _name, _h, _w, dtype, T, _k, _n, _E, _r = case
