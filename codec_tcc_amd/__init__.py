@@ -12,10 +12,11 @@ Reference drop-ins (numpy in/out):    codec_tcc_amd.api (same names as src/codec
 from .codec import Codec, Encoded, Payloads, decode, decode_ref_compat, encode, make_payloads, meta_dict, meta_records
 from .framing import distribute_message_segments, message_to_bits
 from .checksum import IntegrityError, crc32_slices
-from .pee import PeeCodec, PeeEncoded, PeeVolume, decode_blind, decode_volume, encode_blind, encode_volume
+from .pee import (PeeCodec, PeeEncoded, PeeVolume, decode_blind, decode_volume, encode_blind, encode_blind_auto,
+                  encode_volume)
 
 __all__ = [
-    "encode_blind", "decode_blind",
+    "encode_blind", "encode_blind_auto", "decode_blind",
     "Codec", "Encoded", "Payloads", "encode", "decode", "decode_ref_compat", "make_payloads",
     "meta_records", "meta_dict", "message_to_bits", "distribute_message_segments", "PeeCodec", "PeeEncoded",
     "crc32_slices", "IntegrityError", "PeeVolume", "encode_volume", "decode_volume",

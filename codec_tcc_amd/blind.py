@@ -11,6 +11,11 @@ words, then the E location-map entries.  Those pixels lie in a region the ROI em
 the PEE payload.  The plan -- which rows the payload needs, hence E and the region -- is computed
 on the device from the cover alone (tests/pee_blind_spec.py is the specification).
 
+Capacity control (include/codec_tcc_blind_auto.h): embed_auto picks, per slice and on
+the device, the smallest T in 1..tmax whose plan succeeds; the format and the decode are the same.
+
+    stego, info, ts = codec.embed_blind_auto(covers, payloads, tmax=8)
+
 parse_header, check_args and the geometry helpers are pure host code: no GPU, no library load.
 """
 from __future__ import annotations
@@ -29,6 +34,7 @@ NO_ENTRY = 0xFFFFFFFF
 FLAG_CRC = _lib.BLIND_FLAG_CRC
 MAX_ENTRIES = _lib.BLIND_MAX_ENTRIES
 MAX_DIM = _lib.ROI_MAX_DIM
+TMAX = _lib.BLIND_TMAX
 INFO_FIELDS = ("status", "n_user", "E", "n_side", "end", "region_row")
 STATUS_TEXT = {1: "the payload and its side bits exceed the slice's capacity",
                2: "more location-map entries than max_entries"}
@@ -76,6 +82,16 @@ def check_args(*, scheme: int, T, gate, H: int, W: int, maxval: int, max_entries
         raise ValueError(f"max_entries must be an integer in 0..{MAX_ENTRIES}, got {max_entries!r}")
     if in_place:
         raise ValueError("blind MED-PEE embeds out of place only: pass a stego buffer other than the covers")
+
+
+def check_args_auto(*, scheme: int, tmax, gate, H: int, W: int, maxval: int, max_entries: int = 256, roi=None, key=None,
+                    in_place: bool = False) -> None:
+    """check_args for the calls that choose T: the same rules in the same order, with tmax in
+    1..16 in T's place."""
+    if int(scheme) == 1 and (isinstance(tmax, (bool, str)) or int(tmax) != tmax or not 1 <= int(tmax) <= TMAX):
+        raise ValueError(f"blind MED-PEE chooses T in 1..tmax with tmax an integer in 1..{TMAX}, got {tmax!r}")
+    check_args(scheme=scheme, T=1, gate=gate, H=H, W=W, maxval=maxval, max_entries=max_entries, roi=roi, key=key,
+               in_place=in_place)
 
 
 def parse_header(words, H: int, W: int, vmax: int) -> Dict:
@@ -175,18 +191,24 @@ def raise_status(status, what: str = "embed_blind") -> None:
 
 
 # ---------------------------------------------------------------- the device side (PeeCodec's methods call these)
-def _workspace(codec, pw: int, max_entries: int):
+def _workspace(codec, pw: int, max_entries: int, tmax: int = 0):
     """The blind workspace for rows of pw words: a codec_pee workspace with the plan's arrays, a
-    map and the rows behind it, zeroed once (codec_pee_reset) and kept (the last few)."""
+    map and the rows behind it, zeroed once (codec_pee_reset) and kept (the last few).  tmax > 0:
+    the workspace of the calls that choose T, with a row table for every T in 1..tmax."""
     from collections import OrderedDict
     from .codec import _stream, _torch
     cache = codec.__dict__.setdefault("_ws_blind", OrderedDict())
-    key = (int(pw), int(max_entries))
+    key = (int(pw), int(max_entries), int(tmax))
     if key not in cache:
-        P = codec._params(pw)
-        n = int(_lib.load().codec_pee_blind_workspace_bytes(C.byref(P), int(max_entries)))
+        P = _params_auto(codec, pw) if tmax else codec._params(pw)
+        if tmax:
+            fn = "codec_pee_blind_auto_workspace_bytes"
+            n = int(_lib.load().codec_pee_blind_auto_workspace_bytes(C.byref(P), int(tmax), int(max_entries)))
+        else:
+            fn = "codec_pee_blind_workspace_bytes"
+            n = int(_lib.load().codec_pee_blind_workspace_bytes(C.byref(P), int(max_entries)))
         if n == 0:
-            _lib.check(-1, "codec_pee_blind_workspace_bytes")
+            _lib.check(-1, fn)
         ws = _torch().empty(n, dtype=_torch().uint8, device=codec.device)
         _lib.check(_lib.load().codec_pee_reset(C.byref(P), ws.data_ptr(), ws.numel(), _stream()), "codec_pee_reset")
         cache[key] = ws
@@ -194,6 +216,13 @@ def _workspace(codec, pw: int, max_entries: int):
             cache.popitem(last=False)
     cache.move_to_end(key)
     return cache[key]
+
+
+def _params_auto(codec, pw: int):
+    """The codec's parameters with T = 1: the calls that choose T only range-check it."""
+    P = codec._params(pw)
+    P.T = 1
+    return P
 
 
 def _guarded(codec, ws, pw: int, fn):
@@ -312,3 +341,63 @@ def decode(codec, stego, *, cover=None, verify=True):
         _ck.raise_mismatch([b for b in flagged if b in bad], [], "blind MED-PEE decode", rows=host)
     n_user = heads["n_user"].tolist()
     return [framing.unpack_bits(host[b], n_user[b]) for b in range(codec.B)], cover
+
+
+# ---------------------------------------------------------------- capacity control: T chosen per slice
+def _auto_args(codec, tmax, max_entries: int = 256, in_place: bool = False) -> int:
+    tmax = codec.tmax if tmax is None else tmax
+    check_args_auto(scheme=codec.scheme, tmax=tmax, gate=codec.gate, H=codec.H, W=codec.W, maxval=codec.maxval,
+                    max_entries=max_entries, in_place=in_place)
+    return int(tmax)
+
+
+def embed_auto(codec, covers, payloads, *, tmax=None, stego=None, packed=None, checksum=False, max_entries: int = 256,
+               check: bool = True):
+    from . import checksum as _ck
+    from .codec import _stream, _torch
+    from .pee_checks import check_buffers
+    torch = _torch()
+    if checksum not in (False, True):
+        raise ValueError("embed_blind_auto takes checksum=True or False (the header holds the cover's CRC-32 alone)")
+    tmax = _auto_args(codec, tmax, max_entries)
+    check_buffers(codec.device, codec.B, codec.H, codec.W, codec.bytes, lm_words=codec.lm_words, scheme=1,
+                  covers=covers, stego=stego, packed=packed)
+    _auto_args(codec, tmax, max_entries, in_place=stego is not None and stego.data_ptr() == covers.data_ptr())
+    words, lengths, lens_t = packed if packed is not None else codec.pack_payloads(payloads)
+    n_max = max([int(n) for n in lengths] + [0])
+    if n_max > 64 * int(words.shape[1]):
+        raise ValueError(f"a payload of {n_max} bits does not fit the packed rows' {64 * int(words.shape[1])}")
+    pw = row_words(n_max, max_entries)
+    crc = _ck.crc32_slices(covers) if checksum else None   # queued first, as embed_blind does
+    if stego is None:
+        stego = torch.empty_like(covers)
+    ws = _workspace(codec, pw, max_entries, tmax)
+    info = torch.empty((codec.B, _lib.BLIND_INFO_WORDS), dtype=torch.int32, device=codec.device)
+    ts = torch.empty((codec.B,), dtype=torch.int32, device=codec.device)
+    lm = torch.empty((codec.B, codec.lm_words), dtype=torch.int64, device=codec.device)
+    meta = torch.empty((codec.B, _lib.PEE_META_BYTES), dtype=torch.uint8, device=codec.device)
+    P = _params_auto(codec, pw)
+    _guarded(codec, ws, pw, lambda: _lib.check(_lib.load().codec_pee_blind_embed_auto(
+        C.byref(P), covers.data_ptr(), stego.data_ptr(), words.data_ptr(), int(words.shape[1]), lens_t.data_ptr(),
+        None if crc is None else crc.data_ptr(), tmax, int(max_entries), info.data_ptr(), ts.data_ptr(), meta.data_ptr(),
+        lm.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "codec_pee_blind_embed_auto"))
+    out = info[:, :len(INFO_FIELDS)]
+    if check:
+        raise_status(out[:, 0].cpu().tolist(), "embed_blind_auto")   # one read-back
+    return stego, out, ts
+
+
+def capacity_curve(codec, covers, tmax=None, max_entries: int = 256):
+    from .codec import _stream, _torch
+    torch = _torch()
+    tmax = _auto_args(codec, tmax, max_entries)
+    codec._check_buffers(covers=covers)
+    pw = row_words(0, max_entries)
+    ws = _workspace(codec, pw, max_entries, tmax)
+    info = torch.empty((codec.B, _lib.BLIND_INFO_WORDS), dtype=torch.int32, device=codec.device)
+    ts = torch.empty((codec.B,), dtype=torch.int32, device=codec.device)
+    curve = torch.empty((codec.B, tmax), dtype=torch.int32, device=codec.device)
+    _guarded(codec, ws, pw, lambda: _lib.check(_lib.load().codec_pee_blind_plan_auto(
+        C.byref(_params_auto(codec, pw)), covers.data_ptr(), None, tmax, int(max_entries), info.data_ptr(), ts.data_ptr(),
+        curve.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "codec_pee_blind_plan_auto"))
+    return curve

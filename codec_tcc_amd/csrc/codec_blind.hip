@@ -19,9 +19,19 @@
 // Decode: k_blind_headers (side words 0..5 of every slice, read back once by the host layer),
 // then k_blind_zero + k_blind_scatter (entries -> map), codec_pee_roi_extract, k_blind_restore
 // (the first n_side extracted bits back into the LSBs, the user bits shifted down).
+// Capacity control (include/codec_tcc_blind_auto.h; tests/pee_blind_auto_spec.py): the
+// smallest T in 1..tmax whose plan succeeds, per slice, on the device:
+//   k_blind_rows_auto  the same pass for every T in 1..16 at once: one classification per candidate
+//                    gives its counts at all T as sixteen 4-bit fields of two 64-bit words, summed
+//                    per item, widened to bytes and to 16-bit fields in registers, reduced with
+//                    shuffles; table [B][tmax][hc].  The cover is read once.
+//   k_blind_plan_auto  one workgroup per slice, one wave per T: k_blind_plan's rule with wave scans, the
+//                    first T with status 0 (or tmax's refusal), the capacity curve.
+// k_blind_splice, the ROI embed and k_blind_pack then run as for a fixed T, on the per-slice T array.
 // Every kernel clamps what it reads from device memory to the slice, the row and the map.
 #include "codec_common.h"
 #include "codec_tcc_blind.h"
+#include "codec_tcc_blind_auto.h"
 
 #include <limits.h>
 
@@ -36,12 +46,13 @@
 struct BlWs {
     size_t rows, rect, lens, ts, gs, lm, pay, total;
 };
-// the layout behind the codec_pee workspace of P (base = codec_pee_workspace_bytes(P) > 0)
-static BlWs bl_ws(const codec_pee_params* P, size_t base) {
+// the layout behind the codec_pee workspace of P (base = codec_pee_workspace_bytes(P) > 0); the row
+// table holds `tables` T's
+static BlWs bl_ws(const codec_pee_params* P, size_t base, int tables = 1) {
     BlWs L;
     const size_t B = (size_t)P->B;
     size_t o = align_up(base, 256);
-    L.rows = o; o += align_up(B * (size_t)(P->H / 2 > 0 ? P->H / 2 : 1) * 8, 256);
+    L.rows = o; o += align_up(B * (size_t)tables * (size_t)(P->H / 2 > 0 ? P->H / 2 : 1) * 8, 256);
     L.rect = o; o += align_up(B * 16, 256);
     L.lens = o; o += align_up(B * 4, 256);
     L.ts = o; o += align_up(B * 4, 256);
@@ -137,6 +148,254 @@ __global__ __launch_bounds__(256) void k_blind_rows(const T* __restrict__ img, i
     }
 }
 
+// ---- every T in 1..16 from one classification.  A count "for every T > a" is the 64-bit word
+// BL_ONES << 4 a: one 4-bit field per T (field T - 1), so that a few candidates add up in place.
+#define BL_ONES 0x1111111111111111ull
+#define BL_EVEN 0x0F0F0F0F0F0F0F0Full
+#define BL_LOW 0x00FF00FF00FF00FFull
+#define BL_WIDEN_ITEMS 60   // adds of at most 4 per field before the byte fields are widened: 240 < 256
+
+__device__ __forceinline__ u64 bl_above(int a) { return a < 16 ? BL_ONES << (4 * a) : 0ull; }
+
+// bl_class closed over T: with u = e for e >= 0 and -e - 1 otherwise, the candidate expands iff
+// u < T; it is then safe iff ok (no T in that), and otherwise safe iff T <= d, the room towards the
+// end of the range it is shifted to.  So: expandable and safe for T > u if ok; unsafe for T > u if
+// not ok, and for d < T <= u.
+__device__ __forceinline__ void bl_class_all(int x, int a, int b, int c, int maxval, u64& es, u64& un) {
+    const int p = bl_med3(a, b, c), e = x - p;
+    const int u = e >= 0 ? e : -e - 1;
+    const bool ok = (p + 2 * e >= 0) & (p + 2 * e + 1 <= maxval);
+    const int d = max(e >= 0 ? maxval - x : x, 0);
+    const u64 nu = bl_above(u);
+    es += ok ? nu : 0ull;
+    un += (ok ? 0ull : nu) + (d < u ? bl_above(d) - nu : 0ull);   // bl_above(u) is a subset of bl_above(d): no borrow
+}
+
+// a lane's counts of one candidate row: [0] expandable and safe, [1] unsafe.  by: byte fields,
+// [..][0] of T - 1 = 0, 2, .., 14 and [..][1] of 1, 3, .., 15; hf: 16-bit fields, [..][q] of
+// T - 1 = BL_HF_FIRST(q) + 4 j in field j.  A lane sees at most 512 candidates of a row.
+#define BL_HF_FIRST(q) ((q) == 0 ? 0 : (q) == 1 ? 2 : (q) == 2 ? 1 : 3)
+struct BlAcc {
+    u64 by[2][2], hf[2][4];
+    __device__ __forceinline__ void zero() {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            by[k][0] = by[k][1] = 0ull;
+            hf[k][0] = hf[k][1] = hf[k][2] = hf[k][3] = 0ull;
+        }
+    }
+    // es / un: 4-bit fields of at most 4 each
+    __device__ __forceinline__ void add(u64 es, u64 un) {
+        by[0][0] += es & BL_EVEN; by[0][1] += (es >> 4) & BL_EVEN;
+        by[1][0] += un & BL_EVEN; by[1][1] += (un >> 4) & BL_EVEN;
+    }
+    __device__ __forceinline__ void widen() {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            hf[k][0] += by[k][0] & BL_LOW; hf[k][1] += (by[k][0] >> 8) & BL_LOW;
+            hf[k][2] += by[k][1] & BL_LOW; hf[k][3] += (by[k][1] >> 8) & BL_LOW;
+            by[k][0] = by[k][1] = 0ull;
+        }
+    }
+    // the wave's sums in every lane: a row has at most 32767 candidates, so no field carries
+    __device__ __forceinline__ void reduce() {
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                uint32_t lo = (uint32_t)hf[k][q], hi = (uint32_t)(hf[k][q] >> 32);
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) {
+                    lo += __shfl_xor(lo, o, 64);
+                    hi += __shfl_xor(hi, o, 64);
+                }
+                hf[k][q] = ((u64)hi << 32) | lo;
+            }
+    }
+    // the count of kind k at T = t + 1, t in 0..15
+    __device__ __forceinline__ uint32_t at(int k, int t) const {
+        const int q = t & 3;
+        const u64 w = q == 0 ? hf[k][0] : q == 2 ? hf[k][1] : q == 1 ? hf[k][2] : hf[k][3];
+        return (uint32_t)(w >> (16 * (t >> 2))) & 0xFFFFu;
+    }
+};
+
+// grid and waves as k_blind_rows; a wave takes its candidate rows one after the other, so that a
+// row's counts at all T stay in one set of registers.  rows_out: [B][tmax][hc], tmax in 1..16.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void k_blind_rows_auto(const T* __restrict__ img, int H, int W, int maxval, int tmax,
+                                                         uint2* __restrict__ rows_out) {
+    typedef typename Vec8<T>::type V;
+    const int b = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int hc = H / 2;
+    const int i0 = (int)blockIdx.x * BL_ROWS_PER_WG + wv * BL_ROWS_PER_WAVE;
+    if (i0 >= hc) return;   // uniform per wave; no barrier below
+    const int nrows = min(BL_ROWS_PER_WAVE, hc - i0);
+    const T* src = img + (size_t)b * H * W;
+    for (int k = 0; k < nrows; ++k) {
+        BlAcc acc;
+        acc.zero();
+        int since = 0;
+        if constexpr (VEC) {
+            const uint32_t CR = (uint32_t)W / 8;
+            const T* r0 = src + (size_t)(2 * (i0 + k)) * W;
+            for (uint32_t t = (uint32_t)lane; t < CR; t += 64u * BL_U) {
+                V v0[BL_U], v1[BL_U];
+                bool in[BL_U];
+#pragma unroll
+                for (int u = 0; u < BL_U; ++u) {
+                    const uint32_t tu = t + 64u * u;
+                    in[u] = tu < CR;
+                    const size_t o0 = (size_t)(in[u] ? tu : CR - 1u) * 8;   // clamped: a valid address
+                    v0[u] = *reinterpret_cast<const V*>(r0 + o0);
+                    v1[u] = *reinterpret_cast<const V*>(r0 + o0 + W);
+                }
+#pragma unroll
+                for (int u = 0; u < BL_U; ++u) {
+                    u64 es = 0ull, un = 0ull;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        bl_class_all((int)bl_px(v1[u], 2 * q + 1), (int)bl_px(v1[u], 2 * q), (int)bl_px(v0[u], 2 * q + 1),
+                                     (int)bl_px(v0[u], 2 * q), maxval, es, un);
+                    acc.add(in[u] ? es : 0ull, in[u] ? un : 0ull);
+                }
+                since += BL_U;
+                if (since + BL_U > BL_WIDEN_ITEMS) { acc.widen(); since = 0; }
+            }
+        } else {
+            const uint32_t wc = (uint32_t)W / 2;
+            const size_t y = 2 * (size_t)(i0 + k) + 1;
+            for (uint32_t j = (uint32_t)lane; j < wc; j += 64u) {
+                const size_t x = 2 * (size_t)j + 1;
+                u64 es = 0ull, un = 0ull;
+                bl_class_all((int)src[y * W + x], (int)src[y * W + x - 1], (int)src[(y - 1) * W + x],
+                             (int)src[(y - 1) * W + x - 1], maxval, es, un);
+                acc.add(es, un);
+                if (++since == BL_WIDEN_ITEMS) { acc.widen(); since = 0; }
+            }
+        }
+        acc.widen();
+        acc.reduce();
+        if (lane < tmax) rows_out[((size_t)b * tmax + lane) * hc + i0 + k] = make_uint2(acc.at(0, lane), acc.at(1, lane));
+    }
+}
+
+// the plan of one slice at one T
+struct BlPlan {
+    int status, E, n_side, istar, y0, cap;
+};
+
+// one row of the plan rule: the row's counts through row i -> (side bits, room for user bits, rows reserved)
+struct BlRow {
+    long long side, room, rr;
+};
+__device__ __forceinline__ BlRow bl_plan_row(uint32_t cap, uint32_t uns, int W) {
+    BlRow r;
+    r.side = BL_HDR_BITS + 32LL * uns;
+    r.room = (long long)cap - r.side;
+    r.rr = (r.side + 2LL * W - 1) / (2LL * W);
+    return r;
+}
+// the largest n_user the row would take, or -1
+__device__ __forceinline__ int bl_plan_cap(const BlRow& r, int i, uint32_t uns, int hc, int max_entries, long long row_bits) {
+    return (i < hc - r.rr && uns <= (uint32_t)max_entries && r.side <= row_bits && r.room >= 0)
+               ? (int)min(r.room, row_bits - r.side) : -1;
+}
+// the plan from the first row that has room (first = row << 32 | unsafe through it, or ~0) and the capacity
+__device__ BlPlan bl_plan_decide(u64 first, int cap, int hc, long long n_user, int W, int max_entries, long long row_bits) {
+    BlPlan p = {0, 0, 0, -1, 0, cap};
+    if (first == ~0ull) {
+        p.status = 1;
+    } else {
+        p.istar = (int)(first >> 32);
+        const long long e = (long long)(first & 0xFFFFFFFFull);
+        const long long side = BL_HDR_BITS + 32 * e;
+        const long long rr = (side + 2LL * W - 1) / (2LL * W);
+        p.E = (int)min(e, (long long)INT_MAX);
+        if (p.istar >= hc - rr) p.status = 1;
+        else if (e > max_entries) p.status = 2;
+        else if (side + n_user > row_bits) p.status = 1;   // a row narrower than the call's lengths: the host sizes it
+        else { p.n_side = (int)side; p.y0 = 2 * (hc - (int)rr); }
+    }
+    return p;
+}
+
+// the plan rule over one slice's row table at one T (rows: its hc entries), by all 256 threads of a
+// workgroup, every one of which gets the result.  An entry is clamped to the row's W / 2 candidates.
+__device__ BlPlan bl_plan_rows(const uint2* __restrict__ rows, int hc, long long n_user, int W, int max_entries,
+                               long long row_bits, uint32_t* sh, u64* s_first, int* s_cap) {
+    const int tid = threadIdx.x;
+    const uint32_t wc = (uint32_t)W / 2;
+    if (tid == 0) { *s_first = ~0ull; *s_cap = -1; }
+    __syncthreads();
+    uint32_t cap0 = 0, uns0 = 0;
+    for (int c0 = 0; c0 < hc; c0 += 256) {
+        const int i = c0 + tid;
+        uint2 v = i < hc ? rows[i] : make_uint2(0u, 0u);
+        v.x = min(v.x, wc);
+        v.y = min(v.y, wc);
+        uint32_t tc, tu;
+        const uint32_t cap = cap0 + block_excl_scan<256>(v.x, sh, &tc) + v.x;   // through row i
+        const uint32_t uns = uns0 + block_excl_scan<256>(v.y, sh, &tu) + v.y;
+        if (i < hc) {
+            const BlRow r = bl_plan_row(cap, uns, W);
+            const int c = bl_plan_cap(r, i, uns, hc, max_entries, row_bits);
+            if (c >= 0) atomicMax(s_cap, c);
+            if (r.room >= n_user) atomicMin(s_first, ((u64)(uint32_t)i << 32) | uns);
+        }
+        cap0 += tc;
+        uns0 += tu;
+    }
+    __syncthreads();
+    return bl_plan_decide(*s_first, *s_cap, hc, n_user, W, max_entries, row_bits);
+}
+
+// the same by one wave, with shuffles alone: no shared memory, no barrier
+__device__ BlPlan bl_plan_rows_wave(const uint2* __restrict__ rows, int hc, long long n_user, int W, int max_entries,
+                                    long long row_bits) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t wc = (uint32_t)W / 2;
+    uint32_t cap0 = 0, uns0 = 0;
+    int best = -1;
+    u64 first = ~0ull;
+    for (int c0 = 0; c0 < hc; c0 += 64) {
+        const int i = c0 + lane;
+        uint2 v = i < hc ? rows[i] : make_uint2(0u, 0u);
+        v.x = min(v.x, wc);
+        v.y = min(v.y, wc);
+        const uint32_t cap = cap0 + wave_incl_scan(v.x), uns = uns0 + wave_incl_scan(v.y);   // through row i
+        bool hit = false;
+        if (i < hc) {
+            const BlRow r = bl_plan_row(cap, uns, W);
+            best = max(best, bl_plan_cap(r, i, uns, hc, max_entries, row_bits));
+            hit = r.room >= n_user;
+        }
+        const u64 hits = __ballot(hit);
+        if (first == ~0ull && hits) {   // uniform: the first row with room, and the unsafe count through it
+            const int l = __ffsll((long long)hits) - 1;
+            first = ((u64)(uint32_t)(c0 + l) << 32) | (uint32_t)__shfl(uns, l, 64);
+        }
+        cap0 = (uint32_t)__shfl(cap, 63, 64);
+        uns0 = (uint32_t)__shfl(uns, 63, 64);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) best = max(best, __shfl_xor(best, o, 64));
+    return bl_plan_decide(first, best, hc, n_user, W, max_entries, row_bits);
+}
+
+// info and the ROI embed's arrays of slice b (one thread); thr: the T the ROI embed and the header take
+__device__ void bl_plan_write(int b, const BlPlan& p, long long n_user, int thr, int cap, int H, int W,
+                              int32_t* __restrict__ info, int32_t* __restrict__ rect, int32_t* __restrict__ lens,
+                              int32_t* __restrict__ ts, int32_t* __restrict__ gs) {
+    int32_t* I = info + (size_t)b * CODEC_PEE_BLIND_INFO_WORDS;
+    I[0] = p.status; I[1] = (int)n_user; I[2] = p.E; I[3] = p.n_side; I[4] = -1; I[5] = p.y0; I[6] = p.istar; I[7] = cap;
+    const bool ok = p.status == 0;
+    rect[4 * b] = ok ? p.y0 : 0; rect[4 * b + 1] = 0; rect[4 * b + 2] = ok ? H : 0; rect[4 * b + 3] = ok ? W : 0;
+    lens[b] = ok ? p.n_side + (int)n_user : 0;
+    ts[b] = thr;
+    gs[b] = CODEC_PEE_GATE_MAX;
+}
+
 // one workgroup per slice.  lengths NULL: 0 user bits each; a length is clamped to 0 .. user_bits.
 __global__ __launch_bounds__(256) void k_blind_plan(const uint2* __restrict__ rows, const int32_t* __restrict__ lengths,
                                                     int user_bits, int H, int W, int thr, int max_entries,
@@ -146,52 +405,40 @@ __global__ __launch_bounds__(256) void k_blind_plan(const uint2* __restrict__ ro
     __shared__ uint32_t sh[256 / 64 + 1];
     __shared__ u64 s_first;
     __shared__ int s_cap;
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int b = blockIdx.x;
     const int hc = H / 2;
     const long long n_user = lengths ? (long long)min(max(lengths[b], 0), user_bits) : 0;
-    if (tid == 0) { s_first = ~0ull; s_cap = -1; }
-    __syncthreads();
-    uint32_t cap0 = 0, uns0 = 0;
-    for (int c0 = 0; c0 < hc; c0 += 256) {
-        const int i = c0 + tid;
-        const uint2 v = i < hc ? rows[(size_t)b * hc + i] : make_uint2(0u, 0u);
-        uint32_t tc, tu;
-        const uint32_t cap = cap0 + block_excl_scan<256>(v.x, sh, &tc) + v.x;   // through row i
-        const uint32_t uns = uns0 + block_excl_scan<256>(v.y, sh, &tu) + v.y;
-        if (i < hc) {
-            const long long side = BL_HDR_BITS + 32LL * uns;
-            const long long room = (long long)cap - side;
-            const long long rr = (side + 2LL * W - 1) / (2LL * W);
-            if (i < hc - rr && uns <= (uint32_t)max_entries && side <= row_bits && room >= 0)
-                atomicMax(&s_cap, (int)min(room, row_bits - side));
-            if (room >= n_user) atomicMin(&s_first, ((u64)(uint32_t)i << 32) | uns);
-        }
-        cap0 += tc;
-        uns0 += tu;
+    const BlPlan p = bl_plan_rows(rows + (size_t)b * hc, hc, n_user, W, max_entries, row_bits, sh, &s_first, &s_cap);
+    if (threadIdx.x == 0) bl_plan_write(b, p, n_user, thr, p.cap, H, W, info, rect, lens, ts, gs);
+}
+
+// one workgroup of sixteen waves per slice, wave T - 1 the plan at T over its part of the table
+// [B][tmax][hc].  The slice takes the first T whose plan has status 0, else the refusal of tmax
+// (t_out 0); info's last word is the largest capacity over the T's, curve (or NULL) [B][tmax] holds each.
+__global__ __launch_bounds__(64 * CODEC_PEE_BLIND_TMAX) void k_blind_plan_auto(
+    const uint2* __restrict__ rows, const int32_t* __restrict__ lengths, int user_bits, int H, int W, int tmax,
+    int max_entries, long long row_bits, int32_t* __restrict__ info, int32_t* __restrict__ t_out,
+    int32_t* __restrict__ curve, int32_t* __restrict__ rect, int32_t* __restrict__ lens, int32_t* __restrict__ ts,
+    int32_t* __restrict__ gs) {
+    __shared__ BlPlan s_plan[CODEC_PEE_BLIND_TMAX];
+    const int b = blockIdx.x, wv = threadIdx.x >> 6;
+    const int hc = H / 2;
+    const long long n_user = lengths ? (long long)min(max(lengths[b], 0), user_bits) : 0;
+    tmax = min(max(tmax, 1), CODEC_PEE_BLIND_TMAX);
+    if (wv < tmax) {
+        const BlPlan p = bl_plan_rows_wave(rows + ((size_t)b * tmax + wv) * hc, hc, n_user, W, max_entries, row_bits);
+        if ((threadIdx.x & 63) == 0) s_plan[wv] = p;
     }
     __syncthreads();
-    if (tid != 0) return;
-    int status = 0, E = 0, n_side = 0, istar = -1, y0 = 0;
-    if (s_first == ~0ull) {
-        status = 1;
-    } else {
-        istar = (int)(s_first >> 32);
-        const long long e = (long long)(s_first & 0xFFFFFFFFull);
-        const long long side = BL_HDR_BITS + 32 * e;
-        const long long rr = (side + 2LL * W - 1) / (2LL * W);
-        E = (int)min(e, (long long)INT_MAX);
-        if (istar >= hc - rr) status = 1;
-        else if (e > max_entries) status = 2;
-        else if (side + n_user > row_bits) status = 1;   // a row narrower than the call's lengths: the host sizes it
-        else { n_side = (int)side; y0 = 2 * (hc - (int)rr); }
+    if (threadIdx.x != 0) return;
+    int tstar = 0, cap = -1;
+    for (int T = tmax; T >= 1; --T) {
+        cap = max(cap, s_plan[T - 1].cap);
+        if (s_plan[T - 1].status == 0) tstar = T;
+        if (curve) curve[(size_t)b * tmax + (T - 1)] = s_plan[T - 1].cap;
     }
-    int32_t* I = info + (size_t)b * CODEC_PEE_BLIND_INFO_WORDS;
-    I[0] = status; I[1] = (int)n_user; I[2] = E; I[3] = n_side; I[4] = -1; I[5] = y0; I[6] = istar; I[7] = s_cap;
-    const bool ok = status == 0;
-    rect[4 * b] = ok ? y0 : 0; rect[4 * b + 1] = 0; rect[4 * b + 2] = ok ? H : 0; rect[4 * b + 3] = ok ? W : 0;
-    lens[b] = ok ? n_side + (int)n_user : 0;
-    ts[b] = thr;
-    gs[b] = CODEC_PEE_GATE_MAX;
+    bl_plan_write(b, s_plan[(tstar ? tstar : tmax) - 1], n_user, tstar ? tstar : tmax, cap, H, W, info, rect, lens, ts, gs);
+    t_out[b] = tstar;
 }
 
 // word k of slice b's user row, bits past n_user cleared
@@ -253,9 +500,11 @@ __device__ __forceinline__ uint32_t bl_get_word(const T* __restrict__ px, long l
     return w;
 }
 
-// one workgroup per slice, after the ROI embed: header, entries, padding; info's `end`
+// one workgroup per slice, after the ROI embed: header, entries, padding; info's `end`.  ts: the
+// plan's T per slice (clamped to the header's 1..64)
 template <typename T>
-__global__ __launch_bounds__(256) void k_blind_pack(T* __restrict__ stego, long long npx, int nc, int thr, int maxval,
+__global__ __launch_bounds__(256) void k_blind_pack(T* __restrict__ stego, long long npx, int nc,
+                                                    const int32_t* __restrict__ ts, int maxval,
                                                     const codec_pee_meta* __restrict__ meta, const u64* __restrict__ lm,
                                                     int lm_words, const uint32_t* __restrict__ crc,
                                                     int32_t* __restrict__ info) {
@@ -267,6 +516,7 @@ __global__ __launch_bounds__(256) void k_blind_pack(T* __restrict__ stego, long 
     const int end = min(max(meta[b].end, -1), min(nc, 64 * lm_words) - 1);
     T* px = stego + (size_t)b * npx;
     if (tid < CODEC_PEE_BLIND_HDR_WORDS) {
+        const int thr = min(max(ts[b], 1), 64);
         const uint32_t hw[CODEC_PEE_BLIND_HDR_WORDS] = {
             CODEC_PEE_BLIND_MAGIC,
             (uint32_t)thr | ((crc ? (uint32_t)CODEC_PEE_BLIND_FLAG_CRC : 0u) << 8) | ((uint32_t)maxval << 16),
@@ -363,10 +613,12 @@ __global__ __launch_bounds__(256) void k_blind_restore(T* __restrict__ cover, lo
 }
 
 // the checks every entry shares; `ws`: the entry takes the workspace
-static int blind_check(const codec_pee_params* P, int32_t max_entries, bool ws, size_t* base, const char* who) {
+static int blind_check(const codec_pee_params* P, int32_t max_entries, bool ws, size_t* base, const char* who,
+                       int32_t tmax = 1) {
     if (!P) return set_err(CODEC_EINVAL, "%s: params is NULL", who);
     if (max_entries < 0 || max_entries > CODEC_PEE_BLIND_MAX_ENTRIES)
         return set_err(CODEC_EINVAL, "%s: max_entries must be in 0..65536", who);
+    if (tmax < 1 || tmax > CODEC_PEE_BLIND_TMAX) return set_err(CODEC_EINVAL, "%s: tmax must be in 1..16", who);
     *base = codec_pee_workspace_bytes(P);
     if (!*base) return CODEC_EINVAL;   // codec_pee_workspace_bytes set the text
     int rc = pee_roi_dim_check(P, who);
@@ -400,6 +652,66 @@ static int blind_plan(const codec_pee_params* P, const BlWs& L, const void* cove
                        reinterpret_cast<int32_t*>(ws + L.lens), reinterpret_cast<int32_t*>(ws + L.ts),
                        reinterpret_cast<int32_t*>(ws + L.gs));
     LAUNCH_CHECK("k_blind_plan");
+    return 0;
+}
+
+// the same for every T in 1..tmax: one pass over the cover, the table [B][tmax][hc], the plan that
+// picks T per slice (t_out; curve or NULL)
+static int blind_plan_auto(const codec_pee_params* P, const BlWs& L, const void* cover, const int32_t* lengths,
+                           int user_bits, long long row_bits, int32_t tmax, int32_t max_entries, int32_t* info,
+                           int32_t* t_out, int32_t* curve, char* ws, hipStream_t st) {
+    uint2* rows = reinterpret_cast<uint2*>(ws + L.rows);
+    const int hc = P->H / 2;
+    if (hc > 0) {
+        ProfScope prof(st, CODEC_K_BLIND_ROWS_AUTO);
+        dim3 grid((unsigned)((hc + BL_ROWS_PER_WG - 1) / BL_ROWS_PER_WG), (unsigned)P->B);
+        pee_pixel(P->bytes, [&](auto px) {
+            using TT = decltype(px);
+            auto go = [&](auto kern) {
+                hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, static_cast<const TT*>(cover), P->H, P->W, P->maxval,
+                                   (int)tmax, rows);
+            };
+            pee_flag(pee_vec_route(P, cover), [&](auto v) { go(k_blind_rows_auto<TT, v()>); });
+        });
+        LAUNCH_CHECK("k_blind_rows_auto");
+    }
+    hipLaunchKernelGGL(k_blind_plan_auto, dim3((unsigned)P->B), dim3(64 * CODEC_PEE_BLIND_TMAX), 0, st, rows, lengths, user_bits, P->H, P->W,
+                       (int)tmax, (int)max_entries, row_bits, info, t_out, curve, reinterpret_cast<int32_t*>(ws + L.rect),
+                       reinterpret_cast<int32_t*>(ws + L.lens), reinterpret_cast<int32_t*>(ws + L.ts),
+                       reinterpret_cast<int32_t*>(ws + L.gs));
+    LAUNCH_CHECK("k_blind_plan_auto");
+    return 0;
+}
+
+// after a plan: splice, the ROI embed on the plan's arrays, pack
+static int blind_embed_planned(const codec_pee_params* P, const BlWs& L, const void* cover, void* stego,
+                               const uint64_t* payload, int32_t user_words, const uint32_t* crc, int32_t* info,
+                               codec_pee_meta* meta, uint64_t* lm, void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t st = as_stream(stream);
+    char* ws = static_cast<char*>(workspace);
+    u64* rows = reinterpret_cast<u64*>(ws + L.pay);
+    const long long npx = (long long)P->H * P->W;
+    {
+        dim3 grid((unsigned)((P->payload_words + 255) / 256), (unsigned)P->B);
+        pee_pixel(P->bytes, [&](auto px) {
+            using TT = decltype(px);
+            hipLaunchKernelGGL(k_blind_splice<TT>, grid, dim3(256), 0, st, static_cast<const TT*>(cover), npx,
+                               reinterpret_cast<const u64*>(payload), (int)user_words, info, rows, P->payload_words);
+        });
+        LAUNCH_CHECK("k_blind_splice");
+    }
+    const int32_t* ts = reinterpret_cast<const int32_t*>(ws + L.ts);
+    int rc = codec_pee_roi_embed(P, cover, stego, reinterpret_cast<const uint64_t*>(rows),
+                                 reinterpret_cast<const int32_t*>(ws + L.lens), ts, reinterpret_cast<const int32_t*>(ws + L.gs),
+                                 reinterpret_cast<const int32_t*>(ws + L.rect), meta, lm, workspace, workspace_bytes, stream);
+    if (rc) return rc;
+    const int nc = (P->H / 2) * (P->W / 2);
+    pee_pixel(P->bytes, [&](auto px) {
+        using TT = decltype(px);
+        hipLaunchKernelGGL(k_blind_pack<TT>, dim3((unsigned)P->B), dim3(256), 0, st, static_cast<TT*>(stego), npx, nc, ts,
+                           P->maxval, meta, reinterpret_cast<const u64*>(lm), P->lm_words, crc, info);
+    });
+    LAUNCH_CHECK("k_blind_pack");
     return 0;
 }
 
@@ -441,33 +753,10 @@ int codec_pee_blind_embed(const codec_pee_params* P, const void* cover, void* st
     const BlWs L = bl_ws(P, base);
     if (workspace_bytes < L.total) return set_err(CODEC_EINVAL, "codec_pee_blind_embed: workspace too small");
     if ((rc = pee_workspace_enter(P, workspace, stream))) return rc;
-    hipStream_t st = as_stream(stream);
-    char* ws = static_cast<char*>(workspace);
-    if ((rc = blind_plan(P, L, cover, lengths, 64 * user_words, 64LL * P->payload_words, max_entries, info, ws, st))) return rc;
-    u64* rows = reinterpret_cast<u64*>(ws + L.pay);
-    const long long npx = (long long)P->H * P->W;
-    {
-        dim3 grid((unsigned)((P->payload_words + 255) / 256), (unsigned)P->B);
-        pee_pixel(P->bytes, [&](auto px) {
-            using TT = decltype(px);
-            hipLaunchKernelGGL(k_blind_splice<TT>, grid, dim3(256), 0, st, static_cast<const TT*>(cover), npx,
-                               reinterpret_cast<const u64*>(payload), (int)user_words, info, rows, P->payload_words);
-        });
-        LAUNCH_CHECK("k_blind_splice");
-    }
-    rc = codec_pee_roi_embed(P, cover, stego, reinterpret_cast<const uint64_t*>(rows),
-                             reinterpret_cast<const int32_t*>(ws + L.lens), reinterpret_cast<const int32_t*>(ws + L.ts),
-                             reinterpret_cast<const int32_t*>(ws + L.gs), reinterpret_cast<const int32_t*>(ws + L.rect), meta,
-                             lm, workspace, workspace_bytes, stream);
-    if (rc) return rc;
-    const int nc = (P->H / 2) * (P->W / 2);
-    pee_pixel(P->bytes, [&](auto px) {
-        using TT = decltype(px);
-        hipLaunchKernelGGL(k_blind_pack<TT>, dim3((unsigned)P->B), dim3(256), 0, st, static_cast<TT*>(stego), npx, nc, P->T,
-                           P->maxval, meta, reinterpret_cast<const u64*>(lm), P->lm_words, crc, info);
-    });
-    LAUNCH_CHECK("k_blind_pack");
-    return 0;
+    if ((rc = blind_plan(P, L, cover, lengths, 64 * user_words, 64LL * P->payload_words, max_entries, info,
+                         static_cast<char*>(workspace), as_stream(stream))))
+        return rc;
+    return blind_embed_planned(P, L, cover, stego, payload, user_words, crc, info, meta, lm, workspace, workspace_bytes, stream);
 }
 
 int codec_pee_blind_headers(const codec_pee_params* P, const void* stego, uint32_t* hdr_out, void* stream) {
@@ -532,6 +821,48 @@ int codec_pee_blind_extract(const codec_pee_params* P, const void* stego, const 
         LAUNCH_CHECK("k_blind_restore");
     }
     return 0;
+}
+
+// ---- include/codec_tcc_blind_auto.h
+size_t codec_pee_blind_auto_workspace_bytes(const codec_pee_params* P, int32_t tmax, int32_t max_entries) {
+    size_t base = 0;
+    if (blind_check(P, max_entries, true, &base, "codec_pee_blind_auto_workspace_bytes", tmax)) return 0;
+    return bl_ws(P, base, tmax).total;
+}
+
+int codec_pee_blind_plan_auto(const codec_pee_params* P, const void* cover, const int32_t* lengths, int32_t tmax,
+                              int32_t max_entries, int32_t* info, int32_t* t_out, int32_t* curve, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    size_t base = 0;
+    int rc = blind_check(P, max_entries, true, &base, "codec_pee_blind_plan_auto", tmax);
+    if (rc) return rc;
+    if (!cover || !info || !t_out || !workspace) return set_err(CODEC_EINVAL, "codec_pee_blind_plan_auto: NULL pointer argument");
+    const BlWs L = bl_ws(P, base, tmax);
+    if (workspace_bytes < L.total) return set_err(CODEC_EINVAL, "codec_pee_blind_plan_auto: workspace too small");
+    if ((rc = pee_workspace_enter(P, workspace, stream))) return rc;
+    return blind_plan_auto(P, L, cover, lengths, INT_MAX, 1LL << 40, tmax, max_entries, info, t_out, curve,
+                           static_cast<char*>(workspace), as_stream(stream));
+}
+
+int codec_pee_blind_embed_auto(const codec_pee_params* P, const void* cover, void* stego, const uint64_t* payload,
+                               int32_t user_words, const int32_t* lengths, const uint32_t* crc, int32_t tmax,
+                               int32_t max_entries, int32_t* info, int32_t* t_out, codec_pee_meta* meta, uint64_t* lm,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    size_t base = 0;
+    int rc = blind_check(P, max_entries, true, &base, "codec_pee_blind_embed_auto", tmax);
+    if (rc) return rc;
+    if (!cover || !stego || !payload || !lengths || !info || !t_out || !meta || !lm || !workspace)
+        return set_err(CODEC_EINVAL, "codec_pee_blind_embed_auto: NULL pointer argument");
+    if (cover == stego) return set_err(CODEC_EINVAL, "codec_pee_blind_embed_auto: out of place only (cover == stego)");
+    if (user_words < 1 || user_words > (1 << 24))
+        return set_err(CODEC_EINVAL, "codec_pee_blind_embed_auto: user_words must be in 1..2^24");
+    const BlWs L = bl_ws(P, base, tmax);
+    if (workspace_bytes < L.total) return set_err(CODEC_EINVAL, "codec_pee_blind_embed_auto: workspace too small");
+    if ((rc = pee_workspace_enter(P, workspace, stream))) return rc;
+    if ((rc = blind_plan_auto(P, L, cover, lengths, 64 * user_words, 64LL * P->payload_words, tmax, max_entries, info, t_out,
+                              nullptr, static_cast<char*>(workspace), as_stream(stream))))
+        return rc;
+    return blind_embed_planned(P, L, cover, stego, payload, user_words, crc, info, meta, lm, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -671,6 +671,23 @@ class PeeCodec:
         (the plan rule of DESIGN §3k), -1 where not even the header fits."""
         return _blind.capacity(self, covers, max_entries)
 
+    def embed_blind_auto(self, covers, payloads, *, tmax=None, stego=None, packed=None, checksum=False,
+                         max_entries: int = 256, check: bool = True):
+        """(stego, info, ts): embed_blind with T chosen per slice on the device (DESIGN §3l;
+        include/codec_tcc_blind_auto.h): the smallest T in 1..tmax whose plan takes the slice's
+        payload, so the least distortion that holds it.  ts: int32 [B] on the device, the chosen T,
+        0 for a refused slice, whose info is the plan's at tmax.  tmax: 1..16, None: this codec's.
+        The codec's own T is ignored (fixed or "auto"); every other rule of embed_blind holds, and
+        decode_blind reads the stego as it is.  One pass over the covers fills the row table of
+        every T; nothing is read back before the embed (capturable with packed= and check=False)."""
+        return _blind.embed_auto(self, covers, payloads, tmax=tmax, stego=stego, packed=packed, checksum=checksum,
+                                 max_entries=max_entries, check=check)
+
+    def blind_capacity_curve(self, covers, tmax=None, max_entries: int = 256):
+        """int32 [B, tmax] device tensor: blind_capacity at every T in 1..tmax (None: this codec's
+        tmax, at most 16), from one pass over the covers."""
+        return _blind.capacity_curve(self, covers, tmax, max_entries)
+
     # ---- volume payloads: one bitstream across the stack (include/codec_tcc_vol.h)
     def _cached_workspace(self, fn: str, payload_words: int, tmax: int):
         """A workspace sized by the library's `fn` for this row pitch; the last few are kept, so a
@@ -1045,6 +1062,26 @@ def encode_blind(covers, payloads: Sequence, *, T: int = 2, maxval: Optional[int
     dt = "uint16" if _elem_bytes(covers) == 2 else "uint8"
     codec = _codec_for(tuple(covers.shape), dt, T=int(T), tmax=16, maxval=maxval)
     return codec.embed_blind(covers, payloads, checksum=checksum, max_entries=max_entries)
+
+
+def encode_blind_auto(covers, payloads: Sequence, *, tmax: int = 16, maxval: Optional[int] = None, checksum=False,
+                      max_entries: int = 256):
+    """encode_blind with T chosen per slice (PeeCodec.embed_blind_auto): (stego, info, ts), each
+    slice at the smallest T in 1..tmax that takes its payload.  Raises ValueError naming the slices
+    that no T <= tmax serves; argument errors are raised before the GPU is touched."""
+    shape = tuple(covers.shape)
+    if len(shape) < 2:
+        raise ValueError(f"covers must be [B, H, W] or [H, W], got shape {shape}")
+    mv = maxval if maxval is not None else (255 if "8" in str(covers.dtype) and "16" not in str(covers.dtype) else 65535)
+    _blind.check_args_auto(scheme=1, tmax=tmax, gate=None, H=int(shape[-2]), W=int(shape[-1]), maxval=mv,
+                           max_entries=max_entries)
+    _require_gpu()
+    covers = _as_gpu_batch(covers)
+    if isinstance(payloads, (str, bytes, bytearray)):
+        payloads = [payloads]
+    dt = "uint16" if _elem_bytes(covers) == 2 else "uint8"
+    codec = _codec_for(tuple(covers.shape), dt, T=1, tmax=int(tmax), maxval=maxval)
+    return codec.embed_blind_auto(covers, payloads, checksum=checksum, max_entries=max_entries)
 
 
 def decode_blind(stego, verify=True, *, restore: bool = True):

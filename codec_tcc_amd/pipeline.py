@@ -279,6 +279,34 @@ def encode_dicom_pee(image_or_path, payload, out_path: str, T: int = 2, checksum
             **dict(zip(("status", "L", "E", "n_side", "end", "region_row"), row))}
 
 
+def encode_dicom_pee_auto(image_or_path, payload, out_path: str, tmax: int = 16, checksum: bool = True,
+                          maxval: Optional[int] = None, max_entries: int = 256) -> Dict:
+    """encode_dicom_pee with T chosen on the device (PeeCodec.embed_blind_auto): the
+    smallest T in 1..tmax that takes the payload and its side bits.  The result's "T" is the chosen
+    one; decode_dicom_pee reads the file as it is.  ValueError when no T <= tmax serves."""
+    from .pee import PeeCodec
+    _require_gpu()
+    torch = _torch()
+    if isinstance(image_or_path, np.ndarray):
+        img = image_or_path
+    else:
+        img, attrs = dicom.read_dicom(image_or_path)
+        if maxval is None and attrs.get("bits_stored"):
+            maxval = (1 << int(attrs["bits_stored"])) - 1
+    if img.ndim != 2 or img.dtype not in (np.uint8, np.uint16):
+        raise ValueError("A imagem deve ser 2D uint8 ou uint16.")
+    h, w = img.shape
+    bits = framing.to_bits(payload)
+    pc = PeeCodec(1, h, w, dtype=str(img.dtype), T=1, tmax=tmax, maxval=maxval)
+    stego, info, ts = pc.embed_blind_auto(torch.from_numpy(np.ascontiguousarray(img)[None]).cuda(), [bits],
+                                          checksum=bool(checksum), max_entries=max_entries)
+    out = stego.cpu().numpy()[0]
+    size = dicom.save_dicom(out, out_path)
+    row = [int(v) for v in info.cpu().tolist()[0]]
+    return {"path": out_path, "bytes": size, "T": int(ts.cpu().tolist()[0]), "maxval": pc.maxval, "stego": out,
+            **dict(zip(("status", "L", "E", "n_side", "end", "region_row"), row))}
+
+
 def decode_dicom_pee(path, verify=True) -> Tuple[np.ndarray, np.ndarray]:
     """(payload bits as a 0/1 uint8 vector, restored cover) from a DICOM written by
     encode_dicom_pee (a path or the file's bytes): PeeCodec.decode_blind on its pixels.  ValueError
