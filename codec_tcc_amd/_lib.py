@@ -1,7 +1,7 @@
 """ctypes binding of libcodec_hip.so (include/codec_tcc.h, include/codec_tcc_ext.h,
 include/codec_tcc_crc.h, include/codec_tcc_vol.h, include/codec_tcc_gate.h, include/codec_tcc_gvol.h,
 include/codec_tcc_tile.h, include/codec_tcc_roi.h, include/codec_tcc_aead.h, include/codec_tcc_blind.h,
-include/codec_tcc_blind_auto.h).
+include/codec_tcc_blind_auto.h, include/codec_tcc_blind_keyed.h).
 
 The library is built in-tree (codec_tcc_amd/libcodec_hip.so, see build.py).  There is no
 CPU fallback: if the library cannot be loaded, every entry point raises RuntimeError.
@@ -285,6 +285,20 @@ _SIGS_BLIND_AUTO = {
                                              _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
 }
 EXPORTS_BLIND_AUTO = tuple(_SIGS_BLIND_AUTO)
+# include/codec_tcc_blind_keyed.h: keyed blind MED-PEE (blind.py embed_keyed / decode_keyed; aead.py, the *_n calls)
+BLIND_FLAG_KEYED = 2              # CODEC_PEE_BLIND_FLAG_KEYED
+BLIND_FRAME_BITS = 224            # CODEC_PEE_BLIND_FRAME_BITS
+BLIND_FRAME_WORDS = 7             # CODEC_PEE_BLIND_FRAME_WORDS
+_SIGS_BLIND_KEYED = {
+    "codec_chacha20_rows_n": (C.c_int, [_VP, C.c_int32, _VP, _VP, C.c_int32, _VP, _VP, _VP]),
+    "codec_poly1305_tags_n": (C.c_int, [_VP, C.c_int32, _VP, _VP, C.c_int64, _VP, C.c_int32, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "codec_aead_release_n": (C.c_int, [_VP, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, _VP, _VP, _VP]),
+    "codec_pee_blind_frames": (C.c_int, [_VP, C.c_int32, C.c_uint32, _VP, _VP, _VP]),
+    "codec_pee_blind_embed_keyed": (C.c_int, [C.POINTER(PeeParams), _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, C.c_int32,
+                                              _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "codec_pee_blind_unframe": (C.c_int, [C.c_int32, _VP, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, _VP]),
+}
+EXPORTS_BLIND_KEYED = tuple(_SIGS_BLIND_KEYED)
 
 _lib = None
 _load_error = None
@@ -314,7 +328,8 @@ def load(path: str = LIB_PATH):
         _load_error = e
         raise RuntimeError(f"cannot load {path}: {e}") from e
     for name, (res, args) in {**_SIGS, **_SIGS_EXT, **_SIGS_CRC, **_SIGS_VOL, **_SIGS_GATE, **_SIGS_GVOL,
-                              **_SIGS_TILE, **_SIGS_ROI, **_SIGS_AEAD, **_SIGS_BLIND, **_SIGS_BLIND_AUTO}.items():
+                              **_SIGS_TILE, **_SIGS_ROI, **_SIGS_AEAD, **_SIGS_BLIND, **_SIGS_BLIND_AUTO,
+                              **_SIGS_BLIND_KEYED}.items():
         fn = getattr(lib, name, None)
         if fn is None:
             if name == "codec_build_digest" and not in_tree:   # a diagnostic build (tools/)

@@ -231,6 +231,70 @@ def release(ctx, tags_got, tags_want, rows, lengths, index0: int = 0, out=None, 
     return out, ok
 
 
+# ------------------------------------------------------------------ one nonce per slice (include/codec_tcc_blind_keyed.h)
+def _check_nonce12(n12, B: int, device):
+    torch = _torch()
+    if not isinstance(n12, torch.Tensor) or n12.dtype != torch.int32 or tuple(n12.shape) != (B, 3) \
+            or not n12.is_contiguous() or n12.device != device:
+        raise ValueError(f"nonce12 must be a contiguous int32 [{B}, 3] tensor on {device}: (g, nonce word 0, nonce word 1)")
+    return n12
+
+
+def nonce12_rows(nonce, index0: int, B: int, device=None):
+    """int32 [B, 3] device tensor: (index0 + b, the nonce's two little-endian words), i.e. what the
+    calls that take (nonce, index0) use for slice b."""
+    nonce = check_nonce(nonce)
+    index0 = check_index(index0, B)
+    _require_gpu()
+    torch = _torch()
+    w = np.frombuffer(nonce, dtype="<u4").astype(np.int64)
+    rows = np.stack([(index0 + np.arange(B, dtype=np.int64)) & 0xFFFFFFFF, np.full(B, w[0]), np.full(B, w[1])], axis=1)
+    return torch.from_numpy(rows.astype(np.uint32).view(np.int32)).to(device if device is not None else "cuda")
+
+
+def chacha20_rows_n(ctx, nonce12, rows, lengths, out=None):
+    """chacha20_rows with slice b under nonce12[b] = (g, nonce words) and ctx's key (ctx's own nonce
+    is ignored).  No index rule: a decoder takes g from the stego."""
+    _require_gpu()
+    _check_ctx(ctx)
+    B, rw = _check_rows(rows, lengths, "chacha20_rows_n")
+    _check_nonce12(nonce12, B, rows.device)
+    out = _check_out(out, rows, "out")
+    _lib.check(_lib.load().codec_chacha20_rows_n(ctx.data_ptr(), B, nonce12.data_ptr(), rows.data_ptr(), rw, lengths.data_ptr(),
+                                                 out.data_ptr(), _stream()), "codec_chacha20_rows_n")
+    return out
+
+
+def poly1305_tags_n(ctx, nonce12, aad, rows=None, lengths=None, out=None):
+    """poly1305_tags with slice b's one-time key derived under nonce12[b]."""
+    _check_ctx(ctx)
+    lib, B, ap, nbytes, rp, rw, lp, out, work, ws = _tags("poly1305_tags_n", aad, rows, lengths, out)
+    _check_nonce12(nonce12, B, out.device)
+    _lib.check(lib.codec_poly1305_tags_n(ctx.data_ptr(), B, nonce12.data_ptr(), ap, nbytes, rp, rw, lp, out.data_ptr(),
+                                         work.data_ptr(), ws, _stream()), "codec_poly1305_tags_n")
+    return out
+
+
+def release_n(ctx, nonce12, tags_got, tags_want, rows, lengths, out=None, ok=None):
+    """release with slice b decrypted under nonce12[b]."""
+    _require_gpu()
+    torch = _torch()
+    _check_ctx(ctx)
+    B, rw = _check_rows(rows, lengths, "release_n")
+    _check_nonce12(nonce12, B, rows.device)
+    _check_tags(tags_got, B, rows.device, "tags_got")
+    _check_tags(tags_want, B, rows.device, "tags_want")
+    out = _check_out(out, rows, "out")
+    if ok is None:
+        ok = torch.empty(B, dtype=torch.int32, device=rows.device)
+    elif ok.dtype != torch.int32 or tuple(ok.shape) != (B,) or not ok.is_contiguous() or ok.device != rows.device:
+        raise ValueError(f"ok must be a contiguous int32 [{B}] tensor on the rows' device")
+    _lib.check(_lib.load().codec_aead_release_n(ctx.data_ptr(), B, nonce12.data_ptr(), tags_got.data_ptr(),
+                                                tags_want.data_ptr(), rows.data_ptr(), rw, lengths.data_ptr(), out.data_ptr(),
+                                                ok.data_ptr(), _stream()), "codec_aead_release_n")
+    return out, ok
+
+
 def tag_bytes(tags) -> list:
     """The tags of a poly1305_tags() tensor as 16-byte strings (one read-back)."""
     raw = tags.detach().cpu().contiguous().numpy().astype("<i4").tobytes()

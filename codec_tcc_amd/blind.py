@@ -16,6 +16,13 @@ the device, the smallest T in 1..tmax whose plan succeeds; the format and the de
 
     stego, info, ts = codec.embed_blind_auto(covers, payloads, tmax=8)
 
+Keyed (include/codec_tcc_blind_keyed.h): the user bits of a slice with flag bit 1 are a
+224-bit frame (nonce12, Poly1305 tag) and the ChaCha20 ciphertext, so a 32-byte key is all a reader
+needs besides the pixels; tests/pee_blind_keyed_spec.py is the specification.
+
+    stego, info, ts = codec.embed_blind_keyed(covers, payloads, key=key)
+    bits, cover = codec.decode_blind_keyed(stego, key)
+
 parse_header, check_args and the geometry helpers are pure host code: no GPU, no library load.
 """
 from __future__ import annotations
@@ -32,6 +39,8 @@ HDR_WORDS = _lib.BLIND_HDR_WORDS
 HDR_BITS = 32 * HDR_WORDS
 NO_ENTRY = 0xFFFFFFFF
 FLAG_CRC = _lib.BLIND_FLAG_CRC
+FLAG_KEYED = _lib.BLIND_FLAG_KEYED
+KEYED_FRAME_BITS = _lib.BLIND_FRAME_BITS
 MAX_ENTRIES = _lib.BLIND_MAX_ENTRIES
 MAX_DIM = _lib.ROI_MAX_DIM
 TMAX = _lib.BLIND_TMAX
@@ -94,9 +103,23 @@ def check_args_auto(*, scheme: int, tmax, gate, H: int, W: int, maxval: int, max
                in_place=in_place)
 
 
-def parse_header(words, H: int, W: int, vmax: int) -> Dict:
+def _flags_error(flags: int, n_user: int, keyed: bool):
+    """The reason (or None) the flags of a header are refused: unkeyed, bit 0 alone is defined; keyed,
+    they are exactly FLAG_KEYED and n_user holds the frame."""
+    if not keyed:
+        return f"flags = {flags:#x} (bit 0 alone is defined)" if flags & ~FLAG_CRC else None
+    if flags != FLAG_KEYED:
+        return (f"flags = {flags:#x} (a keyed slice has exactly {FLAG_KEYED:#x}" +
+                ("; an unkeyed stego is decode_blind's)" if not flags & ~FLAG_CRC else ")"))
+    if n_user < KEYED_FRAME_BITS:
+        return f"n_user = {n_user} (a keyed slice holds the {KEYED_FRAME_BITS} frame bits)"
+    return None
+
+
+def parse_header(words, H: int, W: int, vmax: int, *, keyed: bool = False) -> Dict:
     """One slice's six header words -> {T, flags, maxval, n_user, E, end, crc, n_side, rect, L};
-    ValueError naming the field for anything that is no header of an H x W slice."""
+    ValueError naming the field for anything that is no header of an H x W slice.  keyed=True: the
+    header of a keyed slice (flags exactly FLAG_KEYED, n_user >= 224), which the default refuses."""
     w = [int(v) & 0xFFFFFFFF for v in list(words)[:HDR_WORDS]]
     H, W = int(H), int(W)
     hc, wc = H // 2, W // 2
@@ -106,8 +129,9 @@ def parse_header(words, H: int, W: int, vmax: int) -> Dict:
     T, flags, maxval = w[1] & 0xFF, (w[1] >> 8) & 0xFF, w[1] >> 16
     if not 1 <= T <= 64:
         raise ValueError(f"T = {T} (1..64)")
-    if flags & ~FLAG_CRC:
-        raise ValueError(f"flags = {flags:#x} (bit 0 alone is defined)")
+    why = _flags_error(flags, w[2], keyed)
+    if why:
+        raise ValueError(why)
     if not 1 <= maxval <= vmax:
         raise ValueError(f"maxval = {maxval} (1..{vmax})")
     n_user, E = w[2], w[3]
@@ -129,11 +153,11 @@ def parse_header(words, H: int, W: int, vmax: int) -> Dict:
             "n_side": n_side, "rect": rect, "L": L}
 
 
-def parse_headers(hdr: np.ndarray, H: int, W: int, nbytes: int) -> Dict[str, np.ndarray]:
+def parse_headers(hdr: np.ndarray, H: int, W: int, nbytes: int, *, keyed: bool = False) -> Dict[str, np.ndarray]:
     """Every slice's header (hdr: uint32 [B, >= 6] as codec_pee_blind_headers gathers them) as int64
     arrays [B] under parse_header's names ("rect": [B, 4]): parse_header's rules applied to all
     slices at once.  ValueError naming the slices that carry no header, each with parse_header's
-    reason."""
+    reason.  keyed: parse_header's."""
     H, W = int(H), int(W)
     hc, wc = H // 2, W // 2
     nc = hc * wc
@@ -145,17 +169,18 @@ def parse_headers(hdr: np.ndarray, H: int, W: int, nbytes: int) -> Dict[str, np.
     n_side = HDR_BITS + 32 * E
     r = -(-n_side // (2 * W))
     L = n_side + n_user
-    ok = ((w[:, 0] == MAGIC) & (T >= 1) & (T <= 64) & ((flags & ~FLAG_CRC) == 0) & (maxval >= 1) & (maxval <= vmax)
+    flags_ok = ((flags == FLAG_KEYED) & (n_user >= KEYED_FRAME_BITS)) if keyed else ((flags & ~FLAG_CRC) == 0)
+    ok = ((w[:, 0] == MAGIC) & (T >= 1) & (T <= 64) & flags_ok & (maxval >= 1) & (maxval <= vmax)
           & (end < nc) & (E <= nc) & (n_side <= H * W) & (r <= hc) & (end < (hc - r) * wc) & (L <= end + 1))
     if not ok.all():
         bad = []
         for b in np.flatnonzero(~ok):
             try:
-                parse_header(w[b], H, W, vmax)
+                parse_header(w[b], H, W, vmax, keyed=keyed)
                 bad.append((int(b), "inconsistent header"))   # (the two statements of the rules disagree)
             except ValueError as e:
                 bad.append((int(b), str(e)))
-        raise ValueError(f"no valid blind MED-PEE header in slices {[b for b, _ in bad]}: "
+        raise ValueError(f"no valid {'keyed ' if keyed else ''}blind MED-PEE header in slices {[b for b, _ in bad]}: "
                          + "; ".join(f"slice {b}: {why}" for b, why in bad[:4]))
     rect = np.stack([2 * (hc - r), np.zeros_like(r), np.full_like(r, H), np.full_like(r, W)], axis=1)
     return {"T": T, "flags": flags, "maxval": maxval, "n_user": n_user, "E": E, "end": end, "crc": w[:, 5],
@@ -292,12 +317,12 @@ def capacity(codec, covers, max_entries: int = 256):
     return info[:, _lib.BLIND_INFO_WORDS - 1].contiguous()
 
 
-def decode(codec, stego, *, cover=None, verify=True):
-    from . import checksum as _ck, framing, pee_verify as _pv
+def _headers(codec, stego, cover, *, keyed: bool = False):
+    """(hdr, heads): the buffers judged, every slice's header gathered on the device and read back
+    once (hdr: the device tensor, heads: parse_headers' arrays)."""
     from .codec import _stream, _torch
-    from .pee_checks import check_buffers, check_records
+    from .pee_checks import check_buffers
     torch = _torch()
-    mode = _ck.verify_mode(verify)
     if codec.scheme != 1:
         raise ValueError("blind MED-PEE is scheme 1's")
     if codec.H > MAX_DIM or codec.W > MAX_DIM or codec.H * codec.W < HDR_BITS:
@@ -306,36 +331,65 @@ def decode(codec, stego, *, cover=None, verify=True):
                   stego=stego, cover=cover)
     if cover is not None and cover.data_ptr() == stego.data_ptr():
         raise ValueError("blind MED-PEE decodes out of place only: pass a cover buffer other than the stego")
-    lib = _lib.load()
     hdr = torch.empty((codec.B, 8), dtype=torch.int32, device=codec.device)
-    _lib.check(lib.codec_pee_blind_headers(C.byref(codec._params(1)), stego.data_ptr(), hdr.data_ptr(), _stream()),
+    _lib.check(_lib.load().codec_pee_blind_headers(C.byref(codec._params(1)), stego.data_ptr(), hdr.data_ptr(), _stream()),
                "codec_pee_blind_headers")
-    heads = parse_headers(hdr.cpu().numpy().view(np.uint32), codec.H, codec.W, codec.bytes)   # the one read-back before the extract
+    # the one read-back before the extract
+    return hdr, parse_headers(hdr.cpu().numpy().view(np.uint32), codec.H, codec.W, codec.bytes, keyed=keyed)
+
+
+def _extract(codec, stego, hdr, heads, cover):
+    """(user rows [B, uw] on the device, cover, ws, pw): the records rebuilt from the checked headers
+    and judged, then codec_pee_blind_extract queued."""
+    from .codec import _stream, _torch
+    from .pee_checks import check_records
+    torch = _torch()
     pw = max(HDR_BITS // 64, int((heads["L"].max() + 63) // 64))
     uw = max(1, int((heads["n_user"].max() + 63) // 64))
     raw = records_bytes(heads, codec.H, codec.W)
     check_records([_lib.PeeMeta.from_buffer_copy(raw, b * _lib.PEE_META_BYTES) for b in range(codec.B)], codec.H, codec.W,
                   scheme=1, payload_words=pw, lm_words=codec.lm_words, bytes=codec.bytes)
-    has_crc = (heads["flags"] & FLAG_CRC) != 0
-    if mode == "require" and not has_crc.all():
-        raise _ck.IntegrityError("blind MED-PEE decode: verify='require' and slices "
-                                 f"{np.flatnonzero(~has_crc).tolist()} carry no cover checksum")
     meta = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy().reshape(codec.B, _lib.PEE_META_BYTES)).to(codec.device)
     if cover is None:
         cover = torch.empty_like(stego)
     words = torch.empty((codec.B, uw), dtype=torch.int64, device=codec.device)
     ws = _workspace(codec, pw, 0)
-    _guarded(codec, ws, pw, lambda: _lib.check(lib.codec_pee_blind_extract(
+    _guarded(codec, ws, pw, lambda: _lib.check(_lib.load().codec_pee_blind_extract(
         C.byref(codec._params(pw)), stego.data_ptr(), hdr.data_ptr(), meta.data_ptr(), cover.data_ptr(), words.data_ptr(),
         uw, ws.data_ptr(), ws.numel(), _stream()), "codec_pee_blind_extract"))
+    return words, cover, ws, pw
+
+
+def _lookback_flag(codec, ws, pw):
+    """The flat look-back route's flag word in the workspace (small batches take that route out of
+    place too) as an int32 [1] device view, or None when the shape has none."""
+    from .codec import _torch
+    off = int(_lib.load().codec_pee_extract_flag_offset(C.byref(codec._params(pw))))
+    return ws[off:off + 4].view(_torch().int32) if off else None
+
+
+def _raise_lookback(codec, ws, pw):
+    from . import pee_verify as _pv
+    from .codec import _stream
+    _lib.check(_lib.load().codec_pee_reset(C.byref(codec._params(pw)), ws.data_ptr(), ws.numel(), _stream()), "codec_pee_reset")
+    raise RuntimeError(_pv.LOOKBACK_TIMEOUT)
+
+
+def decode(codec, stego, *, cover=None, verify=True):
+    from . import checksum as _ck, framing, pee_verify as _pv
+    mode = _ck.verify_mode(verify)
+    hdr, heads = _headers(codec, stego, cover)
+    has_crc = (heads["flags"] & FLAG_CRC) != 0
+    if mode == "require" and not has_crc.all():
+        raise _ck.IntegrityError("blind MED-PEE decode: verify='require' and slices "
+                                 f"{np.flatnonzero(~has_crc).tolist()} carry no cover checksum")
+    words, cover, ws, pw = _extract(codec, stego, hdr, heads, cover)
     flagged = np.flatnonzero(has_crc).tolist()
     got = _ck.crc32_slices(cover) if mode is not None and flagged else None
     host = words.cpu().numpy()
-    # small batches take the flat look-back route out of place too: its flag, as decode() reads it
-    off = int(lib.codec_pee_extract_flag_offset(C.byref(codec._params(pw))))
-    if off and int(ws[off:off + 4].view(torch.int32).item()) != 0:
-        _lib.check(lib.codec_pee_reset(C.byref(codec._params(pw)), ws.data_ptr(), ws.numel(), _stream()), "codec_pee_reset")
-        raise RuntimeError(_pv.LOOKBACK_TIMEOUT)
+    flag = _lookback_flag(codec, ws, pw)   # as decode() reads it
+    if flag is not None and int(flag.item()) != 0:
+        _raise_lookback(codec, ws, pw)
     if got is not None:
         bad = set(_pv.cover_mismatches(got, heads["crc"].tolist(), codec.B))
         _ck.raise_mismatch([b for b in flagged if b in bad], [], "blind MED-PEE decode", rows=host)
@@ -401,3 +455,95 @@ def capacity_curve(codec, covers, tmax=None, max_entries: int = 256):
         C.byref(_params_auto(codec, pw)), covers.data_ptr(), None, tmax, int(max_entries), info.data_ptr(), ts.data_ptr(),
         curve.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "codec_pee_blind_plan_auto"))
     return curve
+
+
+# ---------------------------------------------------------------- keyed: nonce and tag ride in the stego
+def embed_keyed(codec, covers, payloads, *, key, nonce=None, index0: int = 0, tmax=None, stego=None, packed=None,
+                max_entries: int = 256, check: bool = True):
+    from . import aead as _aead
+    from .codec import _stream, _torch
+    from .pee_checks import check_buffers
+    torch = _torch()
+    if key is None:
+        raise ValueError("embed_blind_keyed takes key= (32 bytes); embed_blind is the unkeyed call")
+    key, nonce, index0 = _aead.check_call(key, nonce, index0, codec.B)   # judged before anything is queued
+    auto = tmax is not None
+
+    def rules(in_place=False):
+        if auto:
+            return _auto_args(codec, tmax, max_entries, in_place)
+        _codec_args(codec, max_entries, in_place)
+        return 0
+    tmax = rules()
+    check_buffers(codec.device, codec.B, codec.H, codec.W, codec.bytes, lm_words=codec.lm_words, scheme=1,
+                  covers=covers, stego=stego, packed=packed)
+    rules(in_place=stego is not None and stego.data_ptr() == covers.data_ptr())
+    words, lengths, lens_t = packed if packed is not None else codec.pack_payloads(payloads)
+    n_max = max([int(n) for n in lengths] + [0])
+    if n_max > 64 * int(words.shape[1]):
+        raise ValueError(f"a payload of {n_max} bits does not fit the packed rows' {64 * int(words.shape[1])}")
+    pw = row_words(n_max + KEYED_FRAME_BITS, max_entries)
+    lib = _lib.load()
+    ctx = _aead.upload_ctx(key, nonce, codec.device)
+    ct = _aead.chacha20_rows(ctx, words, lens_t, index0)          # into a new buffer: packed= rows are not modified
+    tag = _aead.poly1305_tags(ctx, covers, ct, lens_t, index0)    # PeeCodec.embed(key=)'s tag of (cover, ciphertext)
+    frames = torch.empty((codec.B, _lib.BLIND_FRAME_WORDS), dtype=torch.int32, device=codec.device)
+    _lib.check(lib.codec_pee_blind_frames(ctx.data_ptr(), codec.B, index0, tag.data_ptr(), frames.data_ptr(), _stream()),
+               "codec_pee_blind_frames")
+    if stego is None:
+        stego = torch.empty_like(covers)
+    ws = _workspace(codec, pw, max_entries, tmax)
+    info = torch.empty((codec.B, _lib.BLIND_INFO_WORDS), dtype=torch.int32, device=codec.device)
+    ts = torch.empty((codec.B,), dtype=torch.int32, device=codec.device) if auto else \
+        torch.full((codec.B,), codec.T, dtype=torch.int32, device=codec.device)
+    lm = torch.empty((codec.B, codec.lm_words), dtype=torch.int64, device=codec.device)
+    meta = torch.empty((codec.B, _lib.PEE_META_BYTES), dtype=torch.uint8, device=codec.device)
+    P = _params_auto(codec, pw) if auto else codec._params(pw)
+    _guarded(codec, ws, pw, lambda: _lib.check(lib.codec_pee_blind_embed_keyed(
+        C.byref(P), covers.data_ptr(), stego.data_ptr(), frames.data_ptr(), ct.data_ptr(), int(ct.shape[1]),
+        lens_t.data_ptr(), tmax, int(max_entries), info.data_ptr(), ts.data_ptr() if auto else None, meta.data_ptr(),
+        lm.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "codec_pee_blind_embed_keyed"))
+    out = info[:, :len(INFO_FIELDS)]
+    if check:
+        raise_status(out[:, 0].cpu().tolist(), "embed_blind_keyed")   # one read-back
+    return stego, out, ts
+
+
+def decode_keyed(codec, stego, key, *, cover=None, verify=True):
+    from . import aead as _aead, checksum as _ck, framing
+    from .codec import _stream, _torch
+    torch = _torch()
+    key = _aead.check_key(key)
+    mode = _ck.verify_mode(verify)   # 'require' is satisfied by the tag every keyed slice carries
+    hdr, heads = _headers(codec, stego, cover, keyed=True)
+    words, cover, ws, pw = _extract(codec, stego, hdr, heads, cover)
+    B = codec.B
+    n_ct = (heads["n_user"] - KEYED_FRAME_BITS).tolist()
+    cw = max(1, (max(n_ct) + 63) // 64)
+    n12 = torch.empty((B, 3), dtype=torch.int32, device=codec.device)
+    want = torch.empty((B, _aead.TAG_WORDS), dtype=torch.int32, device=codec.device)
+    ct = torch.empty((B, cw), dtype=torch.int64, device=codec.device)
+    ct_len = torch.empty((B,), dtype=torch.int32, device=codec.device)
+    _lib.check(_lib.load().codec_pee_blind_unframe(B, words.data_ptr(), int(words.shape[1]), hdr.data_ptr(), n12.data_ptr(),
+                                                   want.data_ptr(), ct.data_ptr(), cw, ct_len.data_ptr(), _stream()),
+               "codec_pee_blind_unframe")
+    ctx = _aead.upload_ctx(key, bytes(_aead.NONCE_BYTES), codec.device)   # the key alone: every slice brings its nonce
+    if mode is None:
+        pt, ok = _aead.chacha20_rows_n(ctx, n12, ct, ct_len), None
+    else:   # the tag of (restored cover, ciphertext) compared and the rows released on the device
+        got = _aead.poly1305_tags_n(ctx, n12, cover, ct, ct_len)
+        pt, ok = _aead.release_n(ctx, n12, got, want, ct, ct_len)
+    flag = _lookback_flag(codec, ws, pw)
+    parts = [pt.reshape(-1)] + ([ok.to(torch.int64)] if ok is not None else []) + \
+        ([flag.to(torch.int64)] if flag is not None else [])
+    host = torch.cat(parts).cpu().numpy()   # the final read-back: rows, ok and the flag
+    rows = host[:B * cw].reshape(B, cw)
+    if flag is not None and int(host[-1]) != 0:
+        _raise_lookback(codec, ws, pw)
+    if ok is not None:
+        bad = [b for b in range(B) if not int(host[B * cw + b])]
+        if bad:
+            raise _ck.IntegrityError(
+                f"keyed blind MED-PEE decode: authentication failed in slices {bad} (Poly1305 tag mismatch: wrong key, or "
+                "cover / payload / nonce / tag altered)", slices=bad, keyed=True, rows=rows)
+    return [framing.unpack_bits(rows[b], n_ct[b]) for b in range(B)], cover

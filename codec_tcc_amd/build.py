@@ -60,7 +60,7 @@ def _common_deps():
                    os.path.join(INC, "codec_tcc_gate.h"), os.path.join(INC, "codec_tcc_gvol.h"),
                    os.path.join(INC, "codec_tcc_tile.h"), os.path.join(INC, "codec_tcc_roi.h"),
                    os.path.join(INC, "codec_tcc_aead.h"), os.path.join(INC, "codec_tcc_blind.h"),
-                   os.path.join(INC, "codec_tcc_blind_auto.h")]
+                   os.path.join(INC, "codec_tcc_blind_auto.h"), os.path.join(INC, "codec_tcc_blind_keyed.h")]
 
 
 def _digest(paths, flags) -> str:

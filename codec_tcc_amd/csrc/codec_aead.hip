@@ -42,6 +42,7 @@
 // in the same call.
 #include "codec_common.h"
 #include "codec_tcc_aead.h"
+#include "codec_tcc_blind_keyed.h"
 
 #define P13_CHUNK (256u * 1024u)
 #define P13_T 256
@@ -133,10 +134,12 @@ __device__ __forceinline__ uint32_t row_bits(const int32_t* __restrict__ lengths
 }
 
 // VARIANT as above.  RELEASE: tg / tw are compared, ok[] written, and the stores are zero for a slice
-// whose tags differ (a mask, not a branch).
-template <int VARIANT, bool RELEASE>
+// whose tags differ (a mask, not a branch).  NONCES: slice b takes (g, nonce) from n12[b]
+// (codec_tcc_blind_keyed.h) instead of (index0 + b, ctx's nonce).
+template <int VARIANT, bool RELEASE, bool NONCES>
 __global__ __launch_bounds__(256) void k_chacha20_rows(const codec_aead_ctx* __restrict__ ctx, uint32_t index0,
-                                                       const u64* in, uint32_t row_words, uint32_t bpr, u64 nitems,
+                                                       const uint32_t* __restrict__ n12, const u64* in,
+                                                       uint32_t row_words, uint32_t bpr, u64 nitems,
                                                        const int32_t* __restrict__ lengths, u64* out,
                                                        const uint32_t* __restrict__ tg, const uint32_t* __restrict__ tw,
                                                        int32_t* __restrict__ ok) {
@@ -155,18 +158,19 @@ __global__ __launch_bounds__(256) void k_chacha20_rows(const codec_aead_ctx* __r
         keep = diff == 0 ? ~0ull : 0ull;
         if (blk == 0 && (VARIANT == 0 || q == 0)) ok[b] = diff == 0 ? 1 : 0;
     }
-    const uint32_t g = index0 + (uint32_t)b;
+    const uint32_t g = NONCES ? n12[3 * b] : index0 + (uint32_t)b;
+    const uint32_t n0 = NONCES ? n12[3 * b + 1] : ctx->nonce[0], n1 = NONCES ? n12[3 * b + 2] : ctx->nonce[1];
     const u64* ri = in + b * row_words;
     u64* ro = out + b * row_words;
     if constexpr (VARIANT == 1) {
         uint32_t o[4];
-        chacha_block_quad(ctx->key, blk + 1u, g, ctx->nonce[0], ctx->nonce[1], q, o);
+        chacha_block_quad(ctx->key, blk + 1u, g, n0, n1, q, o);
         const uint32_t w0 = blk * 8u + 2u * (uint32_t)q;
         if (w0 < row_words) ro[w0] = mask_word(ri[w0] ^ (((u64)o[1] << 32) | o[0]), w0, L) & keep;
         if (w0 + 1 < row_words) ro[w0 + 1] = mask_word(ri[w0 + 1] ^ (((u64)o[3] << 32) | o[2]), w0 + 1, L) & keep;
     } else {
         uint32_t x[16];
-        chacha_block(ctx->key, blk + 1u, g, ctx->nonce[0], ctx->nonce[1], x);
+        chacha_block(ctx->key, blk + 1u, g, n0, n1, x);
         u64 v[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -275,8 +279,10 @@ __device__ __forceinline__ P13 p13_wg_sum(const P13& x, u64* s_red) {
     return o;
 }
 
-// One workgroup per slice: one-time key, clamped r, power table.
+// One workgroup per slice: one-time key, clamped r, power table.  n12 (or NULL): the slices' own
+// (g, nonce) in place of (index0 + b, ctx's nonce).
 __global__ __launch_bounds__(P13_T) void k_poly1305_prep(const codec_aead_ctx* __restrict__ ctx, uint32_t index0,
+                                                         const uint32_t* __restrict__ n12,
                                                          const uint32_t* __restrict__ otk_in,
                                                          uint32_t* __restrict__ ws_s, uint32_t* __restrict__ ws_pw) {
     __shared__ uint32_t s_pw[P13_T + 1][5];
@@ -290,7 +296,8 @@ __global__ __launch_bounds__(P13_T) void k_poly1305_prep(const codec_aead_ctx* _
             for (int i = 0; i < 8; ++i) k[i] = otk_in[8 * b + i];
         } else {
             uint32_t x[16];
-            chacha_block(ctx->key, 0u, index0 + (uint32_t)b, ctx->nonce[0], ctx->nonce[1], x);
+            chacha_block(ctx->key, 0u, n12 ? n12[3 * b] : index0 + (uint32_t)b, n12 ? n12[3 * b + 1] : ctx->nonce[0],
+                         n12 ? n12[3 * b + 2] : ctx->nonce[1], x);
 #pragma unroll
             for (int i = 0; i < 8; ++i) k[i] = x[i];
         }
@@ -465,7 +472,8 @@ static bool p13_chunks(int32_t B, int64_t aad_bytes, u64* nch) {
 }
 
 template <bool RELEASE>
-static int chacha_launch(const codec_aead_ctx* ctx, int32_t B, uint32_t index0, const uint64_t* in, int32_t row_words,
+static int chacha_launch(const codec_aead_ctx* ctx, int32_t B, uint32_t index0, const uint32_t* n12, const uint64_t* in,
+                         int32_t row_words,
                          const int32_t* lengths, uint64_t* out, const uint32_t* tg, const uint32_t* tw, int32_t* ok,
                          hipStream_t st) {
     const uint32_t bpr = ((uint32_t)row_words + 7u) / 8u;
@@ -477,19 +485,24 @@ static int chacha_launch(const codec_aead_ctx* ctx, int32_t B, uint32_t index0, 
     const unsigned wg = threads < 256ull * 256ull ? 64u : 256u;   // small batches: one wave per workgroup, more CUs
     const unsigned grid = (unsigned)((threads + wg - 1) / wg);
     ProfScope prof(st, RELEASE ? CODEC_K_AEAD_RELEASE : CODEC_K_CHACHA20_ROWS);
-#define CL(V)                                                                                                       \
-    hipLaunchKernelGGL((k_chacha20_rows<V, RELEASE>), dim3(grid), dim3(wg), 0, st, ctx, index0, (const u64*)in,      \
+#define CL(V, N)                                                                                                    \
+    hipLaunchKernelGGL((k_chacha20_rows<V, RELEASE, N>), dim3(grid), dim3(wg), 0, st, ctx, index0, n12, (const u64*)in, \
                        (uint32_t)row_words, bpr, nitems, lengths, (u64*)out, tg, tw, ok)
-    if (variant == 0) CL(0);
-    else CL(1);
+    if (n12) {
+        if (variant == 0) CL(0, true);
+        else CL(1, true);
+    } else {
+        if (variant == 0) CL(0, false);
+        else CL(1, false);
+    }
 #undef CL
     LAUNCH_CHECK(RELEASE ? "k_aead_release" : "k_chacha20_rows");
     return 0;
 }
 
 static int p13_tags(const char* who, const codec_aead_ctx* ctx, const uint32_t* otk, int32_t B, uint32_t index0,
-                    const void* aad, int64_t aad_bytes, const uint64_t* ct_rows, int32_t row_words, const int32_t* lengths,
-                    uint32_t* tags, void* workspace, size_t workspace_bytes, void* stream) {
+                    const uint32_t* n12, bool per_slice, const void* aad, int64_t aad_bytes, const uint64_t* ct_rows,
+                    int32_t row_words, const int32_t* lengths, uint32_t* tags, void* workspace, size_t workspace_bytes, void* stream) {
     if (B < 1) return set_err(CODEC_EINVAL, "%s: bad batch B=%d", who, B);
     if (aad_bytes < 0 || aad_bytes > AEAD_MAX_AAD) return set_err(CODEC_EINVAL, "%s: aad_bytes=%lld outside 0 .. 2^32", who, (long long)aad_bytes);
     if ((aad == nullptr) != (aad_bytes == 0)) return set_err(CODEC_EINVAL, "%s: aad is NULL exactly when aad_bytes is 0", who);
@@ -501,10 +514,10 @@ static int p13_tags(const char* who, const codec_aead_ctx* ctx, const uint32_t* 
     }
     u64 nch = 0;
     if (!p13_chunks(B, aad_bytes, &nch)) return set_err(CODEC_EINVAL, "%s: batch too large", who);
-    if (!otk) {
+    if (!otk && !per_slice) {
         if (int rc = aead_index_check(index0, B, who)) return rc;
     }
-    if ((!ctx && !otk) || !tags || !workspace) return set_err(CODEC_EINVAL, "%s: NULL pointer argument", who);
+    if ((!ctx && !otk) || (per_slice && !n12) || !tags || !workspace) return set_err(CODEC_EINVAL, "%s: NULL pointer argument", who);
     const size_t need = codec_aead_workspace_bytes(B, aad_bytes, row_words);
     if (workspace_bytes < need) return set_err(CODEC_EINVAL, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
     hipStream_t st = as_stream(stream);
@@ -513,7 +526,7 @@ static int p13_tags(const char* who, const codec_aead_ctx* ctx, const uint32_t* 
     uint32_t* part = ws_pw + (size_t)B * P13_PW_STRIDE;
     {
         ProfScope prof(st, CODEC_K_POLY1305_PREP);
-        hipLaunchKernelGGL(k_poly1305_prep, dim3((unsigned)B), dim3(P13_T), 0, st, ctx, index0, otk, ws_s, ws_pw);
+        hipLaunchKernelGGL(k_poly1305_prep, dim3((unsigned)B), dim3(P13_T), 0, st, ctx, index0, n12, otk, ws_s, ws_pw);
         LAUNCH_CHECK("k_poly1305_prep");
     }
     if (nch) {
@@ -546,14 +559,14 @@ int codec_chacha20_rows(const codec_aead_ctx* ctx, int32_t B, uint32_t index0, c
     if (int rc = aead_rows_check(B, row_words, "codec_chacha20_rows")) return rc;
     if (int rc = aead_index_check(index0, B, "codec_chacha20_rows")) return rc;
     if (!ctx || !rows_in || !lengths || !rows_out) return set_err(CODEC_EINVAL, "codec_chacha20_rows: NULL pointer argument");
-    return chacha_launch<false>(ctx, B, index0, rows_in, row_words, lengths, rows_out, nullptr, nullptr, nullptr,
+    return chacha_launch<false>(ctx, B, index0, nullptr, rows_in, row_words, lengths, rows_out, nullptr, nullptr, nullptr,
                                 as_stream(stream));
 }
 
 int codec_poly1305_tags(const codec_aead_ctx* ctx, int32_t B, uint32_t index0, const void* aad, int64_t aad_bytes,
                         const uint64_t* ct_rows, int32_t row_words, const int32_t* lengths, uint32_t* tags, void* workspace,
                         size_t workspace_bytes, void* stream) {
-    return p13_tags("codec_poly1305_tags", ctx, nullptr, B, index0, aad, aad_bytes, ct_rows, row_words, lengths, tags,
+    return p13_tags("codec_poly1305_tags", ctx, nullptr, B, index0, nullptr, false, aad, aad_bytes, ct_rows, row_words, lengths, tags,
                     workspace, workspace_bytes, stream);
 }
 
@@ -561,7 +574,7 @@ int codec_poly1305_tags_otk(const uint32_t* otk, int32_t B, const void* aad, int
                             int32_t row_words, const int32_t* lengths, uint32_t* tags, void* workspace,
                             size_t workspace_bytes, void* stream) {
     if (!otk) return set_err(CODEC_EINVAL, "codec_poly1305_tags_otk: NULL pointer argument");
-    return p13_tags("codec_poly1305_tags_otk", nullptr, otk, B, 0u, aad, aad_bytes, ct_rows, row_words, lengths, tags,
+    return p13_tags("codec_poly1305_tags_otk", nullptr, otk, B, 0u, nullptr, false, aad, aad_bytes, ct_rows, row_words, lengths, tags,
                     workspace, workspace_bytes, stream);
 }
 
@@ -572,7 +585,35 @@ int codec_aead_release(const codec_aead_ctx* ctx, int32_t B, uint32_t index0, co
     if (int rc = aead_index_check(index0, B, "codec_aead_release")) return rc;
     if (!ctx || !ct_rows || !lengths || !pt_rows_out) return set_err(CODEC_EINVAL, "codec_aead_release: NULL pointer argument");
     if (!tags_got || !tags_want || !ok) return set_err(CODEC_EINVAL, "codec_aead_release: NULL tag or ok pointer");
-    return chacha_launch<true>(ctx, B, index0, ct_rows, row_words, lengths, pt_rows_out, tags_got, tags_want, ok,
+    return chacha_launch<true>(ctx, B, index0, nullptr, ct_rows, row_words, lengths, pt_rows_out, tags_got, tags_want, ok,
+                               as_stream(stream));
+}
+
+// ---- include/codec_tcc_blind_keyed.h: the same passes with one nonce per slice
+int codec_chacha20_rows_n(const codec_aead_ctx* ctx, int32_t B, const uint32_t* nonce12, const uint64_t* rows_in,
+                          int32_t row_words, const int32_t* lengths, uint64_t* rows_out, void* stream) {
+    if (int rc = aead_rows_check(B, row_words, "codec_chacha20_rows_n")) return rc;
+    if (!ctx || !nonce12 || !rows_in || !lengths || !rows_out)
+        return set_err(CODEC_EINVAL, "codec_chacha20_rows_n: NULL pointer argument");
+    return chacha_launch<false>(ctx, B, 0u, nonce12, rows_in, row_words, lengths, rows_out, nullptr, nullptr, nullptr,
+                                as_stream(stream));
+}
+
+int codec_poly1305_tags_n(const codec_aead_ctx* ctx, int32_t B, const uint32_t* nonce12, const void* aad,
+                          int64_t aad_bytes, const uint64_t* ct_rows, int32_t row_words, const int32_t* lengths,
+                          uint32_t* tags, void* workspace, size_t workspace_bytes, void* stream) {
+    return p13_tags("codec_poly1305_tags_n", ctx, nullptr, B, 0u, nonce12, true, aad, aad_bytes, ct_rows, row_words, lengths,
+                    tags, workspace, workspace_bytes, stream);
+}
+
+int codec_aead_release_n(const codec_aead_ctx* ctx, int32_t B, const uint32_t* nonce12, const uint32_t* tags_got,
+                         const uint32_t* tags_want, const uint64_t* ct_rows, int32_t row_words, const int32_t* lengths,
+                         uint64_t* pt_rows_out, int32_t* ok, void* stream) {
+    if (int rc = aead_rows_check(B, row_words, "codec_aead_release_n")) return rc;
+    if (!ctx || !nonce12 || !ct_rows || !lengths || !pt_rows_out)
+        return set_err(CODEC_EINVAL, "codec_aead_release_n: NULL pointer argument");
+    if (!tags_got || !tags_want || !ok) return set_err(CODEC_EINVAL, "codec_aead_release_n: NULL tag or ok pointer");
+    return chacha_launch<true>(ctx, B, 0u, nonce12, ct_rows, row_words, lengths, pt_rows_out, tags_got, tags_want, ok,
                                as_stream(stream));
 }
 

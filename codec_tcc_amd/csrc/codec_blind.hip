@@ -28,10 +28,16 @@
 //   k_blind_plan_auto  one workgroup per slice, one wave per T: k_blind_plan's rule with wave scans, the
 //                    first T with status 0 (or tmax's refusal), the capacity curve.
 // k_blind_splice, the ROI embed and k_blind_pack then run as for a fixed T, on the per-slice T array.
+// Keyed (include/codec_tcc_blind_keyed.h; tests/pee_blind_keyed_spec.py): the user stream is
+// a 224-bit frame (nonce12, tag) and the ciphertext row.  The plan kernels add the frame's bits to the
+// length, k_blind_splice<.., true> reads the stream through the frame (no shifted copy of the row is
+// made), k_blind_pack writes the flags it is given; k_blind_frames builds the frames from the ctx block
+// and the tags, k_blind_unframe splits the rows k_blind_restore wrote into nonce12, tag and ciphertext.
 // Every kernel clamps what it reads from device memory to the slice, the row and the map.
 #include "codec_common.h"
 #include "codec_tcc_blind.h"
 #include "codec_tcc_blind_auto.h"
+#include "codec_tcc_blind_keyed.h"
 
 #include <limits.h>
 
@@ -396,9 +402,15 @@ __device__ void bl_plan_write(int b, const BlPlan& p, long long n_user, int thr,
     gs[b] = CODEC_PEE_GATE_MAX;
 }
 
-// one workgroup per slice.  lengths NULL: 0 user bits each; a length is clamped to 0 .. user_bits.
+// n_user of slice b: lengths NULL: 0 user bits; else the length clamped to 0 .. user_bits, behind
+// frame_bits bits of frame (0, or a keyed slice's 224)
+__device__ __forceinline__ long long bl_n_user(const int32_t* __restrict__ lengths, int b, int user_bits, int frame_bits) {
+    return lengths ? (long long)frame_bits + (long long)min(max(lengths[b], 0), user_bits) : 0;
+}
+
+// one workgroup per slice
 __global__ __launch_bounds__(256) void k_blind_plan(const uint2* __restrict__ rows, const int32_t* __restrict__ lengths,
-                                                    int user_bits, int H, int W, int thr, int max_entries,
+                                                    int user_bits, int frame_bits, int H, int W, int thr, int max_entries,
                                                     long long row_bits, int32_t* __restrict__ info,
                                                     int32_t* __restrict__ rect, int32_t* __restrict__ lens,
                                                     int32_t* __restrict__ ts, int32_t* __restrict__ gs) {
@@ -407,7 +419,7 @@ __global__ __launch_bounds__(256) void k_blind_plan(const uint2* __restrict__ ro
     __shared__ int s_cap;
     const int b = blockIdx.x;
     const int hc = H / 2;
-    const long long n_user = lengths ? (long long)min(max(lengths[b], 0), user_bits) : 0;
+    const long long n_user = bl_n_user(lengths, b, user_bits, frame_bits);
     const BlPlan p = bl_plan_rows(rows + (size_t)b * hc, hc, n_user, W, max_entries, row_bits, sh, &s_first, &s_cap);
     if (threadIdx.x == 0) bl_plan_write(b, p, n_user, thr, p.cap, H, W, info, rect, lens, ts, gs);
 }
@@ -416,14 +428,14 @@ __global__ __launch_bounds__(256) void k_blind_plan(const uint2* __restrict__ ro
 // [B][tmax][hc].  The slice takes the first T whose plan has status 0, else the refusal of tmax
 // (t_out 0); info's last word is the largest capacity over the T's, curve (or NULL) [B][tmax] holds each.
 __global__ __launch_bounds__(64 * CODEC_PEE_BLIND_TMAX) void k_blind_plan_auto(
-    const uint2* __restrict__ rows, const int32_t* __restrict__ lengths, int user_bits, int H, int W, int tmax,
-    int max_entries, long long row_bits, int32_t* __restrict__ info, int32_t* __restrict__ t_out,
+    const uint2* __restrict__ rows, const int32_t* __restrict__ lengths, int user_bits, int frame_bits, int H, int W,
+    int tmax, int max_entries, long long row_bits, int32_t* __restrict__ info, int32_t* __restrict__ t_out,
     int32_t* __restrict__ curve, int32_t* __restrict__ rect, int32_t* __restrict__ lens, int32_t* __restrict__ ts,
     int32_t* __restrict__ gs) {
     __shared__ BlPlan s_plan[CODEC_PEE_BLIND_TMAX];
     const int b = blockIdx.x, wv = threadIdx.x >> 6;
     const int hc = H / 2;
-    const long long n_user = lengths ? (long long)min(max(lengths[b], 0), user_bits) : 0;
+    const long long n_user = bl_n_user(lengths, b, user_bits, frame_bits);
     tmax = min(max(tmax, 1), CODEC_PEE_BLIND_TMAX);
     if (wv < tmax) {
         const BlPlan p = bl_plan_rows_wave(rows + ((size_t)b * tmax + wv) * hc, hc, n_user, W, max_entries, row_bits);
@@ -451,10 +463,28 @@ __device__ __forceinline__ u64 bl_user_word(const u64* __restrict__ row, long lo
     return v;
 }
 
-// payload row = displaced LSBs (side bit i = bit 0 of pixel npx - 1 - i) || user bits; grid (row words / 256, B)
-template <typename T>
+// word k of a keyed slice's user stream (codec_tcc_blind_keyed.h): the frame's seven 32-bit words f,
+// then the ciphertext row ct, 32 bits off a word; bits past n_user (frame included) cleared
+__device__ __forceinline__ u64 bl_keyed_word(const u64* __restrict__ ct, int ct_words, const uint32_t* __restrict__ f,
+                                             long long k, long long n_user) {
+    const long long nw = (n_user + 63) >> 6;
+    if (k < 0 || k >= nw) return 0ull;
+    const long long n_ct = min(max(n_user - CODEC_PEE_BLIND_FRAME_BITS, 0LL), 64LL * ct_words);
+    u64 v;
+    if (k < 3) v = (u64)f[2 * k] | ((u64)f[2 * k + 1] << 32);
+    else if (k == 3) v = (u64)f[6] | (bl_user_word(ct, 0, n_ct) << 32);
+    else v = (bl_user_word(ct, k - 4, n_ct) >> 32) | (bl_user_word(ct, k - 3, n_ct) << 32);
+    const int tail = (int)(n_user & 63);
+    if (k == nw - 1 && tail) v &= (1ull << tail) - 1ull;
+    return v;
+}
+
+// payload row = displaced LSBs (side bit i = bit 0 of pixel npx - 1 - i) || user bits; grid (row words / 256, B).
+// KEYED: the user bits are frames[b] || user[b] (bl_keyed_word), info's n_user counting both.
+template <typename T, bool KEYED>
 __global__ __launch_bounds__(256) void k_blind_splice(const T* __restrict__ img, long long npx,
                                                       const u64* __restrict__ user, int user_words,
+                                                      const uint32_t* __restrict__ frames,
                                                       const int32_t* __restrict__ info, u64* __restrict__ out,
                                                       int row_words) {
     const int b = blockIdx.y;
@@ -471,13 +501,19 @@ __global__ __launch_bounds__(256) void k_blind_splice(const T* __restrict__ img,
                 if (lo + j < n_side) v |= (u64)(src[npx - 1 - (lo + j)] & 1) << j;
         if (lo + 64 > n_side && n_user > 0) {
             const u64* row = user + (size_t)b * user_words;
+            auto word = [&](long long k) -> u64 {
+                if constexpr (KEYED)
+                    return bl_keyed_word(row, user_words, frames + (size_t)b * CODEC_PEE_BLIND_FRAME_WORDS, k, n_user);
+                else
+                    return bl_user_word(row, k, n_user);
+            };
             const long long q = lo - n_side;   // the user bit at position lo (negative: the row's first user bit lies inside)
             if (q >= 0) {
                 const int sh = (int)(q & 63);
-                v |= bl_user_word(row, q >> 6, n_user) >> sh;
-                if (sh) v |= bl_user_word(row, (q >> 6) + 1, n_user) << (64 - sh);
+                v |= word(q >> 6) >> sh;
+                if (sh) v |= word((q >> 6) + 1) << (64 - sh);
             } else {
-                v |= bl_user_word(row, 0, n_user) << (int)(-q);
+                v |= word(0) << (int)(-q);
             }
         }
     }
@@ -501,12 +537,13 @@ __device__ __forceinline__ uint32_t bl_get_word(const T* __restrict__ px, long l
 }
 
 // one workgroup per slice, after the ROI embed: header, entries, padding; info's `end`.  ts: the
-// plan's T per slice (clamped to the header's 1..64)
+// plan's T per slice (clamped to the header's 1..64); flags: the header's (word 5 is crc[b] when they
+// have CODEC_PEE_BLIND_FLAG_CRC and crc is given, else 0)
 template <typename T>
 __global__ __launch_bounds__(256) void k_blind_pack(T* __restrict__ stego, long long npx, int nc,
                                                     const int32_t* __restrict__ ts, int maxval,
                                                     const codec_pee_meta* __restrict__ meta, const u64* __restrict__ lm,
-                                                    int lm_words, const uint32_t* __restrict__ crc,
+                                                    int lm_words, const uint32_t* __restrict__ crc, uint32_t flags,
                                                     int32_t* __restrict__ info) {
     __shared__ uint32_t sh[256 / 64 + 1];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -519,8 +556,8 @@ __global__ __launch_bounds__(256) void k_blind_pack(T* __restrict__ stego, long 
         const int thr = min(max(ts[b], 1), 64);
         const uint32_t hw[CODEC_PEE_BLIND_HDR_WORDS] = {
             CODEC_PEE_BLIND_MAGIC,
-            (uint32_t)thr | ((crc ? (uint32_t)CODEC_PEE_BLIND_FLAG_CRC : 0u) << 8) | ((uint32_t)maxval << 16),
-            (uint32_t)I[1], (uint32_t)E, (uint32_t)end, crc ? crc[b] : 0u};
+            (uint32_t)thr | ((flags & 0xFFu) << 8) | ((uint32_t)maxval << 16),
+            (uint32_t)I[1], (uint32_t)E, (uint32_t)end, (crc && (flags & CODEC_PEE_BLIND_FLAG_CRC)) ? crc[b] : 0u};
         bl_put_word(px, npx, 32LL * tid, hw[tid]);
     }
     const int nwords = (end + 64) >> 6;   // 0 for end = -1
@@ -612,6 +649,45 @@ __global__ __launch_bounds__(256) void k_blind_restore(T* __restrict__ cover, lo
     }
 }
 
+// ---- keyed: frames in, frames out (include/codec_tcc_blind_keyed.h)
+// one thread per frame word: (index0 + b, the ctx block's nonce words, the slice's tag)
+__global__ __launch_bounds__(256) void k_blind_frames(const codec_aead_ctx* __restrict__ ctx, int B, uint32_t index0,
+                                                      const uint32_t* __restrict__ tags, uint32_t* __restrict__ frames) {
+    const int t = (int)blockIdx.x * 256 + threadIdx.x;
+    if (t >= CODEC_PEE_BLIND_FRAME_WORDS * B) return;
+    const int b = t / CODEC_PEE_BLIND_FRAME_WORDS, k = t - b * CODEC_PEE_BLIND_FRAME_WORDS;
+    frames[t] = k == 0 ? index0 + (uint32_t)b : k < 3 ? ctx->nonce[k - 1] : tags[4 * b + (k - 3)];
+}
+
+// the user rows of k_blind_restore -> nonce12, tag, ciphertext rows and lengths; grid (ct words / 256, B).
+// Thread t writes ciphertext word t; the first seven threads of a slice also write its frame words.
+__global__ __launch_bounds__(256) void k_blind_unframe(const u64* __restrict__ rows, int user_words,
+                                                       const uint32_t* __restrict__ hdr, uint32_t* __restrict__ n12,
+                                                       uint32_t* __restrict__ tags, u64* __restrict__ ct, int ct_words,
+                                                       int32_t* __restrict__ ct_lengths) {
+    const int b = blockIdx.y;
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    const u64* row = rows + (size_t)b * user_words;
+    const long long n_user = min((long long)hdr[8 * b + 2], 64LL * user_words);
+    const long long n_ct = min(max(n_user - CODEC_PEE_BLIND_FRAME_BITS, 0LL), 64LL * ct_words);
+    if (t < CODEC_PEE_BLIND_FRAME_WORDS) {
+        const int k = (int)(t >> 1);
+        const u64 w = k < user_words ? row[k] : 0ull;
+        const uint32_t v = (t & 1) ? (uint32_t)(w >> 32) : (uint32_t)w;
+        if (t < 3) n12[3 * b + t] = v;
+        else tags[4 * b + (t - 3)] = v;
+    }
+    if (t == 0) ct_lengths[b] = (int32_t)n_ct;
+    if (t < ct_words) {
+        u64 v = t + 3 < user_words ? row[t + 3] >> 32 : 0ull;
+        if (t + 4 < user_words) v |= row[t + 4] << 32;
+        const long long left = n_ct - 64 * t;   // ciphertext bits from this word on
+        if (left <= 0) v = 0ull;
+        else if (left < 64) v &= (1ull << left) - 1ull;
+        ct[(size_t)b * ct_words + t] = v;
+    }
+}
+
 // the checks every entry shares; `ws`: the entry takes the workspace
 static int blind_check(const codec_pee_params* P, int32_t max_entries, bool ws, size_t* base, const char* who,
                        int32_t tmax = 1) {
@@ -630,9 +706,9 @@ static int blind_check(const codec_pee_params* P, int32_t max_entries, bool ws, 
     return 0;
 }
 
-// row table and plan on the workspace's arrays (lengths NULL: 0 bits each)
+// row table and plan on the workspace's arrays (lengths NULL: 0 bits each; frame_bits: bl_n_user)
 static int blind_plan(const codec_pee_params* P, const BlWs& L, const void* cover, const int32_t* lengths, int user_bits,
-                      long long row_bits, int32_t max_entries, int32_t* info, char* ws, hipStream_t st) {
+                      int frame_bits, long long row_bits, int32_t max_entries, int32_t* info, char* ws, hipStream_t st) {
     uint2* rows = reinterpret_cast<uint2*>(ws + L.rows);
     const int hc = P->H / 2;
     if (hc > 0) {
@@ -647,8 +723,8 @@ static int blind_plan(const codec_pee_params* P, const BlWs& L, const void* cove
         });
         LAUNCH_CHECK("k_blind_rows");
     }
-    hipLaunchKernelGGL(k_blind_plan, dim3((unsigned)P->B), dim3(256), 0, st, rows, lengths, user_bits, P->H, P->W, P->T,
-                       (int)max_entries, row_bits, info, reinterpret_cast<int32_t*>(ws + L.rect),
+    hipLaunchKernelGGL(k_blind_plan, dim3((unsigned)P->B), dim3(256), 0, st, rows, lengths, user_bits, frame_bits, P->H,
+                       P->W, P->T, (int)max_entries, row_bits, info, reinterpret_cast<int32_t*>(ws + L.rect),
                        reinterpret_cast<int32_t*>(ws + L.lens), reinterpret_cast<int32_t*>(ws + L.ts),
                        reinterpret_cast<int32_t*>(ws + L.gs));
     LAUNCH_CHECK("k_blind_plan");
@@ -658,7 +734,7 @@ static int blind_plan(const codec_pee_params* P, const BlWs& L, const void* cove
 // the same for every T in 1..tmax: one pass over the cover, the table [B][tmax][hc], the plan that
 // picks T per slice (t_out; curve or NULL)
 static int blind_plan_auto(const codec_pee_params* P, const BlWs& L, const void* cover, const int32_t* lengths,
-                           int user_bits, long long row_bits, int32_t tmax, int32_t max_entries, int32_t* info,
+                           int user_bits, int frame_bits, long long row_bits, int32_t tmax, int32_t max_entries, int32_t* info,
                            int32_t* t_out, int32_t* curve, char* ws, hipStream_t st) {
     uint2* rows = reinterpret_cast<uint2*>(ws + L.rows);
     const int hc = P->H / 2;
@@ -675,17 +751,20 @@ static int blind_plan_auto(const codec_pee_params* P, const BlWs& L, const void*
         });
         LAUNCH_CHECK("k_blind_rows_auto");
     }
-    hipLaunchKernelGGL(k_blind_plan_auto, dim3((unsigned)P->B), dim3(64 * CODEC_PEE_BLIND_TMAX), 0, st, rows, lengths, user_bits, P->H, P->W,
-                       (int)tmax, (int)max_entries, row_bits, info, t_out, curve, reinterpret_cast<int32_t*>(ws + L.rect),
+    hipLaunchKernelGGL(k_blind_plan_auto, dim3((unsigned)P->B), dim3(64 * CODEC_PEE_BLIND_TMAX), 0, st, rows, lengths,
+                       user_bits, frame_bits, P->H, P->W, (int)tmax, (int)max_entries, row_bits, info, t_out, curve,
+                       reinterpret_cast<int32_t*>(ws + L.rect),
                        reinterpret_cast<int32_t*>(ws + L.lens), reinterpret_cast<int32_t*>(ws + L.ts),
                        reinterpret_cast<int32_t*>(ws + L.gs));
     LAUNCH_CHECK("k_blind_plan_auto");
     return 0;
 }
 
-// after a plan: splice, the ROI embed on the plan's arrays, pack
+// after a plan: splice, the ROI embed on the plan's arrays, pack.  frames (or NULL): a keyed embed's, the
+// user stream being frames[b] || payload[b]; flags: the header's
 static int blind_embed_planned(const codec_pee_params* P, const BlWs& L, const void* cover, void* stego,
-                               const uint64_t* payload, int32_t user_words, const uint32_t* crc, int32_t* info,
+                               const uint64_t* payload, int32_t user_words, const uint32_t* frames, const uint32_t* crc,
+                               uint32_t flags, int32_t* info,
                                codec_pee_meta* meta, uint64_t* lm, void* workspace, size_t workspace_bytes, void* stream) {
     hipStream_t st = as_stream(stream);
     char* ws = static_cast<char*>(workspace);
@@ -695,8 +774,11 @@ static int blind_embed_planned(const codec_pee_params* P, const BlWs& L, const v
         dim3 grid((unsigned)((P->payload_words + 255) / 256), (unsigned)P->B);
         pee_pixel(P->bytes, [&](auto px) {
             using TT = decltype(px);
-            hipLaunchKernelGGL(k_blind_splice<TT>, grid, dim3(256), 0, st, static_cast<const TT*>(cover), npx,
-                               reinterpret_cast<const u64*>(payload), (int)user_words, info, rows, P->payload_words);
+            auto go = [&](auto kern) {
+                hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, static_cast<const TT*>(cover), npx,
+                                   reinterpret_cast<const u64*>(payload), (int)user_words, frames, info, rows, P->payload_words);
+            };
+            pee_flag(frames != nullptr, [&](auto k) { go(k_blind_splice<TT, k()>); });
         });
         LAUNCH_CHECK("k_blind_splice");
     }
@@ -709,7 +791,7 @@ static int blind_embed_planned(const codec_pee_params* P, const BlWs& L, const v
     pee_pixel(P->bytes, [&](auto px) {
         using TT = decltype(px);
         hipLaunchKernelGGL(k_blind_pack<TT>, dim3((unsigned)P->B), dim3(256), 0, st, static_cast<TT*>(stego), npx, nc, ts,
-                           P->maxval, meta, reinterpret_cast<const u64*>(lm), P->lm_words, crc, info);
+                           P->maxval, meta, reinterpret_cast<const u64*>(lm), P->lm_words, crc, flags, info);
     });
     LAUNCH_CHECK("k_blind_pack");
     return 0;
@@ -735,7 +817,7 @@ int codec_pee_blind_plan(const codec_pee_params* P, const void* cover, const int
     // workspace in use for a larger shape they fall inside that shape's state
     if ((rc = pee_workspace_enter(P, workspace, stream))) return rc;
     // no row is filled here: the plan and the capacity are the format's own, unbounded by a row width
-    return blind_plan(P, L, cover, lengths, INT_MAX, 1LL << 40, max_entries, info, static_cast<char*>(workspace),
+    return blind_plan(P, L, cover, lengths, INT_MAX, 0, 1LL << 40, max_entries, info, static_cast<char*>(workspace),
                       as_stream(stream));
 }
 
@@ -753,10 +835,11 @@ int codec_pee_blind_embed(const codec_pee_params* P, const void* cover, void* st
     const BlWs L = bl_ws(P, base);
     if (workspace_bytes < L.total) return set_err(CODEC_EINVAL, "codec_pee_blind_embed: workspace too small");
     if ((rc = pee_workspace_enter(P, workspace, stream))) return rc;
-    if ((rc = blind_plan(P, L, cover, lengths, 64 * user_words, 64LL * P->payload_words, max_entries, info,
+    if ((rc = blind_plan(P, L, cover, lengths, 64 * user_words, 0, 64LL * P->payload_words, max_entries, info,
                          static_cast<char*>(workspace), as_stream(stream))))
         return rc;
-    return blind_embed_planned(P, L, cover, stego, payload, user_words, crc, info, meta, lm, workspace, workspace_bytes, stream);
+    return blind_embed_planned(P, L, cover, stego, payload, user_words, nullptr, crc, crc ? CODEC_PEE_BLIND_FLAG_CRC : 0u, info,
+                               meta, lm, workspace, workspace_bytes, stream);
 }
 
 int codec_pee_blind_headers(const codec_pee_params* P, const void* stego, uint32_t* hdr_out, void* stream) {
@@ -840,7 +923,7 @@ int codec_pee_blind_plan_auto(const codec_pee_params* P, const void* cover, cons
     const BlWs L = bl_ws(P, base, tmax);
     if (workspace_bytes < L.total) return set_err(CODEC_EINVAL, "codec_pee_blind_plan_auto: workspace too small");
     if ((rc = pee_workspace_enter(P, workspace, stream))) return rc;
-    return blind_plan_auto(P, L, cover, lengths, INT_MAX, 1LL << 40, tmax, max_entries, info, t_out, curve,
+    return blind_plan_auto(P, L, cover, lengths, INT_MAX, 0, 1LL << 40, tmax, max_entries, info, t_out, curve,
                            static_cast<char*>(workspace), as_stream(stream));
 }
 
@@ -859,10 +942,72 @@ int codec_pee_blind_embed_auto(const codec_pee_params* P, const void* cover, voi
     const BlWs L = bl_ws(P, base, tmax);
     if (workspace_bytes < L.total) return set_err(CODEC_EINVAL, "codec_pee_blind_embed_auto: workspace too small");
     if ((rc = pee_workspace_enter(P, workspace, stream))) return rc;
-    if ((rc = blind_plan_auto(P, L, cover, lengths, 64 * user_words, 64LL * P->payload_words, tmax, max_entries, info, t_out,
+    if ((rc = blind_plan_auto(P, L, cover, lengths, 64 * user_words, 0, 64LL * P->payload_words, tmax, max_entries, info, t_out,
                               nullptr, static_cast<char*>(workspace), as_stream(stream))))
         return rc;
-    return blind_embed_planned(P, L, cover, stego, payload, user_words, crc, info, meta, lm, workspace, workspace_bytes, stream);
+    return blind_embed_planned(P, L, cover, stego, payload, user_words, nullptr, crc, crc ? CODEC_PEE_BLIND_FLAG_CRC : 0u, info,
+                               meta, lm, workspace, workspace_bytes, stream);
+}
+
+// ---- include/codec_tcc_blind_keyed.h
+int codec_pee_blind_frames(const codec_aead_ctx* ctx, int32_t B, uint32_t index0, const uint32_t* tags,
+                           uint32_t* frames_out, void* stream) {
+    if (B < 1) return set_err(CODEC_EINVAL, "codec_pee_blind_frames: bad batch B=%d", B);
+    if (!(index0 == CODEC_AEAD_STREAM_INDEX && B == 1) && (u64)index0 + (u64)B > (1ull << 31))
+        return set_err(CODEC_EINVAL, "codec_pee_blind_frames: slice indices %u .. %llu are not all < 2^31", index0,
+                       (u64)index0 + (u64)B - 1);
+    if (!ctx || !tags || !frames_out) return set_err(CODEC_EINVAL, "codec_pee_blind_frames: NULL pointer argument");
+    const long long n = (long long)CODEC_PEE_BLIND_FRAME_WORDS * B;
+    hipLaunchKernelGGL(k_blind_frames, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), ctx, (int)B, index0,
+                       tags, frames_out);
+    LAUNCH_CHECK("k_blind_frames");
+    return 0;
+}
+
+int codec_pee_blind_embed_keyed(const codec_pee_params* P, const void* cover, void* stego, const uint32_t* frames,
+                                const uint64_t* ct_rows, int32_t ct_words, const int32_t* lengths, int32_t tmax,
+                                int32_t max_entries, int32_t* info, int32_t* ts, codec_pee_meta* meta, uint64_t* lm,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "codec_pee_blind_embed_keyed";
+    if (P && max_entries >= 0 && max_entries <= CODEC_PEE_BLIND_MAX_ENTRIES && (tmax < 0 || tmax > CODEC_PEE_BLIND_TMAX))
+        return set_err(CODEC_EINVAL, "%s: tmax must be in 0..16 (0: the fixed T)", who);
+    size_t base = 0;
+    int rc = blind_check(P, max_entries, true, &base, who, tmax ? tmax : 1);
+    if (rc) return rc;
+    if (P->payload_words < CODEC_PEE_BLIND_ROW_WORDS(CODEC_PEE_BLIND_FRAME_BITS, max_entries))
+        return set_err(CODEC_EINVAL, "%s: payload_words is below the row of the side bits and the 224 frame bits", who);
+    if (!cover || !stego || !frames || !ct_rows || !lengths || !info || (tmax && !ts) || !meta || !lm || !workspace)
+        return set_err(CODEC_EINVAL, "%s: NULL pointer argument", who);
+    if (cover == stego) return set_err(CODEC_EINVAL, "%s: out of place only (cover == stego)", who);
+    if (ct_words < 1 || ct_words > (1 << 24)) return set_err(CODEC_EINVAL, "%s: ct_words must be in 1..2^24", who);
+    const BlWs L = bl_ws(P, base, tmax ? tmax : 1);
+    if (workspace_bytes < L.total) return set_err(CODEC_EINVAL, "%s: workspace too small", who);
+    if ((rc = pee_workspace_enter(P, workspace, stream))) return rc;
+    const long long row_bits = 64LL * P->payload_words;
+    const int fb = CODEC_PEE_BLIND_FRAME_BITS;
+    char* ws = static_cast<char*>(workspace);
+    rc = tmax ? blind_plan_auto(P, L, cover, lengths, 64 * ct_words, fb, row_bits, tmax, max_entries, info, ts, nullptr, ws,
+                                as_stream(stream))
+              : blind_plan(P, L, cover, lengths, 64 * ct_words, fb, row_bits, max_entries, info, ws, as_stream(stream));
+    if (rc) return rc;
+    return blind_embed_planned(P, L, cover, stego, ct_rows, ct_words, frames, nullptr, CODEC_PEE_BLIND_FLAG_KEYED, info, meta,
+                               lm, workspace, workspace_bytes, stream);
+}
+
+int codec_pee_blind_unframe(int32_t B, const uint64_t* rows, int32_t user_words, const uint32_t* hdr,
+                            uint32_t* nonce12_out, uint32_t* tags_out, uint64_t* ct_out, int32_t ct_words,
+                            int32_t* ct_lengths_out, void* stream) {
+    if (B < 1 || B > 65535) return set_err(CODEC_EINVAL, "codec_pee_blind_unframe: bad batch B=%d (1..65535)", B);
+    if (user_words < 1 || user_words > (1 << 24) || ct_words < 1 || ct_words > (1 << 24))
+        return set_err(CODEC_EINVAL, "codec_pee_blind_unframe: user_words and ct_words must be in 1..2^24");
+    if (!rows || !hdr || !nonce12_out || !tags_out || !ct_out || !ct_lengths_out)
+        return set_err(CODEC_EINVAL, "codec_pee_blind_unframe: NULL pointer argument");
+    dim3 grid((unsigned)((ct_words + 255) / 256), (unsigned)B);
+    hipLaunchKernelGGL(k_blind_unframe, grid, dim3(256), 0, as_stream(stream), reinterpret_cast<const u64*>(rows),
+                       (int)user_words, hdr, nonce12_out, tags_out, reinterpret_cast<u64*>(ct_out), (int)ct_words,
+                       ct_lengths_out);
+    LAUNCH_CHECK("k_blind_unframe");
+    return 0;
 }
 
 }  // extern "C"

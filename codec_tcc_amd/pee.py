@@ -28,7 +28,8 @@ it, decode() needs no configuration.
 Keyed embedding (include/codec_tcc_aead.h, aead.py): codec.embed(..., key=, nonce=)
 encrypts the payload rows with ChaCha20 and tags (cover, ciphertext) with Poly1305 per slice;
 codec.decode(enc, key=) authenticates the restored cover and the extracted rows on the device
-before any plaintext leaves it.
+before any plaintext leaves it.  codec.embed_blind_keyed / decode_blind_keyed (blind.py)
+do the same for a blind stego, which then carries its nonce and tag itself.
 """
 from __future__ import annotations
 
@@ -683,6 +684,32 @@ class PeeCodec:
         return _blind.embed_auto(self, covers, payloads, tmax=tmax, stego=stego, packed=packed, checksum=checksum,
                                  max_entries=max_entries, check=check)
 
+    def embed_blind_keyed(self, covers, payloads, *, key, nonce=None, index0: int = 0, tmax=None, stego=None, packed=None,
+                          max_entries: int = 256, check: bool = True):
+        """(stego, info, ts): a blind stego that is confidential and authenticated under a 32-byte key
+        (include/codec_tcc_blind_keyed.h).  Each slice's user bits are a 224-bit frame --
+        nonce12 = LE32(index0 + b) || nonce, then the Poly1305 tag of (cover, ciphertext), the tag
+        embed(key=) computes -- and the ChaCha20 ciphertext of its payload; header flag bit 1 marks it.
+        info[:, 1] is the header's n_user, frame included.  tmax=None: the codec's fixed T (ts holds
+        it); tmax in 1..16: T chosen per slice as embed_blind_auto does.  nonce: 8 bytes, drawn from
+        os.urandom when None; never reuse one under a key.  Key, nonce, index and every rule of
+        embed_blind are judged before anything is queued; the queue order is chacha20_rows,
+        poly1305_tags, the frames, the embed, and check=False makes no host round trip.  There is no
+        CRC beside the tag."""
+        return _blind.embed_keyed(self, covers, payloads, key=key, nonce=nonce, index0=index0, tmax=tmax, stego=stego,
+                                  packed=packed, max_entries=max_entries, check=check)
+
+    def decode_blind_keyed(self, stego, key, *, cover=None, verify=True):
+        """(bits per slice, cover) of embed_blind_keyed's stegos from the pixels and the key; the
+        slices of a batch may come from different calls, each brings its nonce and index.  After the
+        header read-back (ValueError naming the slices whose flags are not exactly 2 or whose n_user is
+        below 224 -- an unkeyed stego is decode_blind's) everything runs on the device: extract,
+        unframe, the tag of (restored cover, ciphertext), release.  IntegrityError(keyed=True,
+        slices=...) names the slices whose tag fails; their plaintext never reaches the host (rows
+        holds the device's zeros).  verify=False decrypts without the tag pass; 'require' is
+        satisfied by the tag."""
+        return _blind.decode_keyed(self, stego, key, cover=cover, verify=verify)
+
     def blind_capacity_curve(self, covers, tmax=None, max_entries: int = 256):
         """int32 [B, tmax] device tensor: blind_capacity at every T in 1..tmax (None: this codec's
         tmax, at most 16), from one pass over the covers."""
@@ -1092,6 +1119,47 @@ def decode_blind(stego, verify=True, *, restore: bool = True):
     dt = "uint16" if _elem_bytes(stego) == 2 else "uint8"
     codec = _codec_for(tuple(stego.shape), dt, T=2, tmax=16, maxval=None)
     bits, cover = codec.decode_blind(stego, verify=verify)
+    return bits, (cover if restore else None)
+
+
+def encode_blind_keyed(covers, payloads: Sequence, key, *, T: int = 2, tmax=None, nonce=None, index0: int = 0,
+                       maxval: Optional[int] = None, max_entries: int = 256):
+    """Keyed blind MED-PEE embed of one payload per slice (PeeCodec.embed_blind_keyed): (stego, info,
+    ts), a stego that decode_blind_keyed reads with the key alone.  T: the fixed threshold; tmax in
+    1..16: T chosen per slice instead.  Argument errors (key, nonce, index, the blind rules) are
+    raised before the GPU is touched."""
+    shape = tuple(covers.shape)
+    if len(shape) < 2:
+        raise ValueError(f"covers must be [B, H, W] or [H, W], got shape {shape}")
+    if key is None:
+        raise ValueError("encode_blind_keyed takes a 32-byte key; encode_blind is the unkeyed call")
+    _aead.check_call(key, nonce, index0, int(shape[0]) if len(shape) > 2 else 1, fresh=False)
+    mv = maxval if maxval is not None else (255 if "8" in str(covers.dtype) and "16" not in str(covers.dtype) else 65535)
+    if tmax is None:
+        _blind.check_args(scheme=1, T=T, gate=None, H=int(shape[-2]), W=int(shape[-1]), maxval=mv, max_entries=max_entries)
+    else:
+        _blind.check_args_auto(scheme=1, tmax=tmax, gate=None, H=int(shape[-2]), W=int(shape[-1]), maxval=mv,
+                               max_entries=max_entries)
+    _require_gpu()
+    covers = _as_gpu_batch(covers)
+    if isinstance(payloads, (str, bytes, bytearray)):
+        payloads = [payloads]
+    dt = "uint16" if _elem_bytes(covers) == 2 else "uint8"
+    codec = _codec_for(tuple(covers.shape), dt, T=int(T) if tmax is None else 1, tmax=16 if tmax is None else int(tmax),
+                       maxval=maxval)
+    return codec.embed_blind_keyed(covers, payloads, key=key, nonce=nonce, index0=index0, tmax=tmax,
+                                   max_entries=max_entries)
+
+
+def decode_blind_keyed(stego, key, verify=True, *, restore: bool = True):
+    """(payload_bit_lists, cover) of a keyed blind stego ([B,H,W] / [H,W] tensor or numpy array) from
+    its pixels and the key (PeeCodec.decode_blind_keyed); cover is None with restore=False."""
+    _aead.check_key(key)
+    _require_gpu()
+    stego = _as_gpu_batch(stego)
+    dt = "uint16" if _elem_bytes(stego) == 2 else "uint8"
+    codec = _codec_for(tuple(stego.shape), dt, T=2, tmax=16, maxval=None)
+    bits, cover = codec.decode_blind_keyed(stego, key, verify=verify)
     return bits, (cover if restore else None)
 
 

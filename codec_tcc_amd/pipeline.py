@@ -323,6 +323,59 @@ def decode_dicom_pee(path, verify=True) -> Tuple[np.ndarray, np.ndarray]:
     return bits[0], cover.cpu().numpy()[0]
 
 
+def encode_dicom_pee_keyed(image_or_path, payload, out_path: str, key, T: int = 2, tmax=None, nonce=None,
+                           maxval: Optional[int] = None, max_entries: int = 256) -> Dict:
+    """encode_dicom_pee under a 32-byte key (PeeCodec.embed_blind_keyed): the file's pixels
+    carry the nonce, the Poly1305 tag of (cover, ciphertext) and the encrypted payload, so
+    decode_dicom_pee_keyed needs the file and the key alone.  tmax in 1..16: T chosen on the device
+    instead of the fixed T.  The result names the T used, the nonce and the payload bits ("L";
+    "n_user" is the header's count, frame included)."""
+    from . import aead as _aead
+    from .pee import PeeCodec
+    if key is None:
+        raise ValueError("encode_dicom_pee_keyed takes a 32-byte key; encode_dicom_pee is the unkeyed call")
+    key, nonce, _i = _aead.check_call(key, nonce)   # before the GPU is touched; a fresh nonce when None
+    _require_gpu()
+    torch = _torch()
+    if isinstance(image_or_path, np.ndarray):
+        img = image_or_path
+    else:
+        img, attrs = dicom.read_dicom(image_or_path)
+        if maxval is None and attrs.get("bits_stored"):
+            maxval = (1 << int(attrs["bits_stored"])) - 1
+    if img.ndim != 2 or img.dtype not in (np.uint8, np.uint16):
+        raise ValueError("A imagem deve ser 2D uint8 ou uint16.")
+    h, w = img.shape
+    bits = framing.to_bits(payload)
+    pc = PeeCodec(1, h, w, dtype=str(img.dtype), T=T if tmax is None else 1, tmax=16 if tmax is None else tmax, maxval=maxval)
+    stego, info, ts = pc.embed_blind_keyed(torch.from_numpy(np.ascontiguousarray(img)[None]).cuda(), [bits], key=key,
+                                           nonce=nonce, tmax=tmax, max_entries=max_entries)
+    out = stego.cpu().numpy()[0]
+    size = dicom.save_dicom(out, out_path)
+    row = [int(v) for v in info.cpu().tolist()[0]]
+    return {"path": out_path, "bytes": size, "T": int(ts.cpu().tolist()[0]), "maxval": pc.maxval, "stego": out,
+            "nonce": nonce, "L": int(bits.size),
+            **dict(zip(("status", "n_user", "E", "n_side", "end", "region_row"), row))}
+
+
+def decode_dicom_pee_keyed(path, key, verify=True) -> Tuple[np.ndarray, np.ndarray]:
+    """(payload bits as a 0/1 uint8 vector, restored cover) from a DICOM written by
+    encode_dicom_pee_keyed (a path or the file's bytes) and its key: PeeCodec.decode_blind_keyed on
+    its pixels.  ValueError for an image without a keyed header (an unkeyed one is
+    decode_dicom_pee's), IntegrityError when the tag fails."""
+    from . import aead as _aead
+    from .pee import PeeCodec
+    _aead.check_key(key)
+    img, _attrs = dicom.read_dicom(path)
+    if img.ndim != 2 or img.dtype not in (np.uint8, np.uint16):
+        raise ValueError("A imagem deve ser 2D uint8 ou uint16.")
+    _require_gpu()
+    h, w = img.shape
+    pc = PeeCodec(1, h, w, dtype=str(img.dtype), T=1)
+    bits, cover = pc.decode_blind_keyed(_torch().from_numpy(np.ascontiguousarray(img)[None]).cuda(), key, verify=verify)
+    return bits[0], cover.cpu().numpy()[0]
+
+
 @dataclass
 class PeeFile:
     """The host half of a MED-PEE file decode (read_pee_bytes): everything the launch needs."""
