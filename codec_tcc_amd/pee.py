@@ -89,7 +89,8 @@ class PeeEncoded:
         """Payload bits embedded per slice (scheme 2: the passes' sum)."""
         if self.scheme == 1:
             return [int(min(r.L, r.capacity)) if r.status == 1 else int(r.L) for r in self.records()]
-        return [sum(int(pr[b].L) for pr in self.pass_records()) for b in range(len(self.lengths))]
+        prs = self.pass_records()   # one read-back
+        return [sum(int(pr[b].L) for pr in prs) for b in range(len(self.lengths))]
 
 
 _TILE_UNSET = object()   # embed(tile=) not given: checksum.TILE_DEFAULT (a ROI call with tiles insists on one)

@@ -86,12 +86,13 @@ def _check_enc(enc, covers, bits, Ts, Gs, maxval, sides=None):
     return out
 
 
-def _round_trip(covers, Ts, Gs, maxval, *, inplace=False, rule="mixed", decode_codec=None, unaligned=False):
+def _round_trip(covers, Ts, Gs, maxval, *, inplace=False, rule="mixed", decode_codec=None, unaligned=False, bits=None):
+    """bits: the slices' payloads, for a caller that brings its own (else `rule`'s)"""
     torch = pytest.importorskip("torch")
     from codec_tcc_amd import framing
     B, H, W = covers.shape
     dtype = str(covers.dtype)
-    bits = _payloads(covers, Ts, Gs, maxval, rule)
+    bits = _payloads(covers, Ts, Gs, maxval, rule) if bits is None else bits
     codec = _gated_codec(B, H, W, dtype, maxval, Ts, Gs)
     if unaligned:   # a view one pixel into its buffer: no 16-byte alignment, the scalar kernels
         flat = torch.empty(B * H * W + 1, dtype=getattr(torch, dtype), device="cuda")

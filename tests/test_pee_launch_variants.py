@@ -43,7 +43,8 @@ uint8_t, "IP" = in place and out of place, both run.
     k_pee_dcount<TT, false>, k_pee_recover<TT, false>), k_pee_embed_v, k_pee_dcount_w,
     k_pee_dcount<TT, true>, k_pee_embed<TT, true>: test_pee.py PATHS x test_gpu_matches_oracle
     the GATE = true instances (NT only): test_pee_gate.py (its knob sets cover one pass, two
-    passes with and without CODEC_PEE_FUSED / _EMBED_V / _WAVE_TILES)
+    passes with and without CODEC_PEE_FUSED / _EMBED_V / _WAVE_TILES); at batches of several slot
+    groups with a ragged last lane: test_pee_batch_dispatch.py (no knob)
   scheme 1, T = "auto" (test_auto_T)
     k_pee_embed_res<NI, NT, NTS, NTH, LIN> for the seven (NI, NTH, LIN) launches, with
         (NT, NTS) = (true, true): res_nts_*, (false, false): res_nt0_*; (true, false) is the
@@ -67,7 +68,6 @@ launch the same instance: CODEC_PEE_SSX_D=6 in place with early refill runs the 
 k_pee_extract_ss<u16, true, true, 1, true, true> is both "early ring of one, NTS = NTL = 1" and
 what a plain early ring of one would name.
 """
-import contextlib
 import functools
 
 import numpy as np
@@ -76,6 +76,7 @@ import pytest
 from codec_tcc_amd import synth
 from oracle import pee_cpu as P
 
+from pee_launches import launches as _launches
 from test_pee import _bits, _check_multi_vs_oracle
 
 BASE = (2, 67, 264)
@@ -153,23 +154,6 @@ def _cases(table):
             for name, (knobs, dtypes, places, shape) in table.items() for dt in dtypes for ip in places]
 
 
-@contextlib.contextmanager
-def _launches(seen):
-    """adds the launch families (profiling tags) recorded inside the block to `seen`"""
-    import ctypes as C
-    import torch
-    from codec_tcc_amd import _lib
-    lib = _lib.load()
-    _lib.check(lib.codec_profile_begin(64), "codec_profile_begin")
-    try:
-        yield
-    finally:
-        torch.cuda.synchronize()
-        tags = (C.c_int32 * 64)()
-        n = lib.codec_profile_end(None, tags, 64)
-        seen.update(_lib.KERNEL_TAGS.get(tags[i], str(tags[i])) for i in range(max(n, 0)))
-
-
 @functools.lru_cache(maxsize=None)
 def _covers(dtype, shape):
     bsz, h, w = shape
@@ -221,8 +205,10 @@ def _run_scheme1(codec, covers, payloads, refs, ts, inplace, route):
                                      cover=enc.stego if inplace else None)
     assert seen == route
     host = words.cpu().numpy()
-    for i, bits in enumerate(payloads):
-        np.testing.assert_array_equal(framing.unpack_bits(host[i], len(bits)), bits)
+    for i, bits in enumerate(payloads):   # side["L"] = len(bits) but on a slice that overflowed (status 1)
+        n = refs[i][1]["L"]
+        assert n == len(bits) or refs[i][1]["status"] == 1, i
+        np.testing.assert_array_equal(framing.unpack_bits(host[i], n), bits[:n])
     np.testing.assert_array_equal(cover.cpu().numpy(), covers)
 
 

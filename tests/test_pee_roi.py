@@ -119,12 +119,13 @@ def _check_enc(enc, covers, bits, Ts, Gs, rects, maxval):
     return out
 
 
-def _round_trip(covers, Ts, Gs, maxval, *, rects=None, inplace=False, rule="mixed", shift=None):
+def _round_trip(covers, Ts, Gs, maxval, *, rects=None, inplace=False, rule="mixed", shift=None, bits=None):
+    """bits: the slices' payloads, for a caller that brings its own (else `rule`'s)"""
     torch = pytest.importorskip("torch")
     from codec_tcc_amd import framing
     B, H, W = covers.shape
     rects = _rects(covers, Ts, Gs, maxval, shift=int(inplace) if shift is None else shift) if rects is None else rects
-    bits = _payloads(covers, Ts, Gs, rects, maxval, rule)
+    bits = _payloads(covers, Ts, Gs, rects, maxval, rule) if bits is None else bits
     codec = _codec(B, H, W, str(covers.dtype), maxval, Ts, Gs)
     cov = torch.from_numpy(covers).cuda()
     enc = codec.embed(cov, bits, stego=cov if inplace else None, roi=rects)
