@@ -41,6 +41,8 @@ NO_ENTRY = 0xFFFFFFFF
 FLAG_CRC = _lib.BLIND_FLAG_CRC
 FLAG_KEYED = _lib.BLIND_FLAG_KEYED
 KEYED_FRAME_BITS = _lib.BLIND_FRAME_BITS
+FLAG_VOLUME = _lib.BLIND_FLAG_VOLUME
+VOLUME_FRAME_BITS = _lib.BVOL_FRAME_BITS
 MAX_ENTRIES = _lib.BLIND_MAX_ENTRIES
 MAX_DIM = _lib.ROI_MAX_DIM
 TMAX = _lib.BLIND_TMAX
@@ -103,9 +105,16 @@ def check_args_auto(*, scheme: int, tmax, gate, H: int, W: int, maxval: int, max
                in_place=in_place)
 
 
-def _flags_error(flags: int, n_user: int, keyed: bool):
+def _flags_error(flags: int, n_user: int, keyed: bool, volume: bool = False):
     """The reason (or None) the flags of a header are refused: unkeyed, bit 0 alone is defined; keyed,
-    they are exactly FLAG_KEYED and n_user holds the frame."""
+    they are exactly FLAG_KEYED and n_user holds the frame; volume, they are FLAG_VOLUME
+    with or without bit 0 and n_user holds the 192-bit volume frame."""
+    if volume:
+        if keyed or (flags & ~FLAG_CRC) != FLAG_VOLUME:
+            return f"flags = {flags:#x} (a volume slice has bit 2, and bit 0 at most beside it)"
+        if n_user < VOLUME_FRAME_BITS:
+            return f"n_user = {n_user} (a volume slice holds the {VOLUME_FRAME_BITS} frame bits)"
+        return None
     if not keyed:
         return f"flags = {flags:#x} (bit 0 alone is defined)" if flags & ~FLAG_CRC else None
     if flags != FLAG_KEYED:
@@ -116,10 +125,11 @@ def _flags_error(flags: int, n_user: int, keyed: bool):
     return None
 
 
-def parse_header(words, H: int, W: int, vmax: int, *, keyed: bool = False) -> Dict:
+def parse_header(words, H: int, W: int, vmax: int, *, keyed: bool = False, volume: bool = False) -> Dict:
     """One slice's six header words -> {T, flags, maxval, n_user, E, end, crc, n_side, rect, L};
     ValueError naming the field for anything that is no header of an H x W slice.  keyed=True: the
-    header of a keyed slice (flags exactly FLAG_KEYED, n_user >= 224), which the default refuses."""
+    header of a keyed slice (flags exactly FLAG_KEYED, n_user >= 224), which the default refuses;
+    volume=True: that of a volume slice (flag bit 2, n_user >= 192), which the default refuses too."""
     w = [int(v) & 0xFFFFFFFF for v in list(words)[:HDR_WORDS]]
     H, W = int(H), int(W)
     hc, wc = H // 2, W // 2
@@ -129,7 +139,7 @@ def parse_header(words, H: int, W: int, vmax: int, *, keyed: bool = False) -> Di
     T, flags, maxval = w[1] & 0xFF, (w[1] >> 8) & 0xFF, w[1] >> 16
     if not 1 <= T <= 64:
         raise ValueError(f"T = {T} (1..64)")
-    why = _flags_error(flags, w[2], keyed)
+    why = _flags_error(flags, w[2], keyed, volume)
     if why:
         raise ValueError(why)
     if not 1 <= maxval <= vmax:
@@ -153,11 +163,12 @@ def parse_header(words, H: int, W: int, vmax: int, *, keyed: bool = False) -> Di
             "n_side": n_side, "rect": rect, "L": L}
 
 
-def parse_headers(hdr: np.ndarray, H: int, W: int, nbytes: int, *, keyed: bool = False) -> Dict[str, np.ndarray]:
+def parse_headers(hdr: np.ndarray, H: int, W: int, nbytes: int, *, keyed: bool = False,
+                  volume: bool = False) -> Dict[str, np.ndarray]:
     """Every slice's header (hdr: uint32 [B, >= 6] as codec_pee_blind_headers gathers them) as int64
     arrays [B] under parse_header's names ("rect": [B, 4]): parse_header's rules applied to all
     slices at once.  ValueError naming the slices that carry no header, each with parse_header's
-    reason.  keyed: parse_header's."""
+    reason.  keyed, volume: parse_header's."""
     H, W = int(H), int(W)
     hc, wc = H // 2, W // 2
     nc = hc * wc
@@ -169,18 +180,21 @@ def parse_headers(hdr: np.ndarray, H: int, W: int, nbytes: int, *, keyed: bool =
     n_side = HDR_BITS + 32 * E
     r = -(-n_side // (2 * W))
     L = n_side + n_user
-    flags_ok = ((flags == FLAG_KEYED) & (n_user >= KEYED_FRAME_BITS)) if keyed else ((flags & ~FLAG_CRC) == 0)
+    if volume:
+        flags_ok = ((flags & ~FLAG_CRC) == FLAG_VOLUME) & (n_user >= VOLUME_FRAME_BITS) & (not keyed)
+    else:
+        flags_ok = ((flags == FLAG_KEYED) & (n_user >= KEYED_FRAME_BITS)) if keyed else ((flags & ~FLAG_CRC) == 0)
     ok = ((w[:, 0] == MAGIC) & (T >= 1) & (T <= 64) & flags_ok & (maxval >= 1) & (maxval <= vmax)
           & (end < nc) & (E <= nc) & (n_side <= H * W) & (r <= hc) & (end < (hc - r) * wc) & (L <= end + 1))
     if not ok.all():
         bad = []
         for b in np.flatnonzero(~ok):
             try:
-                parse_header(w[b], H, W, vmax, keyed=keyed)
+                parse_header(w[b], H, W, vmax, keyed=keyed, volume=volume)
                 bad.append((int(b), "inconsistent header"))   # (the two statements of the rules disagree)
             except ValueError as e:
                 bad.append((int(b), str(e)))
-        raise ValueError(f"no valid {'keyed ' if keyed else ''}blind MED-PEE header in slices {[b for b, _ in bad]}: "
+        raise ValueError(f"no valid {'keyed ' if keyed else 'volume ' if volume else ''}blind MED-PEE header in slices {[b for b, _ in bad]}: "
                          + "; ".join(f"slice {b}: {why}" for b, why in bad[:4]))
     rect = np.stack([2 * (hc - r), np.zeros_like(r), np.full_like(r, H), np.full_like(r, W)], axis=1)
     return {"T": T, "flags": flags, "maxval": maxval, "n_user": n_user, "E": E, "end": end, "crc": w[:, 5],

@@ -33,11 +33,14 @@
 // length, k_blind_splice<.., true> reads the stream through the frame (no shifted copy of the row is
 // made), k_blind_pack writes the flags it is given; k_blind_frames builds the frames from the ctx block
 // and the tags, k_blind_unframe splits the rows k_blind_restore wrote into nonce12, tag and ciphertext.
+// Volumes (include/codec_tcc_blind_vol.h; codec_bvol.hip): k_blind_plan_auto, k_blind_scatter
+// and k_blind_restore take skip marks (NULL from the entries of this file) -- a marked slice is refused
+// with status 3 on the embed side and has no header on the decode side; codec_blind_int.h declares the
+// launch sequences codec_bvol.hip puts its plan between.
 // Every kernel clamps what it reads from device memory to the slice, the row and the map.
-#include "codec_common.h"
-#include "codec_tcc_blind.h"
-#include "codec_tcc_blind_auto.h"
+#include "codec_blind_int.h"
 #include "codec_tcc_blind_keyed.h"
+#include "codec_tcc_blind_vol.h"
 
 #include <limits.h>
 
@@ -48,26 +51,6 @@
 #define BL_ROWS_PER_WAVE 4
 #define BL_ROWS_PER_WG (4 * BL_ROWS_PER_WAVE)
 #define BL_U 4
-
-struct BlWs {
-    size_t rows, rect, lens, ts, gs, lm, pay, total;
-};
-// the layout behind the codec_pee workspace of P (base = codec_pee_workspace_bytes(P) > 0); the row
-// table holds `tables` T's
-static BlWs bl_ws(const codec_pee_params* P, size_t base, int tables = 1) {
-    BlWs L;
-    const size_t B = (size_t)P->B;
-    size_t o = align_up(base, 256);
-    L.rows = o; o += align_up(B * (size_t)tables * (size_t)(P->H / 2 > 0 ? P->H / 2 : 1) * 8, 256);
-    L.rect = o; o += align_up(B * 16, 256);
-    L.lens = o; o += align_up(B * 4, 256);
-    L.ts = o; o += align_up(B * 4, 256);
-    L.gs = o; o += align_up(B * 4, 256);
-    L.lm = o; o += align_up(B * (size_t)P->lm_words * 8, 256);
-    L.pay = o; o += align_up(B * (size_t)P->payload_words * 8, 256);
-    L.total = o;
-    return L;
-}
 
 __device__ __forceinline__ int bl_med3(int a, int b, int c) { return max(min(a, b), min(max(a, b), a + b - c)); }
 
@@ -427,8 +410,11 @@ __global__ __launch_bounds__(256) void k_blind_plan(const uint2* __restrict__ ro
 // one workgroup of sixteen waves per slice, wave T - 1 the plan at T over its part of the table
 // [B][tmax][hc].  The slice takes the first T whose plan has status 0, else the refusal of tmax
 // (t_out 0); info's last word is the largest capacity over the T's, curve (or NULL) [B][tmax] holds each.
+// skip (or NULL): a slice with a nonzero entry is refused with status CODEC_PEE_BLIND_SKIPPED and no bits
+// (codec_tcc_blind_vol.h: the volume plan gave it none).
 __global__ __launch_bounds__(64 * CODEC_PEE_BLIND_TMAX) void k_blind_plan_auto(
-    const uint2* __restrict__ rows, const int32_t* __restrict__ lengths, int user_bits, int frame_bits, int H, int W,
+    const uint2* __restrict__ rows, const int32_t* __restrict__ lengths, const int32_t* __restrict__ skip, int user_bits,
+    int frame_bits, int H, int W,
     int tmax, int max_entries, long long row_bits, int32_t* __restrict__ info, int32_t* __restrict__ t_out,
     int32_t* __restrict__ curve, int32_t* __restrict__ rect, int32_t* __restrict__ lens, int32_t* __restrict__ ts,
     int32_t* __restrict__ gs) {
@@ -448,6 +434,12 @@ __global__ __launch_bounds__(64 * CODEC_PEE_BLIND_TMAX) void k_blind_plan_auto(
         cap = max(cap, s_plan[T - 1].cap);
         if (s_plan[T - 1].status == 0) tstar = T;
         if (curve) curve[(size_t)b * tmax + (T - 1)] = s_plan[T - 1].cap;
+    }
+    if (skip && skip[b]) {
+        const BlPlan p = {CODEC_PEE_BLIND_SKIPPED, 0, 0, -1, 0, cap};
+        bl_plan_write(b, p, 0, tmax, cap, H, W, info, rect, lens, ts, gs);
+        t_out[b] = 0;
+        return;
     }
     bl_plan_write(b, s_plan[(tstar ? tstar : tmax) - 1], n_user, tstar ? tstar : tmax, cap, H, W, info, rect, lens, ts, gs);
     t_out[b] = tstar;
@@ -614,9 +606,11 @@ __device__ __forceinline__ BlHdr bl_hdr(const uint32_t* __restrict__ hdr, int b,
 template <typename T>
 __global__ __launch_bounds__(256) void k_blind_scatter(const T* __restrict__ stego, long long npx, int nc,
                                                        long long row_bits, const uint32_t* __restrict__ hdr,
-                                                       u64* __restrict__ lm, int lm_words) {
+                                                       const int32_t* __restrict__ skip, u64* __restrict__ lm,
+                                                       int lm_words) {
     const int b = blockIdx.y;
     const int e = (int)blockIdx.x * 256 + threadIdx.x;
+    if (skip && skip[b]) return;   // no header (codec_tcc_blind_vol.h)
     const BlHdr h = bl_hdr(hdr, b, npx, row_bits, nc);
     if (e >= h.E) return;
     const uint32_t idx = bl_get_word(stego + (size_t)b * npx, npx, BL_HDR_BITS + 32LL * e);
@@ -624,14 +618,17 @@ __global__ __launch_bounds__(256) void k_blind_scatter(const T* __restrict__ ste
     atomicOr(reinterpret_cast<u64*>(lm) + (size_t)b * lm_words + (idx >> 6), 1ull << (idx & 63));
 }
 
-// after the ROI extract: thread t restores side bit t and writes user word t; grid (max(bits, words) / 256, B)
+// after the ROI extract: thread t restores side bit t and writes user word t; grid (max(bits, words) / 256, B).
+// skip (or NULL): a slice with a nonzero entry has no side bits and a zero user row.
 template <typename T>
 __global__ __launch_bounds__(256) void k_blind_restore(T* __restrict__ cover, long long npx, int nc, long long row_bits,
-                                                       const uint32_t* __restrict__ hdr, const u64* __restrict__ rows,
-                                                       int row_words, u64* __restrict__ out, int user_words) {
+                                                       const uint32_t* __restrict__ hdr, const int32_t* __restrict__ skip,
+                                                       const u64* __restrict__ rows, int row_words, u64* __restrict__ out,
+                                                       int user_words) {
     const int b = blockIdx.y;
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    const BlHdr h = bl_hdr(hdr, b, npx, row_bits, nc);
+    BlHdr h = bl_hdr(hdr, b, npx, row_bits, nc);
+    if (skip && skip[b]) h.n_side = h.n_user = 0;
     const u64* row = rows + (size_t)b * row_words;
     if (t < h.n_side) {
         T* p = cover + (size_t)b * npx + (npx - 1 - t);
@@ -689,8 +686,7 @@ __global__ __launch_bounds__(256) void k_blind_unframe(const u64* __restrict__ r
 }
 
 // the checks every entry shares; `ws`: the entry takes the workspace
-static int blind_check(const codec_pee_params* P, int32_t max_entries, bool ws, size_t* base, const char* who,
-                       int32_t tmax = 1) {
+int blind_check(const codec_pee_params* P, int32_t max_entries, bool ws, size_t* base, const char* who, int32_t tmax) {
     if (!P) return set_err(CODEC_EINVAL, "%s: params is NULL", who);
     if (max_entries < 0 || max_entries > CODEC_PEE_BLIND_MAX_ENTRIES)
         return set_err(CODEC_EINVAL, "%s: max_entries must be in 0..65536", who);
@@ -731,11 +727,8 @@ static int blind_plan(const codec_pee_params* P, const BlWs& L, const void* cove
     return 0;
 }
 
-// the same for every T in 1..tmax: one pass over the cover, the table [B][tmax][hc], the plan that
-// picks T per slice (t_out; curve or NULL)
-static int blind_plan_auto(const codec_pee_params* P, const BlWs& L, const void* cover, const int32_t* lengths,
-                           int user_bits, int frame_bits, long long row_bits, int32_t tmax, int32_t max_entries, int32_t* info,
-                           int32_t* t_out, int32_t* curve, char* ws, hipStream_t st) {
+// the table [B][tmax][hc] for every T in 1..tmax: one pass over the cover
+int blind_rows_auto(const codec_pee_params* P, const BlWs& L, const void* cover, int32_t tmax, char* ws, hipStream_t st) {
     uint2* rows = reinterpret_cast<uint2*>(ws + L.rows);
     const int hc = P->H / 2;
     if (hc > 0) {
@@ -751,21 +744,37 @@ static int blind_plan_auto(const codec_pee_params* P, const BlWs& L, const void*
         });
         LAUNCH_CHECK("k_blind_rows_auto");
     }
-    hipLaunchKernelGGL(k_blind_plan_auto, dim3((unsigned)P->B), dim3(64 * CODEC_PEE_BLIND_TMAX), 0, st, rows, lengths,
-                       user_bits, frame_bits, P->H, P->W, (int)tmax, (int)max_entries, row_bits, info, t_out, curve,
-                       reinterpret_cast<int32_t*>(ws + L.rect),
+    return 0;
+}
+
+// the plan that picks T per slice over that table (t_out; curve or NULL; skip or NULL)
+int blind_plan_table(const codec_pee_params* P, const BlWs& L, const int32_t* lengths, const int32_t* skip, int user_bits,
+                     int frame_bits, long long row_bits, int32_t tmax, int32_t max_entries, int32_t* info, int32_t* t_out,
+                     int32_t* curve, char* ws, hipStream_t st) {
+    hipLaunchKernelGGL(k_blind_plan_auto, dim3((unsigned)P->B), dim3(64 * CODEC_PEE_BLIND_TMAX), 0, st,
+                       reinterpret_cast<const uint2*>(ws + L.rows), lengths, skip, user_bits, frame_bits, P->H, P->W, (int)tmax,
+                       (int)max_entries, row_bits, info, t_out, curve, reinterpret_cast<int32_t*>(ws + L.rect),
                        reinterpret_cast<int32_t*>(ws + L.lens), reinterpret_cast<int32_t*>(ws + L.ts),
                        reinterpret_cast<int32_t*>(ws + L.gs));
     LAUNCH_CHECK("k_blind_plan_auto");
     return 0;
 }
 
+// both: the pass over the cover, then the plan
+static int blind_plan_auto(const codec_pee_params* P, const BlWs& L, const void* cover, const int32_t* lengths,
+                           int user_bits, int frame_bits, long long row_bits, int32_t tmax, int32_t max_entries, int32_t* info,
+                           int32_t* t_out, int32_t* curve, char* ws, hipStream_t st) {
+    int rc = blind_rows_auto(P, L, cover, tmax, ws, st);
+    if (rc) return rc;
+    return blind_plan_table(P, L, lengths, nullptr, user_bits, frame_bits, row_bits, tmax, max_entries, info, t_out, curve, ws,
+                            st);
+}
+
 // after a plan: splice, the ROI embed on the plan's arrays, pack.  frames (or NULL): a keyed embed's, the
 // user stream being frames[b] || payload[b]; flags: the header's
-static int blind_embed_planned(const codec_pee_params* P, const BlWs& L, const void* cover, void* stego,
-                               const uint64_t* payload, int32_t user_words, const uint32_t* frames, const uint32_t* crc,
-                               uint32_t flags, int32_t* info,
-                               codec_pee_meta* meta, uint64_t* lm, void* workspace, size_t workspace_bytes, void* stream) {
+int blind_embed_planned(const codec_pee_params* P, const BlWs& L, const void* cover, void* stego, const uint64_t* payload,
+                        int32_t user_words, const uint32_t* frames, const uint32_t* crc, uint32_t flags, int32_t* info,
+                        codec_pee_meta* meta, uint64_t* lm, void* workspace, size_t workspace_bytes, void* stream) {
     hipStream_t st = as_stream(stream);
     char* ws = static_cast<char*>(workspace);
     u64* rows = reinterpret_cast<u64*>(ws + L.pay);
@@ -794,6 +803,45 @@ static int blind_embed_planned(const codec_pee_params* P, const BlWs& L, const v
                            P->maxval, meta, reinterpret_cast<const u64*>(lm), P->lm_words, crc, flags, info);
     });
     LAUNCH_CHECK("k_blind_pack");
+    return 0;
+}
+
+// codec_pee_blind_extract behind its checks: zero the map, scatter the entries, the ROI extract, restore
+int blind_extract_launch(const codec_pee_params* P, const BlWs& L, const void* stego, const uint32_t* hdr,
+                         const codec_pee_meta* meta, const int32_t* skip, void* cover_out, uint64_t* payload_out,
+                         int32_t user_words, void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t st = as_stream(stream);
+    char* ws = static_cast<char*>(workspace);
+    u64* lm = reinterpret_cast<u64*>(ws + L.lm);
+    u64* rows = reinterpret_cast<u64*>(ws + L.pay);
+    const long long npx = (long long)P->H * P->W, row_bits = 64LL * P->payload_words;
+    const int nc = (P->H / 2) * (P->W / 2);
+    const size_t nlm = (size_t)P->B * P->lm_words;
+    hipLaunchKernelGGL(k_blind_zero, dim3((unsigned)std::min<size_t>(4096, (nlm + 255) / 256)), dim3(256), 0, st, lm, nlm);
+    LAUNCH_CHECK("k_blind_zero");
+    const long long ebound = (row_bits - BL_HDR_BITS) / 32;   // >= 0 by the row check
+    if (ebound > 0) {
+        dim3 grid((unsigned)((ebound + 255) / 256), (unsigned)P->B);
+        pee_pixel(P->bytes, [&](auto px) {
+            using TT = decltype(px);
+            hipLaunchKernelGGL(k_blind_scatter<TT>, grid, dim3(256), 0, st, static_cast<const TT*>(stego), npx, nc, row_bits,
+                               hdr, skip, lm, P->lm_words);
+        });
+        LAUNCH_CHECK("k_blind_scatter");
+    }
+    int rc = codec_pee_roi_extract(P, stego, meta, reinterpret_cast<const uint64_t*>(lm), cover_out,
+                               reinterpret_cast<uint64_t*>(rows), workspace, workspace_bytes, stream);
+    if (rc) return rc;
+    {
+        const long long n = std::max(row_bits, (long long)user_words);
+        dim3 grid((unsigned)((n + 255) / 256), (unsigned)P->B);
+        pee_pixel(P->bytes, [&](auto px) {
+            using TT = decltype(px);
+            hipLaunchKernelGGL(k_blind_restore<TT>, grid, dim3(256), 0, st, static_cast<TT*>(cover_out), npx, nc, row_bits, hdr,
+                               skip, rows, P->payload_words, reinterpret_cast<u64*>(payload_out), (int)user_words);
+        });
+        LAUNCH_CHECK("k_blind_restore");
+    }
     return 0;
 }
 
@@ -871,39 +919,8 @@ int codec_pee_blind_extract(const codec_pee_params* P, const void* stego, const 
     const BlWs L = bl_ws(P, base);
     if (workspace_bytes < L.total) return set_err(CODEC_EINVAL, "codec_pee_blind_extract: workspace too small");
     if ((rc = pee_workspace_enter(P, workspace, stream))) return rc;
-    hipStream_t st = as_stream(stream);
-    char* ws = static_cast<char*>(workspace);
-    u64* lm = reinterpret_cast<u64*>(ws + L.lm);
-    u64* rows = reinterpret_cast<u64*>(ws + L.pay);
-    const long long npx = (long long)P->H * P->W, row_bits = 64LL * P->payload_words;
-    const int nc = (P->H / 2) * (P->W / 2);
-    const size_t nlm = (size_t)P->B * P->lm_words;
-    hipLaunchKernelGGL(k_blind_zero, dim3((unsigned)std::min<size_t>(4096, (nlm + 255) / 256)), dim3(256), 0, st, lm, nlm);
-    LAUNCH_CHECK("k_blind_zero");
-    const long long ebound = (row_bits - BL_HDR_BITS) / 32;   // >= 0 by the row check
-    if (ebound > 0) {
-        dim3 grid((unsigned)((ebound + 255) / 256), (unsigned)P->B);
-        pee_pixel(P->bytes, [&](auto px) {
-            using TT = decltype(px);
-            hipLaunchKernelGGL(k_blind_scatter<TT>, grid, dim3(256), 0, st, static_cast<const TT*>(stego), npx, nc, row_bits,
-                               hdr, lm, P->lm_words);
-        });
-        LAUNCH_CHECK("k_blind_scatter");
-    }
-    rc = codec_pee_roi_extract(P, stego, meta, reinterpret_cast<const uint64_t*>(lm), cover_out,
-                               reinterpret_cast<uint64_t*>(rows), workspace, workspace_bytes, stream);
-    if (rc) return rc;
-    {
-        const long long n = std::max(row_bits, (long long)user_words);
-        dim3 grid((unsigned)((n + 255) / 256), (unsigned)P->B);
-        pee_pixel(P->bytes, [&](auto px) {
-            using TT = decltype(px);
-            hipLaunchKernelGGL(k_blind_restore<TT>, grid, dim3(256), 0, st, static_cast<TT*>(cover_out), npx, nc, row_bits, hdr,
-                               rows, P->payload_words, reinterpret_cast<u64*>(payload_out), (int)user_words);
-        });
-        LAUNCH_CHECK("k_blind_restore");
-    }
-    return 0;
+    return blind_extract_launch(P, L, stego, hdr, meta, nullptr, cover_out, payload_out, user_words, workspace, workspace_bytes,
+                                stream);
 }
 
 // ---- include/codec_tcc_blind_auto.h

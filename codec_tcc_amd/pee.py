@@ -711,6 +711,37 @@ class PeeCodec:
         satisfied by the tag."""
         return _blind.decode_keyed(self, stego, key, cover=cover, verify=verify)
 
+    # ---- blind volume payloads: one stream across self-contained stegos (include/codec_tcc_blind_vol.h)
+    def embed_blind_volume(self, covers, payload, *, volume_id=None, policy: str = "even", tmax=None, checksum=False,
+                           max_entries: int = 256, stego=None, check: bool = True, packed=None, key=None):
+        """(stego, info, ts): one payload (str / bytes / 0-1 vector) embedded across the stack as blind
+        stegos (blind_volume.py).  The device plans the shares (embed_volume's rule on the
+        blind capacity curve less the 192 frame bits, policy "even" or "fill"), and every slice that
+        takes bits carries a frame -- volume_id, its index, B, its offset, N, the stream's CRC -- before
+        its share, so decode_blind_volume needs the pixels alone, in any order.  A slice that takes no
+        bit is copied through (ts 0, info["slices"] status 3).  info: {"volume": int32 [8] device
+        tensor (status, T*, S(T*), S(tmax), carriers, N, policy, B), "volume_id", "n", "off" (int32 [B]),
+        "frames" (int32 [B, 6]), "slices" (int32 [B, 6], embed_blind's fields)}.  A payload beyond
+        S(tmax) is refused, never truncated: the stego is the covers, and check=True (one read-back)
+        raises ValueError with N and S(tmax).  volume_id=None draws 32 random bits.  checksum=True:
+        the covers' CRC-32 in the headers and the stream's in the frames.  packed=(words, N): the
+        stream already on the device (no upload; no stream CRC).  One pass over the covers, no host
+        round trip, capturable with check=False.  key: must be None (a blind volume is unkeyed)."""
+        from . import blind_volume as _bv
+        return _bv.embed(self, covers, payload, volume_id=volume_id, policy=policy, tmax=tmax, checksum=checksum,
+                         max_entries=max_entries, stego=stego, check=check, packed=packed, key=key)
+
+    def decode_blind_volume(self, stego, *, cover=None, verify=True, partial: bool = False):
+        """(bits, covers) of embed_blind_volume's stegos from the pixels alone, the slices in any
+        order; slices without a blind header are tolerated and returned as they are.  ValueError
+        when no slice carries a frame, volumes are mixed, a carrier is duplicated or stream bits are
+        missing (the message names the ranges); a slice with a blind header that is no volume slice's
+        is a ValueError too.  partial=True: missing bits read 0 and (bits, covers, missing) is
+        returned, missing the list of uncovered ranges [lo, hi).  IntegrityError when a restored
+        cover or the stream fails the CRC-32 it carries (verify as decode_blind's)."""
+        from . import blind_volume as _bv
+        return _bv.decode(self, stego, cover=cover, verify=verify, partial=partial)
+
     def blind_capacity_curve(self, covers, tmax=None, max_entries: int = 256):
         """int32 [B, tmax] device tensor: blind_capacity at every T in 1..tmax (None: this codec's
         tmax, at most 16), from one pass over the covers."""
@@ -1121,6 +1152,37 @@ def decode_blind(stego, verify=True, *, restore: bool = True):
     codec = _codec_for(tuple(stego.shape), dt, T=2, tmax=16, maxval=None)
     bits, cover = codec.decode_blind(stego, verify=verify)
     return bits, (cover if restore else None)
+
+
+def encode_blind_volume(covers, payload, *, volume_id=None, policy: str = "even", tmax: int = 16,
+                        maxval: Optional[int] = None, checksum=False, max_entries: int = 256):
+    """One payload across a [B,H,W] stack of blind stegos (PeeCodec.embed_blind_volume): (stego, info,
+    ts).  ValueError when the payload exceeds the stack's capacity at tmax; argument errors are raised
+    before the GPU is touched."""
+    from . import blind_volume as _bv
+    shape = tuple(covers.shape)
+    if len(shape) != 3:
+        raise ValueError(f"covers must be a [B, H, W] stack, got shape {shape}")
+    mv = maxval if maxval is not None else (255 if "8" in str(covers.dtype) and "16" not in str(covers.dtype) else 65535)
+    _bv.check_args(scheme=1, tmax=tmax, gate=None, B=int(shape[0]), H=int(shape[1]), W=int(shape[2]), maxval=mv,
+                   nbits=int(framing.to_bits(payload).size), policy=policy, max_entries=max_entries, volume_id=volume_id)
+    _require_gpu()
+    covers = _as_gpu_batch(covers)
+    dt = "uint16" if _elem_bytes(covers) == 2 else "uint8"
+    codec = _codec_for(tuple(covers.shape), dt, T=1, tmax=int(tmax), maxval=maxval)
+    return codec.embed_blind_volume(covers, payload, volume_id=volume_id, policy=policy, checksum=checksum,
+                                    max_entries=max_entries)
+
+
+def decode_blind_volume(stego, verify=True, *, partial: bool = False, restore: bool = True):
+    """(bits, covers) -- with partial=True (bits, covers, missing) -- of a stack of blind volume
+    stegos in any order (PeeCodec.decode_blind_volume); covers is None with restore=False."""
+    _require_gpu()
+    stego = _as_gpu_batch(stego)
+    dt = "uint16" if _elem_bytes(stego) == 2 else "uint8"
+    codec = _codec_for(tuple(stego.shape), dt, T=2, tmax=16, maxval=None)
+    out = codec.decode_blind_volume(stego, verify=verify, partial=partial)
+    return (out[0], out[1] if restore else None) + tuple(out[2:])
 
 
 def encode_blind_keyed(covers, payloads: Sequence, key, *, T: int = 2, tmax=None, nonce=None, index0: int = 0,

@@ -323,6 +323,65 @@ def decode_dicom_pee(path, verify=True) -> Tuple[np.ndarray, np.ndarray]:
     return bits[0], cover.cpu().numpy()[0]
 
 
+def _series_pixels(items, maxval=None):
+    """([H,W] arrays stacked, maxval): a series given as arrays or DICOM paths / bytes, all of one
+    shape and dtype."""
+    imgs = []
+    for it in items:
+        if isinstance(it, np.ndarray):
+            img = it
+        else:
+            img, attrs = dicom.read_dicom(it)
+            if maxval is None and attrs.get("bits_stored"):
+                maxval = (1 << int(attrs["bits_stored"])) - 1
+        if img.ndim != 2 or img.dtype not in (np.uint8, np.uint16):
+            raise ValueError("A imagem deve ser 2D uint8 ou uint16.")
+        imgs.append(np.ascontiguousarray(img))
+    if not imgs or len({(a.shape, a.dtype) for a in imgs}) != 1:
+        raise ValueError("a series is one or more slices of one shape and dtype")
+    return np.stack(imgs), maxval
+
+
+def encode_dicom_series_pee(images_or_paths, payload, out_dir: str, tmax: int = 16, policy: str = "even",
+                            checksum: bool = True, maxval: Optional[int] = None, max_entries: int = 256,
+                            volume_id=None) -> Dict:
+    """One payload across a DICOM series as blind volume stegos (PeeCodec.embed_blind_volume; DESIGN
+    §3n): one plain DICOM per slice in out_dir (slice_00000.dcm, ...), each carrying its place in the
+    stream, so decode_dicom_series_pee reads the files back in any order.  ValueError when the payload
+    exceeds the series' capacity at tmax (nothing is written)."""
+    import os
+    from .pee import PeeCodec
+    _require_gpu()
+    torch = _torch()
+    stack, maxval = _series_pixels(images_or_paths, maxval)
+    B, h, w = stack.shape
+    pc = PeeCodec(B, h, w, dtype=str(stack.dtype), T=1, tmax=tmax, maxval=maxval)
+    stego, info, ts = pc.embed_blind_volume(torch.from_numpy(stack).cuda(), payload, volume_id=volume_id, policy=policy,
+                                            checksum=bool(checksum), max_entries=max_entries)
+    out = stego.cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    paths = [os.path.join(out_dir, f"slice_{b:05d}.dcm") for b in range(B)]
+    sizes = [dicom.save_dicom(out[b], p) for b, p in enumerate(paths)]
+    v = [int(x) for x in info["volume"].cpu().tolist()]
+    return {"paths": paths, "bytes": sizes, "volume_id": info["volume_id"], "T": v[1], "N": v[5], "carriers": v[4],
+            "capacity": v[3], "n": info["n"].cpu().tolist(), "off": info["off"].cpu().tolist(), "ts": ts.cpu().tolist(),
+            "maxval": pc.maxval, "stego": out}
+
+
+def decode_dicom_series_pee(paths, verify=True, partial: bool = False):
+    """(payload bits, restored covers [B,H,W] in the order given) from the DICOMs of
+    encode_dicom_series_pee, in any order and with unmarked slices among them
+    (PeeCodec.decode_blind_volume); partial=True also returns the missing bit ranges instead of
+    raising when slices are absent."""
+    from .pee import PeeCodec
+    stack, _mv = _series_pixels(paths)
+    _require_gpu()
+    B, h, w = stack.shape
+    pc = PeeCodec(B, h, w, dtype=str(stack.dtype), T=1)
+    out = pc.decode_blind_volume(_torch().from_numpy(stack).cuda(), verify=verify, partial=partial)
+    return (out[0], out[1].cpu().numpy()) + tuple(out[2:])
+
+
 def encode_dicom_pee_keyed(image_or_path, payload, out_path: str, key, T: int = 2, tmax=None, nonce=None,
                            maxval: Optional[int] = None, max_entries: int = 256) -> Dict:
     """encode_dicom_pee under a 32-byte key (PeeCodec.embed_blind_keyed): the file's pixels
