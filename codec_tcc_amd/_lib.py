@@ -1,7 +1,8 @@
 """ctypes binding of libcodec_hip.so (include/codec_tcc.h, include/codec_tcc_ext.h,
 include/codec_tcc_crc.h, include/codec_tcc_vol.h, include/codec_tcc_gate.h, include/codec_tcc_gvol.h,
 include/codec_tcc_tile.h, include/codec_tcc_roi.h, include/codec_tcc_aead.h, include/codec_tcc_blind.h,
-include/codec_tcc_blind_auto.h, include/codec_tcc_blind_keyed.h, include/codec_tcc_blind_vol.h).
+include/codec_tcc_blind_auto.h, include/codec_tcc_blind_keyed.h, include/codec_tcc_blind_vol.h,
+include/codec_tcc_blind_gate.h).
 
 The library is built in-tree (codec_tcc_amd/libcodec_hip.so, see build.py).  There is no
 CPU fallback: if the library cannot be loaded, every entry point raises RuntimeError.
@@ -143,7 +144,8 @@ KERNEL_TAGS = {1: "k_scan_fast", 2: "k_scan_generic", 3: "k_block_exact", 4: "k_
                41: "k_pee_gate_table", 42: "k_gvol_plan", 43: "k_tile_crc", 44: "k_tile_crc_bytes",
                45: "k_tile_compare", 46: "k_roi_bbox", 47: "k_chacha20_rows", 48: "k_poly1305_prep", 49: "k_poly1305",
                50: "k_poly1305_finish", 51: "k_aead_release", 52: "k_blind_rows", 53: "k_blind_rows_auto",
-               54: "k_bvol_plan", 55: "k_bvol_rows", 56: "k_bvol_order", 57: "k_bvol_gather"}
+               54: "k_bvol_plan", 55: "k_bvol_rows", 56: "k_bvol_order", 57: "k_bvol_gather",
+               58: "k_blind_rows_gate"}
 EXPORTS = tuple(_SIGS)
 # include/codec_tcc_ext.h: entries added after codec_tcc.h's list (EXPORTS) was fixed
 _SIGS_EXT = {
@@ -323,6 +325,17 @@ _SIGS_BLIND_VOL = {
                                                  C.c_int64, _VP, _VP, _VP, C.c_size_t, _VP]),
 }
 EXPORTS_BLIND_VOL = tuple(_SIGS_BLIND_VOL)
+# include/codec_tcc_blind_gate.h: gated blind MED-PEE (blind.py embed_gated / capacity_gated)
+BLIND_FLAG_GATED = 8              # CODEC_PEE_BLIND_FLAG_GATED
+BLIND_FLAG_GATE_SHIFT = 4         # CODEC_PEE_BLIND_FLAG_GATE_SHIFT
+_SIGS_BLIND_GATE = {
+    "codec_pee_blind_gate_workspace_bytes": (C.c_size_t, [C.POINTER(PeeParams), C.c_int32, C.c_int32]),
+    "codec_pee_blind_plan_gate": (C.c_int, [C.POINTER(PeeParams), _VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _VP,
+                                            _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "codec_pee_blind_embed_gate": (C.c_int, [C.POINTER(PeeParams), _VP, _VP, _VP, C.c_int32, _VP, _VP, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+}
+EXPORTS_BLIND_GATE = tuple(_SIGS_BLIND_GATE)
 
 _lib = None
 _load_error = None
@@ -353,7 +366,7 @@ def load(path: str = LIB_PATH):
         raise RuntimeError(f"cannot load {path}: {e}") from e
     for name, (res, args) in {**_SIGS, **_SIGS_EXT, **_SIGS_CRC, **_SIGS_VOL, **_SIGS_GATE, **_SIGS_GVOL,
                               **_SIGS_TILE, **_SIGS_ROI, **_SIGS_AEAD, **_SIGS_BLIND, **_SIGS_BLIND_AUTO,
-                              **_SIGS_BLIND_KEYED, **_SIGS_BLIND_VOL}.items():
+                              **_SIGS_BLIND_KEYED, **_SIGS_BLIND_VOL, **_SIGS_BLIND_GATE}.items():
         fn = getattr(lib, name, None)
         if fn is None:
             if name == "codec_build_digest" and not in_tree:   # a diagnostic build (tools/)

@@ -23,6 +23,14 @@ needs besides the pixels; tests/pee_blind_keyed_spec.py is the specification.
     stego, info, ts = codec.embed_blind_keyed(covers, payloads, key=key)
     bits, cover = codec.decode_blind_keyed(stego, key)
 
+Gated (include/codec_tcc_blind_gate.h): embed_gated picks, per slice and on the device,
+the pair (T, gate) -- the smallest T for which some gate of the ladder _lib.GATES has a plan, and at
+that T the smallest such gate; only candidates whose MED context is that flat are modified.  The gate
+rides in the header (flag bit 3, its ladder index in flag bits 4-7) and decode reads gated and
+ungated slices alike; tests/pee_blind_gate_spec.py is the specification.
+
+    stego, info, ts, gs = codec.embed_blind_gated(covers, payloads, tmax=8)
+
 parse_header, check_args and the geometry helpers are pure host code: no GPU, no library load.
 """
 from __future__ import annotations
@@ -43,6 +51,11 @@ FLAG_KEYED = _lib.BLIND_FLAG_KEYED
 KEYED_FRAME_BITS = _lib.BLIND_FRAME_BITS
 FLAG_VOLUME = _lib.BLIND_FLAG_VOLUME
 VOLUME_FRAME_BITS = _lib.BVOL_FRAME_BITS
+FLAG_GATED = _lib.BLIND_FLAG_GATED
+FLAG_GATE_SHIFT = _lib.BLIND_FLAG_GATE_SHIFT
+FLAG_GATE_MASK = 15 << FLAG_GATE_SHIFT
+GATES = _lib.GATES
+GATED_TMAX_DEFAULT = 4
 MAX_ENTRIES = _lib.BLIND_MAX_ENTRIES
 MAX_DIM = _lib.ROI_MAX_DIM
 TMAX = _lib.BLIND_TMAX
@@ -106,9 +119,10 @@ def check_args_auto(*, scheme: int, tmax, gate, H: int, W: int, maxval: int, max
 
 
 def _flags_error(flags: int, n_user: int, keyed: bool, volume: bool = False):
-    """The reason (or None) the flags of a header are refused: unkeyed, bit 0 alone is defined; keyed,
-    they are exactly FLAG_KEYED and n_user holds the frame; volume, they are FLAG_VOLUME
-    with or without bit 0 and n_user holds the 192-bit volume frame."""
+    """The reason (or None) the flags of a header are refused: unkeyed, bit 0 and the gate's fields
+    are defined (bit 3, and bits 4-7 beside it: DESIGN §3o); keyed, they are exactly FLAG_KEYED and
+    n_user holds the frame; volume, they are FLAG_VOLUME with or without bit 0 and
+    n_user holds the 192-bit volume frame."""
     if volume:
         if keyed or (flags & ~FLAG_CRC) != FLAG_VOLUME:
             return f"flags = {flags:#x} (a volume slice has bit 2, and bit 0 at most beside it)"
@@ -116,7 +130,12 @@ def _flags_error(flags: int, n_user: int, keyed: bool, volume: bool = False):
             return f"n_user = {n_user} (a volume slice holds the {VOLUME_FRAME_BITS} frame bits)"
         return None
     if not keyed:
-        return f"flags = {flags:#x} (bit 0 alone is defined)" if flags & ~FLAG_CRC else None
+        if flags & ~(FLAG_CRC | FLAG_GATED | FLAG_GATE_MASK):
+            return f"flags = {flags:#x} (bit 0 alone is defined)" if not flags & (FLAG_GATED | FLAG_GATE_MASK) else \
+                f"flags = {flags:#x} (bits 0 and 3 alone are defined, and bits 4-7 beside bit 3)"
+        if flags & FLAG_GATE_MASK and not flags & FLAG_GATED:
+            return f"flags = {flags:#x} (bits 4-7 hold a gate only beside bit 3)"
+        return None
     if flags != FLAG_KEYED:
         return (f"flags = {flags:#x} (a keyed slice has exactly {FLAG_KEYED:#x}" +
                 ("; an unkeyed stego is decode_blind's)" if not flags & ~FLAG_CRC else ")"))
@@ -126,7 +145,8 @@ def _flags_error(flags: int, n_user: int, keyed: bool, volume: bool = False):
 
 
 def parse_header(words, H: int, W: int, vmax: int, *, keyed: bool = False, volume: bool = False) -> Dict:
-    """One slice's six header words -> {T, flags, maxval, n_user, E, end, crc, n_side, rect, L};
+    """One slice's six header words -> {T, flags, maxval, n_user, E, end, crc, n_side, rect, L}, and
+    "G", the gate, for a gated slice (DESIGN §3o; an ungated slice's dict is what it was);
     ValueError naming the field for anything that is no header of an H x W slice.  keyed=True: the
     header of a keyed slice (flags exactly FLAG_KEYED, n_user >= 224), which the default refuses;
     volume=True: that of a volume slice (flag bit 2, n_user >= 192), which the default refuses too."""
@@ -159,15 +179,18 @@ def parse_header(words, H: int, W: int, vmax: int, *, keyed: bool = False, volum
     L = n_side + n_user
     if L > end + 1:
         raise ValueError(f"n_user = {n_user} ({L} bits cannot lie in candidates 0..{end})")
-    return {"T": T, "flags": flags, "maxval": maxval, "n_user": n_user, "E": E, "end": end, "crc": w[5],
-            "n_side": n_side, "rect": rect, "L": L}
+    out = {"T": T, "flags": flags, "maxval": maxval, "n_user": n_user, "E": E, "end": end, "crc": w[5],
+           "n_side": n_side, "rect": rect, "L": L}
+    if flags & FLAG_GATED:
+        out["G"] = GATES[(flags & FLAG_GATE_MASK) >> FLAG_GATE_SHIFT]
+    return out
 
 
 def parse_headers(hdr: np.ndarray, H: int, W: int, nbytes: int, *, keyed: bool = False,
                   volume: bool = False) -> Dict[str, np.ndarray]:
     """Every slice's header (hdr: uint32 [B, >= 6] as codec_pee_blind_headers gathers them) as int64
-    arrays [B] under parse_header's names ("rect": [B, 4]): parse_header's rules applied to all
-    slices at once.  ValueError naming the slices that carry no header, each with parse_header's
+    arrays [B] under parse_header's names ("rect": [B, 4]; without keywords also "G": the gate of a
+    gated slice, _lib.GATE_MAX of any other): parse_header's rules applied to all slices at once.  ValueError naming the slices that carry no header, each with parse_header's
     reason.  keyed, volume: parse_header's."""
     H, W = int(H), int(W)
     hc, wc = H // 2, W // 2
@@ -183,7 +206,8 @@ def parse_headers(hdr: np.ndarray, H: int, W: int, nbytes: int, *, keyed: bool =
     if volume:
         flags_ok = ((flags & ~FLAG_CRC) == FLAG_VOLUME) & (n_user >= VOLUME_FRAME_BITS) & (not keyed)
     else:
-        flags_ok = ((flags == FLAG_KEYED) & (n_user >= KEYED_FRAME_BITS)) if keyed else ((flags & ~FLAG_CRC) == 0)
+        flags_ok = ((flags == FLAG_KEYED) & (n_user >= KEYED_FRAME_BITS)) if keyed else \
+            (((flags & ~(FLAG_CRC | FLAG_GATED | FLAG_GATE_MASK)) == 0) & (((flags & FLAG_GATE_MASK) == 0) | ((flags & FLAG_GATED) != 0)))
     ok = ((w[:, 0] == MAGIC) & (T >= 1) & (T <= 64) & flags_ok & (maxval >= 1) & (maxval <= vmax)
           & (end < nc) & (E <= nc) & (n_side <= H * W) & (r <= hc) & (end < (hc - r) * wc) & (L <= end + 1))
     if not ok.all():
@@ -197,13 +221,18 @@ def parse_headers(hdr: np.ndarray, H: int, W: int, nbytes: int, *, keyed: bool =
         raise ValueError(f"no valid {'keyed ' if keyed else 'volume ' if volume else ''}blind MED-PEE header in slices {[b for b, _ in bad]}: "
                          + "; ".join(f"slice {b}: {why}" for b, why in bad[:4]))
     rect = np.stack([2 * (hc - r), np.zeros_like(r), np.full_like(r, H), np.full_like(r, W)], axis=1)
-    return {"T": T, "flags": flags, "maxval": maxval, "n_user": n_user, "E": E, "end": end, "crc": w[:, 5],
-            "n_side": n_side, "rect": rect, "L": L}
+    out = {"T": T, "flags": flags, "maxval": maxval, "n_user": n_user, "E": E, "end": end, "crc": w[:, 5],
+           "n_side": n_side, "rect": rect, "L": L}
+    if not keyed and not volume:   # those refuse a gated slice: their arrays are what they were
+        out["G"] = np.where((flags & FLAG_GATED) != 0, np.asarray(GATES, np.int64)[(flags & FLAG_GATE_MASK) >> FLAG_GATE_SHIFT],
+                            _lib.GATE_MAX)
+    return out
 
 
 def records_bytes(heads: Dict[str, np.ndarray], H: int, W: int) -> bytes:
     """The codec_pee_meta records of checked headers, as pee_checks.make_record(..., status=0, roi=rect)
-    writes them (B records of 16 int32 words), built for all slices at once."""
+    writes them (B records of 16 int32 words), built for all slices at once; reserved[1] is each
+    slice's gate + 1 (65536 for an ungated one, and for headers parsed without a "G")."""
     B = heads["T"].shape[0]
     nc = (int(H) // 2) * (int(W) // 2)
     m = np.zeros((B, _lib.PEE_META_BYTES // 4), dtype=np.int64)
@@ -213,7 +242,7 @@ def records_bytes(heads: Dict[str, np.ndarray], H: int, W: int) -> bytes:
     m[:, 6] = np.where(end >= 0, end // 1024, -1)
     m[:, 8], m[:, 10], m[:, 11] = heads["L"], int(H), int(W)
     m[:, 13] = (rect[:, 0] << 16) | rect[:, 1]
-    m[:, 14] = _lib.GATE_MAX + 1
+    m[:, 14] = (heads["G"] if "G" in heads else _lib.GATE_MAX) + 1
     m[:, 15] = (rect[:, 2] << 16) | rect[:, 3]
     return (m & 0xFFFFFFFF).astype("<u4").tobytes()
 
@@ -561,3 +590,112 @@ def decode_keyed(codec, stego, key, *, cover=None, verify=True):
                 f"keyed blind MED-PEE decode: authentication failed in slices {bad} (Poly1305 tag mismatch: wrong key, or "
                 "cover / payload / nonce / tag altered)", slices=bad, keyed=True, rows=rows)
     return [framing.unpack_bits(rows[b], n_ct[b]) for b in range(B)], cover
+
+
+# ---------------------------------------------------------------- gated: (T, gate) chosen per slice
+def gate_index(gate) -> int:
+    """The ladder index of a gate value; ValueError naming the ladder for any other value."""
+    if isinstance(gate, (bool, str)) or gate is None or gate != int(gate) or int(gate) not in GATES:
+        raise ValueError(f"gated blind MED-PEE takes gate='auto' or a value of the ladder {GATES} "
+                         f"(the header carries its index), got {gate!r}")
+    return GATES.index(int(gate))
+
+
+def check_args_gated(*, scheme: int, tmax, T=None, gate="auto", H: int, W: int, maxval: int, max_entries: int = 256,
+                     roi=None, key=None, in_place: bool = False):
+    """The argument rules of the gated blind calls, as ValueError before anything is queued, in
+    check_args_auto's order with the gated calls' own T and gate in their places: scheme, tmax, T
+    (None, or an integer in 1..tmax), gate ("auto" or a ladder value), roi / key, the shape, maxval,
+    max_entries, in place.  Returns (t_fixed, j_fixed) as the library takes them (0 / -1: free)."""
+    if int(scheme) == 1 and (isinstance(tmax, (bool, str)) or int(tmax) != tmax or not 1 <= int(tmax) <= TMAX):
+        raise ValueError(f"gated blind MED-PEE chooses T in 1..tmax with tmax an integer in 1..{TMAX}, got {tmax!r}")
+    t_fixed = 0
+    if int(scheme) == 1 and T is not None:
+        if isinstance(T, (bool, str)) or int(T) != T or not 1 <= int(T) <= int(tmax):
+            raise ValueError(f"gated blind MED-PEE takes T=None or an integer in 1..tmax = {int(tmax)}, got {T!r}")
+        t_fixed = int(T)
+    j_fixed = -1 if int(scheme) != 1 or (isinstance(gate, str) and gate == "auto") else gate_index(gate)
+    check_args(scheme=scheme, T=1, gate=None, H=H, W=W, maxval=maxval, max_entries=max_entries, roi=roi, key=key,
+               in_place=in_place)
+    return t_fixed, j_fixed
+
+
+def _gated_args(codec, tmax, T, gate, max_entries: int = 256, in_place: bool = False):
+    tmax = GATED_TMAX_DEFAULT if tmax is None else tmax
+    t_fixed, j_fixed = check_args_gated(scheme=codec.scheme, tmax=tmax, T=T, gate=gate, H=codec.H, W=codec.W,
+                                        maxval=codec.maxval, max_entries=max_entries, in_place=in_place)
+    return int(tmax), t_fixed, j_fixed
+
+
+def _workspace_gated(codec, pw: int, max_entries: int, tmax: int):
+    """_workspace for the gated calls: the table of every (T, gate class) behind the blind workspace."""
+    from collections import OrderedDict
+    from .codec import _stream, _torch
+    cache = codec.__dict__.setdefault("_ws_blind", OrderedDict())
+    key = (int(pw), int(max_entries), int(tmax), "gated")
+    if key not in cache:
+        P = _params_auto(codec, pw)
+        n = int(_lib.load().codec_pee_blind_gate_workspace_bytes(C.byref(P), int(tmax), int(max_entries)))
+        if n == 0:
+            _lib.check(-1, "codec_pee_blind_gate_workspace_bytes")
+        ws = _torch().empty(n, dtype=_torch().uint8, device=codec.device)
+        _lib.check(_lib.load().codec_pee_reset(C.byref(P), ws.data_ptr(), ws.numel(), _stream()), "codec_pee_reset")
+        cache[key] = ws
+        while len(cache) > 4:
+            cache.popitem(last=False)
+    cache.move_to_end(key)
+    return cache[key]
+
+
+def embed_gated(codec, covers, payloads, *, gate="auto", T=None, tmax=None, stego=None, packed=None, checksum=False,
+                max_entries: int = 256, check: bool = True):
+    from . import checksum as _ck
+    from .codec import _stream, _torch
+    from .pee_checks import check_buffers
+    torch = _torch()
+    if checksum not in (False, True):
+        raise ValueError("embed_blind_gated takes checksum=True or False (the header holds the cover's CRC-32 alone)")
+    tmax, t_fixed, j_fixed = _gated_args(codec, tmax, T, gate, max_entries)
+    check_buffers(codec.device, codec.B, codec.H, codec.W, codec.bytes, lm_words=codec.lm_words, scheme=1,
+                  covers=covers, stego=stego, packed=packed)
+    _gated_args(codec, tmax, T, gate, max_entries, in_place=stego is not None and stego.data_ptr() == covers.data_ptr())
+    words, lengths, lens_t = packed if packed is not None else codec.pack_payloads(payloads)
+    n_max = max([int(n) for n in lengths] + [0])
+    if n_max > 64 * int(words.shape[1]):
+        raise ValueError(f"a payload of {n_max} bits does not fit the packed rows' {64 * int(words.shape[1])}")
+    pw = row_words(n_max, max_entries)
+    crc = _ck.crc32_slices(covers) if checksum else None   # queued first, as embed_blind does
+    if stego is None:
+        stego = torch.empty_like(covers)
+    ws = _workspace_gated(codec, pw, max_entries, tmax)
+    info = torch.empty((codec.B, _lib.BLIND_INFO_WORDS), dtype=torch.int32, device=codec.device)
+    ts = torch.empty((codec.B,), dtype=torch.int32, device=codec.device)
+    gs = torch.empty((codec.B,), dtype=torch.int32, device=codec.device)
+    lm = torch.empty((codec.B, codec.lm_words), dtype=torch.int64, device=codec.device)
+    meta = torch.empty((codec.B, _lib.PEE_META_BYTES), dtype=torch.uint8, device=codec.device)
+    P = _params_auto(codec, pw)
+    _guarded(codec, ws, pw, lambda: _lib.check(_lib.load().codec_pee_blind_embed_gate(
+        C.byref(P), covers.data_ptr(), stego.data_ptr(), words.data_ptr(), int(words.shape[1]), lens_t.data_ptr(),
+        None if crc is None else crc.data_ptr(), tmax, t_fixed, j_fixed, int(max_entries), info.data_ptr(), ts.data_ptr(),
+        gs.data_ptr(), meta.data_ptr(), lm.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "codec_pee_blind_embed_gate"))
+    out = info[:, :len(INFO_FIELDS)]
+    if check:
+        raise_status(out[:, 0].cpu().tolist(), "embed_blind_gated")   # one read-back
+    return stego, out, ts, gs
+
+
+def capacity_gated(codec, covers, tmax=None, max_entries: int = 256):
+    from .codec import _stream, _torch
+    torch = _torch()
+    tmax, _t, _j = _gated_args(codec, tmax, None, "auto", max_entries)
+    codec._check_buffers(covers=covers)
+    pw = row_words(0, max_entries)
+    ws = _workspace_gated(codec, pw, max_entries, tmax)
+    info = torch.empty((codec.B, _lib.BLIND_INFO_WORDS), dtype=torch.int32, device=codec.device)
+    ts = torch.empty((codec.B,), dtype=torch.int32, device=codec.device)
+    gs = torch.empty((codec.B,), dtype=torch.int32, device=codec.device)
+    curve = torch.empty((codec.B, tmax, len(GATES)), dtype=torch.int32, device=codec.device)
+    _guarded(codec, ws, pw, lambda: _lib.check(_lib.load().codec_pee_blind_plan_gate(
+        C.byref(_params_auto(codec, pw)), covers.data_ptr(), None, tmax, 0, -1, int(max_entries), info.data_ptr(),
+        ts.data_ptr(), gs.data_ptr(), curve.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "codec_pee_blind_plan_gate"))
+    return curve

@@ -28,7 +28,7 @@ SRCS = [os.path.join(HERE, "csrc", "codec_hip.hip"), os.path.join(HERE, "csrc", 
         os.path.join(HERE, "csrc", "codec_gate.hip"), os.path.join(HERE, "csrc", "codec_gvol.hip"),
         os.path.join(HERE, "csrc", "codec_tile.hip"), os.path.join(HERE, "csrc", "codec_roi.hip"),
         os.path.join(HERE, "csrc", "codec_aead.hip"), os.path.join(HERE, "csrc", "codec_blind.hip"),
-        os.path.join(HERE, "csrc", "codec_bvol.hip")]
+        os.path.join(HERE, "csrc", "codec_bvol.hip"), os.path.join(HERE, "csrc", "codec_blind_gate.hip")]
 HDRS = [os.path.join(HERE, "csrc", "codec_common.h"), os.path.join(HERE, "csrc", "codec_crc_gf2.h"),
         os.path.join(HERE, "csrc", "codec_vol_checks.h"), os.path.join(HERE, "csrc", "codec_blind_int.h")]
 OUT = os.path.join(HERE, "libcodec_hip.so")
@@ -62,7 +62,7 @@ def _common_deps():
                    os.path.join(INC, "codec_tcc_tile.h"), os.path.join(INC, "codec_tcc_roi.h"),
                    os.path.join(INC, "codec_tcc_aead.h"), os.path.join(INC, "codec_tcc_blind.h"),
                    os.path.join(INC, "codec_tcc_blind_auto.h"), os.path.join(INC, "codec_tcc_blind_keyed.h"),
-                   os.path.join(INC, "codec_tcc_blind_vol.h")]
+                   os.path.join(INC, "codec_tcc_blind_vol.h"), os.path.join(INC, "codec_tcc_blind_gate.h")]
 
 
 def _digest(paths, flags) -> str:

@@ -36,7 +36,9 @@
 // Volumes (include/codec_tcc_blind_vol.h; codec_bvol.hip): k_blind_plan_auto, k_blind_scatter
 // and k_blind_restore take skip marks (NULL from the entries of this file) -- a marked slice is refused
 // with status 3 on the embed side and has no header on the decode side; codec_blind_int.h declares the
-// launch sequences codec_bvol.hip puts its plan between.
+// launch sequences codec_bvol.hip puts its plan between and the plan rule's device functions.
+// Gated (include/codec_tcc_blind_gate.h; codec_blind_gate.hip): k_blind_pack takes flag bits of
+// each slice's own (NULL from the entries of this file), which carry the gate.
 // Every kernel clamps what it reads from device memory to the slice, the row and the map.
 #include "codec_blind_int.h"
 #include "codec_tcc_blind_keyed.h"
@@ -46,22 +48,10 @@
 
 #include <algorithm>
 
-#define BL_HDR_BITS 192
 #define BL_PAD 0xFFFFFFFFu
 #define BL_ROWS_PER_WAVE 4
 #define BL_ROWS_PER_WG (4 * BL_ROWS_PER_WAVE)
 #define BL_U 4
-
-__device__ __forceinline__ int bl_med3(int a, int b, int c) { return max(min(a, b), min(max(a, b), a + b - c)); }
-
-template <typename V> __device__ __forceinline__ uint32_t bl_px(const V& v, int e);
-template <> __device__ __forceinline__ uint32_t bl_px<uint4>(const uint4& v, int e) {
-    const uint32_t w = e < 2 ? v.x : (e < 4 ? v.y : (e < 6 ? v.z : v.w));
-    return (e & 1) ? (w >> 16) : (w & 0xFFFFu);
-}
-template <> __device__ __forceinline__ uint32_t bl_px<uint2>(const uint2& v, int e) {
-    return ((e < 4 ? v.x : v.y) >> (8 * (e & 3))) & 0xFFu;
-}
 
 // oracle/pee_cpu.py classify: (expandable and safe) + (unsafe << 16) of one candidate
 __device__ __forceinline__ uint32_t bl_class(int x, int a, int b, int c, int T, int maxval) {
@@ -269,46 +259,6 @@ __global__ __launch_bounds__(256) void k_blind_rows_auto(const T* __restrict__ i
     }
 }
 
-// the plan of one slice at one T
-struct BlPlan {
-    int status, E, n_side, istar, y0, cap;
-};
-
-// one row of the plan rule: the row's counts through row i -> (side bits, room for user bits, rows reserved)
-struct BlRow {
-    long long side, room, rr;
-};
-__device__ __forceinline__ BlRow bl_plan_row(uint32_t cap, uint32_t uns, int W) {
-    BlRow r;
-    r.side = BL_HDR_BITS + 32LL * uns;
-    r.room = (long long)cap - r.side;
-    r.rr = (r.side + 2LL * W - 1) / (2LL * W);
-    return r;
-}
-// the largest n_user the row would take, or -1
-__device__ __forceinline__ int bl_plan_cap(const BlRow& r, int i, uint32_t uns, int hc, int max_entries, long long row_bits) {
-    return (i < hc - r.rr && uns <= (uint32_t)max_entries && r.side <= row_bits && r.room >= 0)
-               ? (int)min(r.room, row_bits - r.side) : -1;
-}
-// the plan from the first row that has room (first = row << 32 | unsafe through it, or ~0) and the capacity
-__device__ BlPlan bl_plan_decide(u64 first, int cap, int hc, long long n_user, int W, int max_entries, long long row_bits) {
-    BlPlan p = {0, 0, 0, -1, 0, cap};
-    if (first == ~0ull) {
-        p.status = 1;
-    } else {
-        p.istar = (int)(first >> 32);
-        const long long e = (long long)(first & 0xFFFFFFFFull);
-        const long long side = BL_HDR_BITS + 32 * e;
-        const long long rr = (side + 2LL * W - 1) / (2LL * W);
-        p.E = (int)min(e, (long long)INT_MAX);
-        if (p.istar >= hc - rr) p.status = 1;
-        else if (e > max_entries) p.status = 2;
-        else if (side + n_user > row_bits) p.status = 1;   // a row narrower than the call's lengths: the host sizes it
-        else { p.n_side = (int)side; p.y0 = 2 * (hc - (int)rr); }
-    }
-    return p;
-}
-
 // the plan rule over one slice's row table at one T (rows: its hc entries), by all 256 threads of a
 // workgroup, every one of which gets the result.  An entry is clamped to the row's W / 2 candidates.
 __device__ BlPlan bl_plan_rows(const uint2* __restrict__ rows, int hc, long long n_user, int W, int max_entries,
@@ -337,58 +287,6 @@ __device__ BlPlan bl_plan_rows(const uint2* __restrict__ rows, int hc, long long
     }
     __syncthreads();
     return bl_plan_decide(*s_first, *s_cap, hc, n_user, W, max_entries, row_bits);
-}
-
-// the same by one wave, with shuffles alone: no shared memory, no barrier
-__device__ BlPlan bl_plan_rows_wave(const uint2* __restrict__ rows, int hc, long long n_user, int W, int max_entries,
-                                    long long row_bits) {
-    const int lane = threadIdx.x & 63;
-    const uint32_t wc = (uint32_t)W / 2;
-    uint32_t cap0 = 0, uns0 = 0;
-    int best = -1;
-    u64 first = ~0ull;
-    for (int c0 = 0; c0 < hc; c0 += 64) {
-        const int i = c0 + lane;
-        uint2 v = i < hc ? rows[i] : make_uint2(0u, 0u);
-        v.x = min(v.x, wc);
-        v.y = min(v.y, wc);
-        const uint32_t cap = cap0 + wave_incl_scan(v.x), uns = uns0 + wave_incl_scan(v.y);   // through row i
-        bool hit = false;
-        if (i < hc) {
-            const BlRow r = bl_plan_row(cap, uns, W);
-            best = max(best, bl_plan_cap(r, i, uns, hc, max_entries, row_bits));
-            hit = r.room >= n_user;
-        }
-        const u64 hits = __ballot(hit);
-        if (first == ~0ull && hits) {   // uniform: the first row with room, and the unsafe count through it
-            const int l = __ffsll((long long)hits) - 1;
-            first = ((u64)(uint32_t)(c0 + l) << 32) | (uint32_t)__shfl(uns, l, 64);
-        }
-        cap0 = (uint32_t)__shfl(cap, 63, 64);
-        uns0 = (uint32_t)__shfl(uns, 63, 64);
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) best = max(best, __shfl_xor(best, o, 64));
-    return bl_plan_decide(first, best, hc, n_user, W, max_entries, row_bits);
-}
-
-// info and the ROI embed's arrays of slice b (one thread); thr: the T the ROI embed and the header take
-__device__ void bl_plan_write(int b, const BlPlan& p, long long n_user, int thr, int cap, int H, int W,
-                              int32_t* __restrict__ info, int32_t* __restrict__ rect, int32_t* __restrict__ lens,
-                              int32_t* __restrict__ ts, int32_t* __restrict__ gs) {
-    int32_t* I = info + (size_t)b * CODEC_PEE_BLIND_INFO_WORDS;
-    I[0] = p.status; I[1] = (int)n_user; I[2] = p.E; I[3] = p.n_side; I[4] = -1; I[5] = p.y0; I[6] = p.istar; I[7] = cap;
-    const bool ok = p.status == 0;
-    rect[4 * b] = ok ? p.y0 : 0; rect[4 * b + 1] = 0; rect[4 * b + 2] = ok ? H : 0; rect[4 * b + 3] = ok ? W : 0;
-    lens[b] = ok ? p.n_side + (int)n_user : 0;
-    ts[b] = thr;
-    gs[b] = CODEC_PEE_GATE_MAX;
-}
-
-// n_user of slice b: lengths NULL: 0 user bits; else the length clamped to 0 .. user_bits, behind
-// frame_bits bits of frame (0, or a keyed slice's 224)
-__device__ __forceinline__ long long bl_n_user(const int32_t* __restrict__ lengths, int b, int user_bits, int frame_bits) {
-    return lengths ? (long long)frame_bits + (long long)min(max(lengths[b], 0), user_bits) : 0;
 }
 
 // one workgroup per slice
@@ -530,13 +428,14 @@ __device__ __forceinline__ uint32_t bl_get_word(const T* __restrict__ px, long l
 
 // one workgroup per slice, after the ROI embed: header, entries, padding; info's `end`.  ts: the
 // plan's T per slice (clamped to the header's 1..64); flags: the header's (word 5 is crc[b] when they
-// have CODEC_PEE_BLIND_FLAG_CRC and crc is given, else 0)
+// have CODEC_PEE_BLIND_FLAG_CRC and crc is given, else 0); flags_b (or NULL): flag bits of each slice's
+// own, or-ed in (codec_tcc_blind_gate.h: the gate)
 template <typename T>
 __global__ __launch_bounds__(256) void k_blind_pack(T* __restrict__ stego, long long npx, int nc,
                                                     const int32_t* __restrict__ ts, int maxval,
                                                     const codec_pee_meta* __restrict__ meta, const u64* __restrict__ lm,
                                                     int lm_words, const uint32_t* __restrict__ crc, uint32_t flags,
-                                                    int32_t* __restrict__ info) {
+                                                    const uint32_t* __restrict__ flags_b, int32_t* __restrict__ info) {
     __shared__ uint32_t sh[256 / 64 + 1];
     const int b = blockIdx.x, tid = threadIdx.x;
     int32_t* I = info + (size_t)b * CODEC_PEE_BLIND_INFO_WORDS;
@@ -546,6 +445,7 @@ __global__ __launch_bounds__(256) void k_blind_pack(T* __restrict__ stego, long 
     T* px = stego + (size_t)b * npx;
     if (tid < CODEC_PEE_BLIND_HDR_WORDS) {
         const int thr = min(max(ts[b], 1), 64);
+        if (flags_b) flags |= flags_b[b];
         const uint32_t hw[CODEC_PEE_BLIND_HDR_WORDS] = {
             CODEC_PEE_BLIND_MAGIC,
             (uint32_t)thr | ((flags & 0xFFu) << 8) | ((uint32_t)maxval << 16),
@@ -774,7 +674,8 @@ static int blind_plan_auto(const codec_pee_params* P, const BlWs& L, const void*
 // user stream being frames[b] || payload[b]; flags: the header's
 int blind_embed_planned(const codec_pee_params* P, const BlWs& L, const void* cover, void* stego, const uint64_t* payload,
                         int32_t user_words, const uint32_t* frames, const uint32_t* crc, uint32_t flags, int32_t* info,
-                        codec_pee_meta* meta, uint64_t* lm, void* workspace, size_t workspace_bytes, void* stream) {
+                        codec_pee_meta* meta, uint64_t* lm, void* workspace, size_t workspace_bytes, void* stream,
+                        const uint32_t* flags_b) {
     hipStream_t st = as_stream(stream);
     char* ws = static_cast<char*>(workspace);
     u64* rows = reinterpret_cast<u64*>(ws + L.pay);
@@ -800,7 +701,7 @@ int blind_embed_planned(const codec_pee_params* P, const BlWs& L, const void* co
     pee_pixel(P->bytes, [&](auto px) {
         using TT = decltype(px);
         hipLaunchKernelGGL(k_blind_pack<TT>, dim3((unsigned)P->B), dim3(256), 0, st, static_cast<TT*>(stego), npx, nc, ts,
-                           P->maxval, meta, reinterpret_cast<const u64*>(lm), P->lm_words, crc, flags, info);
+                           P->maxval, meta, reinterpret_cast<const u64*>(lm), P->lm_words, crc, flags, flags_b, info);
     });
     LAUNCH_CHECK("k_blind_pack");
     return 0;

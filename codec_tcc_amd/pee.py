@@ -685,6 +685,25 @@ class PeeCodec:
         return _blind.embed_auto(self, covers, payloads, tmax=tmax, stego=stego, packed=packed, checksum=checksum,
                                  max_entries=max_entries, check=check)
 
+    def embed_blind_gated(self, covers, payloads, *, gate="auto", T=None, tmax=None, stego=None, packed=None,
+                          checksum=False, max_entries: int = 256, check: bool = True):
+        """(stego, info, ts, gs): embed_blind with the pair (T, gate) chosen per slice on the device
+        (include/codec_tcc_blind_gate.h): over T in 1..tmax (None: 4) and the gates of the
+        ladder _lib.GATES, the smallest T for which some gate has a plan, and at that T the smallest
+        such gate; only candidates whose MED context is that flat are modified, and the gate rides
+        in the slice's header, so decode_blind reads the stego as it is.  ts / gs: int32 [B] device
+        tensors, the chosen T and gate (0 and -1: refused, the slice is copied through with no
+        header).  T= (an integer in 1..tmax) or gate= (a ladder value; anything else is a ValueError
+        naming the ladder) fixes one of the two, or both.  The codec's own T and gate are ignored;
+        every other rule of embed_blind holds."""
+        return _blind.embed_gated(self, covers, payloads, gate=gate, T=T, tmax=tmax, stego=stego, packed=packed,
+                                  checksum=checksum, max_entries=max_entries, check=check)
+
+    def blind_capacity_gated(self, covers, tmax=None, max_entries: int = 256):
+        """int32 [B, tmax, 16] device tensor: the most user bits embed_blind_gated takes per slice at
+        every (T in 1..tmax, gate _lib.GATES[j]), -1 where not even 0 bits fit (tmax None: 4)."""
+        return _blind.capacity_gated(self, covers, tmax, max_entries)
+
     def embed_blind_keyed(self, covers, payloads, *, key, nonce=None, index0: int = 0, tmax=None, stego=None, packed=None,
                           max_entries: int = 256, check: bool = True):
         """(stego, info, ts): a blind stego that is confidential and authenticated under a 32-byte key
@@ -1141,6 +1160,27 @@ def encode_blind_auto(covers, payloads: Sequence, *, tmax: int = 16, maxval: Opt
     dt = "uint16" if _elem_bytes(covers) == 2 else "uint8"
     codec = _codec_for(tuple(covers.shape), dt, T=1, tmax=int(tmax), maxval=maxval)
     return codec.embed_blind_auto(covers, payloads, checksum=checksum, max_entries=max_entries)
+
+
+def encode_blind_gated(covers, payloads: Sequence, *, gate="auto", T=None, tmax: int = 4, maxval: Optional[int] = None,
+                       checksum=False, max_entries: int = 256):
+    """encode_blind with (T, gate) chosen per slice (PeeCodec.embed_blind_gated): (stego, info, ts, gs);
+    decode_blind reads the stego as it is.  Raises ValueError naming the slices that no pair serves;
+    argument errors are raised before the GPU is touched."""
+    shape = tuple(covers.shape)
+    if len(shape) < 2:
+        raise ValueError(f"covers must be [B, H, W] or [H, W], got shape {shape}")
+    mv = maxval if maxval is not None else (255 if "8" in str(covers.dtype) and "16" not in str(covers.dtype) else 65535)
+    _blind.check_args_gated(scheme=1, tmax=tmax, T=T, gate=gate, H=int(shape[-2]), W=int(shape[-1]), maxval=mv,
+                            max_entries=max_entries)
+    _require_gpu()
+    covers = _as_gpu_batch(covers)
+    if isinstance(payloads, (str, bytes, bytearray)):
+        payloads = [payloads]
+    dt = "uint16" if _elem_bytes(covers) == 2 else "uint8"
+    codec = _codec_for(tuple(covers.shape), dt, T=1, tmax=16, maxval=maxval)
+    return codec.embed_blind_gated(covers, payloads, gate=gate, T=T, tmax=int(tmax), checksum=checksum,
+                                   max_entries=max_entries)
 
 
 def decode_blind(stego, verify=True, *, restore: bool = True):

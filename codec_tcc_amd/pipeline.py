@@ -307,6 +307,34 @@ def encode_dicom_pee_auto(image_or_path, payload, out_path: str, tmax: int = 16,
             **dict(zip(("status", "L", "E", "n_side", "end", "region_row"), row))}
 
 
+def encode_dicom_pee_gated(image_or_path, payload, out_path: str, tmax: int = 4, gate="auto", T=None, checksum: bool = True,
+                           maxval: Optional[int] = None, max_entries: int = 256) -> Dict:
+    """encode_dicom_pee with (T, gate) chosen on the device (PeeCodec.embed_blind_gated):
+    only candidates in flat surroundings are modified.  The result's "T" and "G" are the chosen pair;
+    decode_dicom_pee reads the file as it is.  ValueError when no pair serves."""
+    from .pee import PeeCodec
+    _require_gpu()
+    torch = _torch()
+    if isinstance(image_or_path, np.ndarray):
+        img = image_or_path
+    else:
+        img, attrs = dicom.read_dicom(image_or_path)
+        if maxval is None and attrs.get("bits_stored"):
+            maxval = (1 << int(attrs["bits_stored"])) - 1
+    if img.ndim != 2 or img.dtype not in (np.uint8, np.uint16):
+        raise ValueError("A imagem deve ser 2D uint8 ou uint16.")
+    h, w = img.shape
+    bits = framing.to_bits(payload)
+    pc = PeeCodec(1, h, w, dtype=str(img.dtype), T=1, maxval=maxval)
+    stego, info, ts, gs = pc.embed_blind_gated(torch.from_numpy(np.ascontiguousarray(img)[None]).cuda(), [bits], gate=gate, T=T,
+                                               tmax=tmax, checksum=bool(checksum), max_entries=max_entries)
+    out = stego.cpu().numpy()[0]
+    size = dicom.save_dicom(out, out_path)
+    row = [int(v) for v in info.cpu().tolist()[0]]
+    return {"path": out_path, "bytes": size, "T": int(ts.cpu().tolist()[0]), "G": int(gs.cpu().tolist()[0]),
+            "maxval": pc.maxval, "stego": out, **dict(zip(("status", "L", "E", "n_side", "end", "region_row"), row))}
+
+
 def decode_dicom_pee(path, verify=True) -> Tuple[np.ndarray, np.ndarray]:
     """(payload bits as a 0/1 uint8 vector, restored cover) from a DICOM written by
     encode_dicom_pee (a path or the file's bytes): PeeCodec.decode_blind on its pixels.  ValueError
